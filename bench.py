@@ -25,6 +25,14 @@ GPU sees the corpus' mix; orphan ordinals r*n .. (r+1)*n-1) — independent
 units for hashing (no collective), one all-to-all exchange for the c3/c5
 dedup; value = all ranks' files / max-over-ranks time.
 
+A plain run sets up, warms up, times `--steps` steps and prints the line
+(value, ms_per_step, blake3_gbps and the roofline of the timed steps' own
+kernel times); `--dump-outputs DIR` also writes what the last timed step
+computed (dump_outputs: cas keys, dedup links and counts, c4 digests) as .npy
+files, the same inputs on every run. Everything else below — cpu_baseline,
+parity, e2e, sustained, the dedup's timing and exchange figures — takes runs
+of its own after the timed steps and is measured only with `--full`.
+
 Extra fields: blake3_gbps, roofline (leaf/tree kernel, HIP events on its
 stream; bound "valu": BLAKE3 is integer ARX, so achieved = compressions x
 680 int32 lane-ops / kernel time against the spec VALU rate 256 CU x 4 SIMD
@@ -165,6 +173,48 @@ def digest_keys(dig):
     for b in range(8):
         gk = (gk << np.uint64(8)) | dig[:, b].astype(np.uint64)
     return gk
+
+
+DUMP_BUDGET = 60_000_000  # bytes of .npy data per run (all ranks together; under 64 MB with the file headers)
+DUMP_SEED = 0x5D0D
+
+
+def u64_words(a):
+    """64-bit integers (cas keys, dedup links) as float64[n, 2]: the high and
+    the low 32 bits of each, as unsigned values — exact in float64, where the
+    64-bit value itself is not"""
+    u = np.ascontiguousarray(a).view(np.uint64)
+    return np.stack([(u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1)
+
+
+def dump_outputs(outdir, per_file, other=None, rank=0, world=1):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy
+    (float32 / float64; at N > 1 every rank writes its own <name>.rank<r>.npy).
+    per_file: arrays with one row per file; other: small arrays written whole.
+    At most DUMP_BUDGET bytes per run: when the per-file arrays are larger,
+    the same seeded sample of rows (ascending, the same for every build and
+    run with these arguments) is taken of each, its row numbers written
+    beside them as sample_rows. -> {file name: shape}"""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = dict(other or {})
+    budget = DUMP_BUDGET // world - sum(a.nbytes for a in arrays.values())
+    rows = {a.shape[0] for a in per_file.values()}
+    assert len(rows) <= 1, rows
+    row_bytes = sum(a.nbytes // max(1, a.shape[0]) for a in per_file.values())
+    n = rows.pop() if rows else 0
+    if n * row_bytes > budget:
+        m = max(1, budget // (row_bytes + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+        per_file = {k: a[idx] for k, a in per_file.items()}
+        arrays["sample_rows"] = idx.astype(np.float64)
+    arrays.update(per_file)
+    written = {}
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        fn = f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(outdir, fn), np.ascontiguousarray(a))
+        written[fn] = list(a.shape)
+    return written
 
 
 def compressions(lens):
@@ -670,6 +720,11 @@ def run_c4(args, torch, dist, dev, rank, world, distributed, out_f):
     hash_s = mean_ms / 1e3 * launches * args.steps
     if distributed:
         hash_s, wall = max_over_ranks(torch, dist, dev, [hash_s, wall])
+    dumped = None
+    if args.dump_outputs:
+        # the digests this rank holds after the last timed pass (the piece
+        # split: every file's; the file split: its own files', in file order)
+        dumped = dump_outputs(args.dump_outputs, {"digests": out32.cpu().numpy().astype(np.float32)}, None, rank, world)
     total = int(sizes.sum()) * args.steps
     comp = int(sum(int(compressions(np.array([x], np.uint64))[0]) for x in sizes)) * args.steps
     timed = wall if resident else hash_s
@@ -712,6 +767,9 @@ def run_c4(args, torch, dist, dev, rank, world, distributed, out_f):
                            "tests/test_gpu_stream.py (multi-piece messages up to 4 GiB + 1) and the split "
                            "path in tests/test_gpu_multiproc.py"},
     }
+    out["full"] = args.full
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     out["roofline"]["frac"] = out["roofline"]["achieved"] / (VALU_PEAK_OPS / 1e12) if out["roofline"]["achieved"] \
         else None
     hb = out["roofline"]["hbm"]
@@ -724,7 +782,9 @@ def run_c4(args, torch, dist, dev, rank, world, distributed, out_f):
     if tr and resident and tr.get("algorithmic_bytes_per_launch") == my_bytes:
         out["roofline"]["traffic"] = tr["hbm_bytes_per_launch"]
         out["roofline"]["traffic_source"] = tr.get("source")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if not args.full:
+        pass  # the baseline, parity checks and end-to-end legs below are --full's
+    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
         # bounded sample: the first files (in corpus order) up to c4_cpu_gib
         pick, acc = [], 0
         for f in mine:
@@ -750,7 +810,7 @@ def run_c4(args, torch, dist, dev, rank, world, distributed, out_f):
         checked, bad = sum_over_ranks(torch, dist, dev, [checked, bad])
         out["parity"].update({"checked_files": checked, "mismatches": bad, "ranks": world,
                               "sample": "each rank: its smallest file, whole-file checksum vs the oracle"})
-    if rank == 0 and world == 1 and resident and split == "files" and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and resident and split == "files" and not args.no_e2e:
         out["e2e"] = e2e_c4(args, torch, dev, blob, sizes, wins[0], out32, local)
     if args.c4_full_parity:
         # every file this rank holds a digest of, against the oracle's
@@ -875,6 +935,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the benchmark measures and checks: the CPU "
+                         "baselines and the parity checks against the oracle, the end-to-end legs, the sustained "
+                         "phase and the dedup's own timing (a plain run times its steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (cas keys, dedup links and counts; c4: "
+                         "digests) as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--files", type=int, default=0, help="files per GPU (default: the workload's)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="files in the CPU-baseline sample (0: all of rank 0's)")
@@ -902,6 +969,8 @@ def main():
     ap.add_argument("--c4-split", default="auto", choices=["auto", "pieces", "files"],
                     help="c4 over N GPUs: split the files' pieces (auto at N > 1) or assign whole files")
     args = ap.parse_args()
+    if args.c4_full_parity and not args.full:
+        ap.error("--c4-full-parity is one of the checks of a --full run: pass --full with it")
     W = WORKLOADS[args.workload]
 
     import torch
@@ -1008,8 +1077,22 @@ def main():
     eng.dev_sync(sp)
     if distributed:
         dt, leaf_ms, seq_ms = max_over_ranks(torch, dist, dev, [dt, leaf_ms, seq_ms])
+    if dd is not None and len(dd["last"]) == 2:  # (link, counts on the device) of the last timed step
+        c = dd["last"][1].tolist()
+        dd["last"] = (dd["last"][0], int(c[0]), int(c[1]))
+    dumped = None
+    if args.dump_outputs:
+        # what the step leaves its caller: every file's cas key and, with the
+        # dedup, every file's link and the two counts (before any --full leg
+        # runs the step again)
+        per_file = {"cas_keys": u64_words(d_out.cpu().numpy())}
+        other = {}
+        if dd is not None:
+            per_file["dedup_links"] = u64_words(dd["last"][0].cpu().numpy())
+            other["dedup_counts"] = np.array(dd["last"][1:], np.float64)
+        dumped = dump_outputs(args.dump_outputs, per_file, other, rank, world)
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         # the same steps for a few seconds more, outside the timed region: the
         # steady-state rate (clock and power settled); the count follows from
         # the timed steps' max-over-ranks time, so every rank runs as many
@@ -1027,7 +1110,7 @@ def main():
         sustained = {"steps": k, "seconds": st, "value": n * world * k / st, "ms_per_step": st / k * 1e3,
                      "note": "the timed steps' workload repeated back to back after them, untimed by the "
                              "contract (not part of `value`)"}
-    if dd is not None:
+    if dd is not None and args.full:
         # the dedup's share of a step: the same calls on the same resident
         # inputs, `steps` of them back to back between one pair of HIP events
         # (and, at N > 1, the exchange's own events), after the timed steps
@@ -1092,9 +1175,16 @@ def main():
                    "chunks_per_gpu": chunks,
                    "parallelism": f"files sharded over {world} GPU(s)" +
                                   (", dedup: one RCCL all-to-all exchange" if W["dedup"] else ", no collective")},
-        "blake3_gbps": gbps, "roofline": roof, "sustained": sustained,
+        "blake3_gbps": gbps, "roofline": roof, "sustained": sustained, "full": args.full,
     }
-    if dd is not None:
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if dd is not None and not args.full:
+        # a plain run reports what its last timed step found; the dedup's own
+        # timing, roofline and exchange figures take calls of their own (--full)
+        out["dedup"] = {"objects_created": dd["last"][1], "files_linked": dd["last"][2], "records_per_gpu": n,
+                        "protocol": getattr(stages, "last_protocol", None)}
+    if dd is not None and args.full:
         ms = med = float(dd["ms"])
         if distributed:
             ms, med = max_over_ranks(torch, dist, dev, [ms, med])
@@ -1135,7 +1225,9 @@ def main():
                                         "timing": "HIP events around the all-to-alls on the step's stream, "
                                                   "max over ranks",
                                         "link_peak_gbps_per_peer": 153.6}
-    if rank == 0 and world == 1:
+    if not args.full:
+        pass  # the baselines, parity checks and end-to-end legs below are --full's
+    elif rank == 0 and world == 1:
         gk = d_out.cpu().numpy().view(np.uint64)
         if args.workload == "c2" and not args.no_cpu_baseline:
             base, parity = cpu_baseline(gk, min(args.cpu_sample or n, n), args.cpu_threads)

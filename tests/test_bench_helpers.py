@@ -27,6 +27,38 @@ def test_dedup_bytes():
     assert bench.dedup_bytes(10, 3) == 25 * 10 + 16 * 3
 
 
+def test_u64_words_are_exact():
+    """--dump-outputs writes 64-bit keys and links as two float64 words each:
+    every bit survives, the link encoding's INT64_MIN + 1 included"""
+    a = np.array([0, 1, -1, -2**63, -2**63 + 1, 2**63 - 1, 0x123456789ABCDEF], np.int64)
+    w = bench.u64_words(a)
+    assert w.dtype == np.float64 and w.shape == (a.size, 2)
+    back = (w[:, 0].astype(np.uint64) << np.uint64(32)) | w[:, 1].astype(np.uint64)
+    assert np.array_equal(back.view(np.int64), a)
+
+
+def test_dump_outputs_sample_is_fixed(tmp_path, monkeypatch):
+    """small outputs are written whole; larger ones as the same seeded sample
+    of rows on every run, within the byte budget, every rank under its own name"""
+    keys = bench.u64_words(np.arange(1000, dtype=np.int64) * 7)
+    links = bench.u64_words(np.arange(1000, dtype=np.int64))
+    counts = np.array([3.0, 4.0])
+    got = bench.dump_outputs(str(tmp_path / "a"), {"cas_keys": keys, "dedup_links": links}, {"dedup_counts": counts})
+    assert got == {"dedup_counts.npy": [2], "cas_keys.npy": [1000, 2], "dedup_links.npy": [1000, 2]}
+    assert np.array_equal(np.load(tmp_path / "a" / "cas_keys.npy"), keys)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 8000)
+    for d in ("b", "c"):
+        got = bench.dump_outputs(str(tmp_path / d), {"cas_keys": keys, "dedup_links": links}, {"dedup_counts": counts})
+    rows = np.load(tmp_path / "b" / "sample_rows.npy")
+    assert 100 < rows.size < 1000 and np.all(np.diff(rows) > 0)
+    assert sum(int(np.prod(s)) * 8 for s in got.values()) <= 8000
+    for name in got:
+        assert np.array_equal(np.load(tmp_path / "b" / name), np.load(tmp_path / "c" / name)), name
+    assert np.array_equal(np.load(tmp_path / "b" / "dedup_links.npy"), links[rows.astype(np.int64)])
+    got = bench.dump_outputs(str(tmp_path / "d"), {"digests": np.zeros((3, 32), np.float32)}, None, rank=1, world=2)
+    assert got == {"digests.rank1.npy": [3, 32]}
+
+
 def test_peaks():
     # spec lane rate: 256 CUs x 4 SIMD x 32 lanes x 2.4 GHz; 680 lane-ops per compression
     assert bench.VALU_PEAK_OPS / bench.OPS_PER_COMPRESSION / 1e9 == pytest.approx(115.66, abs=0.01)

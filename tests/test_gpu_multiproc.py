@@ -272,7 +272,7 @@ def test_bench_two_ranks(workload, launcher):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     args = ["bench.py", "--gpus", "2", "--workload", workload, "--files", "20000", "--steps", "2", "--warmup", "1",
-            "--sustain-s", "0.5", "--c4-total-gib", "4"]
+            "--sustain-s", "0.5", "--c4-total-gib", "4", "--full"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + args

@@ -7,9 +7,9 @@
 # usage: tools/gpu.sh OUT STEP [STEP ...]
 #   tests[=EXPR]          pytest -m gpu (EXPR: a -k expression, '~' for ' '), OUT/pytest_gpu[_EXPR].log
 #   smoke                 __graft_entry__.smoke()
-#   bench=W[:STEPS:WARM]  bench.py --workload W (c2 c3 c4 c5), OUT/bench_W.json
+#   bench=W[:STEPS:WARM]  bench.py --full --workload W (c2 c3 c4 c5), OUT/bench_W.json
 #   stats=W               rocprofv3 --kernel-trace --stats of a bench.py W run (20 steps, no baselines), OUT/stats_W/
-#   n8=W                  bench.py --gpus 8 --workload W at 100 000 files per rank, gloo on the one GPU (the driver's
+#   n8=W                  bench.py --full --gpus 8 --workload W at 100 000 files per rank, gloo on the one GPU (the driver's
 #                         N = 8 launch rehearsed; every rank's links against the oracle), OUT/n8_gloo_W.json
 #   dedupfull=W[:ARGS]    tools/dedup_full.py --workload W (ARGS: extra flags, '~' for ' '), OUT/dedup_full_W_N.json
 #   pmcdedup=W[:ARGS]     tools/pmc_dedup.sh over tools/dedup_full.py or dedup_probe.py (ARGS: 'full' or probe flags)
@@ -43,7 +43,7 @@ step() {
       IFS=: read -r w st wu <<< "$arg"
       local extra=()
       [ -n "$st" ] && extra=(--steps "$st" --warmup "${wu:-3}")
-      timeout -k 10 700 python -u bench.py --workload "$w" "${extra[@]}" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
+      timeout -k 10 700 python -u bench.py --full --workload "$w" "${extra[@]}" > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
       local rc=$?; cut -c1-300 "$OUT/bench_$w.json"; return $rc ;;
     stats)
       local st=20
@@ -53,7 +53,7 @@ step() {
         --no-e2e --sustain-s 0 > "$R/$OUT/stats_$arg.json" 2> "$R/$OUT/stats_$arg.err")
       local rc=$?; find "$OUT/stats_$arg" -name '*kernel_trace.csv' -delete; return $rc ;;
     n8)
-      SDCAS_BENCH_BACKEND=gloo OMP_NUM_THREADS=2 timeout -k 10 500 python3 -u bench.py --gpus 8 --workload "$arg" \
+      SDCAS_BENCH_BACKEND=gloo OMP_NUM_THREADS=2 timeout -k 10 500 python3 -u bench.py --full --gpus 8 --workload "$arg" \
         --files 100000 --steps 3 --warmup 1 --sustain-s 0 > "$OUT/n8_gloo_$arg.json" 2> "$OUT/n8_gloo_$arg.err"
       local rc=$?; cut -c1-300 "$OUT/n8_gloo_$arg.json"; return $rc ;;
     dedupfull)
