@@ -15,6 +15,9 @@
  *   sdcas_checksums      replaces file_checksum(path)
  *                        core/src/object/validation/hash.rs:11-25, called from
  *                        validation/validator_job.rs:154 and watcher/utils.rs:496
+ *   sdcas_identify_checksums
+ *                        both of the above for a scan that also fills
+ *                        integrity_checksum: one open and one read per file
  *   sdcas_dedup          replaces the cas_id -> Object group-by/link of
  *                        file_identifier/mod.rs:149-254 (HashSet at :149-154,
  *                        existing-object lookup :181-188, linear find :214-224,
@@ -130,8 +133,8 @@ typedef struct sdcas_options {
  * distinct key, any order within an owner's range — same signatures, but a
  * caller that relied on ABI 4's documented key order must change; 6
  * sdcas_file_metadata, and resolve_buckets may overwrite the received
- * records' value words) */
-#define SDCAS_ABI_VERSION 6
+ * records' value words; 7 sdcas_dev_identify and sdcas_identify_checksums) */
+#define SDCAS_ABI_VERSION 7
 int sdcas_abi_version(void);
 const char *sdcas_version(void);
 
@@ -185,6 +188,35 @@ int sdcas_file_metadata(sdcas_ctx *ctx, const char *const *paths, const uint64_t
 int sdcas_checksums(sdcas_ctx *ctx, const char *const *paths, size_t n, uint8_t *out32,
                     int32_t *out_status);
 
+/* FileMetadata::new followed by file_checksum of n files from ONE open and ONE
+ * read of each: per file the results of sdcas_file_metadata followed by
+ * sdcas_checksums on a file nobody writes meanwhile. A file of at most 1 MiB
+ * is read once into the staging slot and both hashes come from that copy
+ * (up to 100 KiB from one pass of the kernel over it, sdcas_dev_identify); a
+ * larger one streams its checksum as sdcas_checksums does and its cas_id
+ * windows are read through the same descriptor. Per file: out_sizes[i] the
+ * length L from fstat of that descriptor; out_flags[i] SDCAS_META_HAS_CAS_ID
+ * when out_keys[i] holds the cas key (a non-empty regular file),
+ * SDCAS_META_HAS_CHECKSUM when out32[32 * i ..] holds the digest (every
+ * regular file read without error; an empty one gets the empty-input digest,
+ * as the validator hashes empty files), SDCAS_META_DIR for a directory
+ * (status 0, no outputs); out_status[i] 0, the errno of the metadata, the
+ * open or the reads, or SDCAS_STATUS_UNEXPECTED_EOF — a nonzero status means
+ * neither result. Both hashes are over the file's first L bytes: a file that
+ * grows while it is read is hashed over L bytes, one that shrinks below L
+ * gets SDCAS_STATUS_UNEXPECTED_EOF. The path is stat'ed before it is opened
+ * and only a regular file is opened: a FIFO, socket or device node gets size
+ * 0, flags 0, status 0. size_hints (may be NULL: one stat pass first) only
+ * plan the staging, as in sdcas_file_metadata: a file of another size now is
+ * read again with room for it, up to 4 times, then gets EAGAIN. An open
+ * refused for an empty file leaves status 0 and no checksum. Progress,
+ * cancellation, SDCAS_MAX_BATCH and SDCAS_OPT_DIRECT_IO as in the two calls
+ * it replaces. ABI 7. */
+#define SDCAS_META_HAS_CHECKSUM 4u
+int sdcas_identify_checksums(sdcas_ctx *ctx, const char *const *paths, const uint64_t *size_hints, size_t n,
+                             uint64_t *out_sizes, uint64_t *out_keys, uint8_t *out32, int32_t *out_status,
+                             uint8_t *out_flags);
+
 /* ---- pre-assembled messages in host memory -----------------------------
  *
  * The bytes go through the context's pinned staging slots (a host copy by the
@@ -215,6 +247,28 @@ int sdcas_dev_hash_messages(sdcas_ctx *ctx, const uint8_t *d_blob, const uint64_
                             const uint64_t *d_lens, size_t n, uint8_t *d_out32, uint64_t *d_out_keys,
                             void *stream);
 int sdcas_dev_sync(sdcas_ctx *ctx, void *stream);
+/* Content-resident files -> cas key (cas.rs:23-62 with size = d_lens[i]) and
+ * BLAKE3(content) (hash.rs:11-25): file i's CONTENT lies at d_blob +
+ * d_offsets[i] (16-byte aligned, d_lens[i] bytes, the blob readable 64 B past
+ * every end). A file of 1..102400 bytes gets both hashes from one pass over
+ * its bytes; a longer one has its cas message (size, header, four samples,
+ * footer) gathered on the device and both messages hashed by the batch
+ * kernels; an empty one gets no key and the empty-input digest.
+ * d_out_has_key[i] = (d_lens[i] != 0). Any output may be NULL. Asynchronous,
+ * with sdcas_dev_hash_messages's stream rules; sdcas_dev_sync() reports a
+ * capacity overflow detected on the device. Workspace (sdcas_dev_reserve):
+ * max_msgs >= n, and max_chunks >= the larger of 2 * (A + 2048) and B, where
+ * A = sum over files of ceil((len + 8) / 1024) for 1 <= len <= 102400 and 1
+ * for any other file (the two hashes' chunk streams each take half of the
+ * workspace), and B = sum over the longer files of ceil(len / 1024). At most
+ * SDCAS_IDENTIFY_MAX_SAMPLED files of one call may be longer than 102400
+ * bytes (each needs 57,360 B of scratch for its gathered message; split a
+ * batch holding more). The context's scratch for n files (and n's worth of
+ * gathered messages up to that limit) is allocated by the first call that
+ * needs it, which waits for the stream: warm up outside timed regions. ABI 7. */
+#define SDCAS_IDENTIFY_MAX_SAMPLED 4096
+int sdcas_dev_identify(sdcas_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_offsets, const uint64_t *d_lens,
+                       size_t n, uint64_t *d_out_keys, uint8_t *d_out32, uint8_t *d_out_has_key, void *stream);
 /* Name a stream's identity. The device calls of a context share its scratch
  * workspace, so each call makes its stream wait for the previous call's use
  * of it (an event wait: a barrier that idles the GPU ~15 us) unless both ran

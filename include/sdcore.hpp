@@ -105,8 +105,13 @@ class Engine {
     std::vector<uint64_t> size, key;
     std::vector<int32_t> status;
     std::vector<uint8_t> flags;  // SDCAS_META_*
+    std::vector<uint8_t> digest;  // identify_checksums only: 32 bytes per file
   };
   RawMetadata file_metadata(const std::vector<const char*>& paths, const uint64_t* size_hints = nullptr);
+  // the same and file_checksum from one open and one read of each file
+  // (sdcas_identify_checksums): digest holds 32 bytes per file, valid where
+  // flags has SDCAS_META_HAS_CHECKSUM
+  RawMetadata identify_checksums(const std::vector<const char*>& paths, const uint64_t* size_hints = nullptr);
 
   // the canonical group-by of mod.rs:149-254 over the job's steps
   // (sdcas_dedup_window; sdcas_dedup encoding of out_link). window may be
@@ -430,6 +435,10 @@ struct FileMetadata {
   std::optional<std::string> cas_id;  // None for an empty file (mod.rs:78-86)
   ObjectKind kind = 0;
   uint64_t len = 0;  // fs_metadata.len()
+  // file_checksum of the same read (hash.rs:11-25; 64 lowercase hex): set only
+  // by file_metadata_batch with `checksums`, for the identifier job that also
+  // fills integrity_checksum (FileIdentifierJobInit::checksums)
+  std::optional<std::string> integrity_checksum;
 };
 
 // FileMetadata::new for a batch of (full path, kind): fs::metadata, the
@@ -443,12 +452,20 @@ struct FileMetadata {
 std::vector<Result<FileMetadata>> file_metadata_batch(Engine& engine,
                                                       const std::vector<std::pair<std::string, ObjectKind>>& files,
                                                       const std::vector<uint64_t>* size_hints = nullptr);
+// The same with `checksums`: every file's cas_id and checksum from one open
+// and one read (sdcas_identify_checksums); integrity_checksum is set for every
+// file read without error, the empty ones included.
+std::vector<Result<FileMetadata>> file_metadata_batch(Engine& engine,
+                                                      const std::vector<std::pair<std::string, ObjectKind>>& files,
+                                                      const std::vector<uint64_t>* size_hints, bool checksums);
 
 // The DB half of the job's steps over a batch of its orphans (mod.rs:157-342
 // per step): write the cas_id of every row the steps read, look up the
 // existing Objects of their cas_ids, group (the GPU's sdcas_dedup_window in
 // identifier_job_step; any function with its encoding here), create Objects
-// and link. md[i] is file_paths[i]'s FileMetadata. window (in: max_steps,
+// and link; a row the steps read whose FileMetadata carries an
+// integrity_checksum gets it written too (set_integrity_checksum, in its
+// step's batch after its cas_id). md[i] is file_paths[i]'s FileMetadata. window (in: max_steps,
 // more; out: steps, rows, rereads) may be null: the whole job over these rows.
 // The steps' bookkeeping comes from sdcas_job_plan before any write. A batch
 // must not hold a row to re-identify — an Object but no cas_id (the indexer
@@ -507,6 +524,14 @@ struct FileIdentifierJobInit {
   // (Library::begin_bulk_identify); the rows and Objects the job leaves are
   // the same either way
   bool bulk_identify = false;
+  // also fill integrity_checksum (what run_object_validator_job would write
+  // afterwards) from the same read of each file: the FileMetadata comes from
+  // sdcas_identify_checksums, and every row the steps read whose metadata
+  // carries a checksum gets it in that row's step. Files the indexer saw
+  // empty are no orphans, so no step reads them: run_file_identifier_job
+  // checksums those after its steps, as the validator would. Clear: the job
+  // writes no checksum, whatever its metadata function returns.
+  bool checksums = false;
 };
 
 // init (count orphans, cursor = first orphan id, task_count = ceil(count /

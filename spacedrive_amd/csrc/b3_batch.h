@@ -91,6 +91,46 @@ hipError_t batch_hash(const BatchWorkspace& ws, const uint8_t* blob, const uint6
                       uint32_t n, uint8_t* out32, uint64_t* out_keys, hipStream_t st, uint64_t max_chunks = 0,
                       hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, const BatchPlan* plan = nullptr);
 
+// The two ends of batch_hash around its leaf kernel, for a caller with a leaf
+// kernel of its own (b3_dual.hip). plan_slots: the slot plan of n device
+// messages in caller order for tiles of kTile slots (k_plan_sums / k_plan_scan
+// / k_plan_write) — S[n], tile_first (entries of tiles below cap_slots) and
+// total[0] = the slot count (total[2] = 0); tmp holds a u64 per 4096
+// messages, plus one. finish_crossing: the merge of every message that
+// crosses a tile boundary from its maximal in-tile nodes (k_finish_q /
+// k_finish_t over `tiles` tile boundaries).
+hipError_t plan_slots(const uint64_t* lens, uint32_t n, void* tmp, size_t tmp_bytes, uint64_t cap_slots, uint64_t* S,
+                      uint32_t* tile_first, uint64_t* total, hipStream_t st);
+hipError_t finish_crossing(uint64_t tiles, const uint64_t* lens, uint32_t n, const uint64_t* S,
+                           const uint32_t* tile_first, const uint64_t* total, uint64_t cap_slots,
+                           const uint32_t* nodes, uint8_t* out32, uint64_t* out_keys, hipStream_t st);
+
+// ---- one pass for cas_id and checksum (b3_dual.hip) --------------------------
+//
+// n files whose CONTENT is resident (blob + offs[i], lens[i] bytes, 16-byte
+// aligned, readable 64 B past every end): the cas key of le64(len) || content
+// and BLAKE3(content) of every file of 1..102400 bytes from one read of its
+// bytes (k_dual_leaf feeds both chains from each 64-byte block it loads). A
+// longer file's cas message is gathered into the scratch (k_cas_gather) and
+// hashed, like its content, by batch_hash; an empty file gets no key and the
+// empty-input digest. has_key[i] = len != 0. Either output may be null.
+constexpr uint64_t kWholeMax = 102400;         // cas.rs:15 MINIMUM_FILE_SIZE
+constexpr uint64_t kGatherStride = 57360;      // a sampled cas message (57352 B), 16-byte aligned
+constexpr uint32_t kIdentifyMaxSampled = 4096;  // files above kWholeMax one call takes
+// Device scratch of one identify call, owned by the caller (the context):
+// sized by identify_scratch_bytes(n, sampled_cap).
+struct IdentifyScratch {
+  uint8_t* p = nullptr;
+  size_t bytes = 0;
+};
+size_t identify_scratch_bytes(uint32_t n, uint32_t sampled_cap);
+// sampled_cap: files above kWholeMax the scratch has room for; more of them
+// set ws.total[0] to UINT64_MAX (as do slot totals past half of ws.cap_slots
+// each), which the caller's next read of it reports as a capacity overflow.
+hipError_t identify_hash(const BatchWorkspace& ws, const IdentifyScratch& sc, const uint8_t* blob,
+                         const uint64_t* offs, const uint64_t* lens, uint32_t n, uint32_t sampled_cap,
+                         uint64_t* out_keys, uint8_t* out32, uint8_t* out_has_key, hipStream_t st);
+
 // ---- big files (C > kTile chunks), hashed as 1 MiB pieces -------------------
 struct PieceDesc {
   uint64_t off;        // byte offset of the piece in the blob (16-byte aligned)

@@ -171,6 +171,7 @@ struct sdcas_ctx {
   DevBuf<FileDesc> d_files;
   DevBuf<uint32_t> d_file_nodes;
   Slot slots[2];  // double-buffered pinned staging (host fills one, GPU hashes the other)
+  DevBuf<uint8_t> id_scratch;  // sdcas_dev_identify / sdcas_identify_checksums: the dual plans and the gathered cas messages
 
   // sdcas_dedup's device copies of the caller's host arrays
   DevBuf<uint64_t> dd_keys, dd_ekeys, dd_ids;
@@ -792,7 +793,7 @@ void sdcas_destroy(sdcas_ctx* c) {
     b->release();
   for (auto* b : {&c->ws_tile_first, &c->ws_nodes, &c->ws_perm, &c->ws_sort_keys, &c->d_file_nodes, &c->piece_ctr, &c->piece_l4})
     b->release();
-  for (auto* b : {&c->ws_scan, &c->d_out32, &c->dd_has}) b->release();
+  for (auto* b : {&c->ws_scan, &c->d_out32, &c->dd_has, &c->id_scratch}) b->release();
   c->d_files.release();
   c->dd_status.release();
   c->dd_link.release();
@@ -941,6 +942,36 @@ int sdcas_dev_hash_messages(sdcas_ctx* c, const uint8_t* d_blob, const uint64_t*
   if (n > c->ws.cap_msgs || !c->ws.S)
     return c->fail(SDCAS_E_CAPACITY, "dev_hash_messages: %zu messages > reserved %u", n, c->ws.cap_msgs);
   return launch_batch(c, d_blob, d_offsets, d_lens, (uint32_t)n, d_out32, d_out_keys, call.st);
+}
+
+// Enqueue identify_hash (b3_dual.hip) with the context's scratch grown to the
+// call: n files, room for `sampled_cap` of them above 100 KiB.
+static int identify_launch(sdcas_ctx* c, const uint8_t* blob, const uint64_t* offs, const uint64_t* lens, uint32_t n,
+                           uint32_t sampled_cap, uint64_t* keys, uint8_t* out32, uint8_t* has_key, hipStream_t st) {
+  const size_t need = identify_scratch_bytes(n, sampled_cap);
+  if (need > c->id_scratch.cap) {
+    // an earlier call's kernels may still read the scratch about to be freed
+    hipError_t e = c->scratch_sync();
+    if (!e) e = hipStreamSynchronize(st);
+    if (!e) e = c->id_scratch.ensure(need + need / 4);
+    if (e) return c->hip_fail(e, "identify scratch");
+  }
+  const IdentifyScratch sc{c->id_scratch.p, c->id_scratch.cap};
+  hipError_t e = identify_hash(c->ws, sc, blob, offs, lens, n, sampled_cap, keys, out32, has_key, st);
+  return e ? c->hip_fail(e, "identify_hash") : SDCAS_OK;
+}
+
+int sdcas_dev_identify(sdcas_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, const uint64_t* d_lens, size_t n,
+                       uint64_t* d_out_keys, uint8_t* d_out32, uint8_t* d_out_has_key, void* stream) {
+  if (!c || (n && (!d_blob || !d_offsets || !d_lens))) return SDCAS_E_INVALID;
+  if (n == 0) return SDCAS_OK;
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (n > c->ws.cap_msgs || !c->ws.S || c->ws.cap_slots < 2 * kTile)
+    return c->fail(SDCAS_E_CAPACITY, "dev_identify: %zu files > reserved %u", n, c->ws.cap_msgs);
+  const uint32_t sampled_cap = (uint32_t)std::min<size_t>(n, SDCAS_IDENTIFY_MAX_SAMPLED);
+  return identify_launch(c, d_blob, d_offsets, d_lens, (uint32_t)n, sampled_cap, d_out_keys, d_out32, d_out_has_key,
+                         call.st);
 }
 
 int sdcas_dev_bind_stream(sdcas_ctx* c, void* stream, uint64_t token) {
@@ -1502,6 +1533,259 @@ int sdcas_checksums(sdcas_ctx* c, const char* const* paths, size_t n, uint8_t* o
     if (rc) return rc;
     for (auto& b : big)
       if (!out_status[b.out_index]) memcpy(out32 + 32 * b.out_index, &d32[32 * b.out_index], 32);
+  }
+  return cancelled ? c->fail(SDCAS_E_CANCELLED, "cancelled") : SDCAS_OK;
+}
+
+static_assert(SDCAS_IDENTIFY_MAX_SAMPLED == kIdentifyMaxSampled, "sdcas.h and b3_batch.h");
+
+// Enqueue a slot of whole file contents (s.n files at s.offs()/s.lens()) for
+// sdcas_identify_checksums: the bytes and the metadata go up as in
+// slot_submit, identify_hash produces digest k at result byte 32 * k and cas
+// key k at 32 * s.n + 8 * k (s.n <= s.cap_n / 2, so both fit the slot's
+// result words), and one copy brings them back.
+static int identify_submit(sdcas_ctx* c, Slot& s) {
+  s.res32 = true;
+  s.blob_uploaded = false;
+  if (!s.n) return SDCAS_OK;
+  if (2 * s.n > s.cap_n) return c->fail(SDCAS_E_CAPACITY, "identify slot of %zu files", s.n);
+  int rc;
+  hipError_t e;
+  hipStream_t st = c->stream;
+  // each plan takes half of the workspace's slots; the files above 100 KiB
+  // run as two ordinary batches (their gathered cas messages, their contents)
+  uint64_t chunks_a = 0, chunks_s = 0;
+  uint32_t sampled = 0;
+  for (size_t k = 0; k < s.n; ++k) {
+    const uint64_t len = s.lens()[k];
+    if (len >= 1 && len <= kMin) {
+      chunks_a += chunks_of(len + 8);
+    } else {
+      chunks_a += 1;
+      if (len) chunks_s += std::max<uint64_t>(chunks_of(len), chunks_of(SDCAS_SAMPLED_MESSAGE_LEN)), ++sampled;
+    }
+  }
+  const uint64_t need_chunks = std::max<uint64_t>(2 * (chunks_a + 2 * kTile), chunks_s);
+  if (s.n > c->ws.cap_msgs || need_chunks > c->ws.cap_chunks) {
+    if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "sync");
+    if ((rc = reserve_ws(c, std::max<size_t>(s.n, c->ws.cap_msgs), std::max<uint64_t>(need_chunks, c->ws.cap_chunks))))
+      return rc;
+  }
+  memcpy(s.hm + s.n, s.lens(), 8 * s.n);  // the lengths behind the offsets: one copy
+  if ((e = slot_upload(c, s, [&](hipStream_t cs) {
+         hipError_t r = hipMemcpyAsync(s.d_blob.p, s.h, s.used, hipMemcpyHostToDevice, cs);
+         return r ? r : hipMemcpyAsync(s.d_meta.p, s.hm, 16 * s.n, hipMemcpyHostToDevice, cs);
+       })))
+    return c->hip_fail(e, "H2D");
+  uint8_t* d32 = s.d_res.p;
+  uint64_t* dkeys = reinterpret_cast<uint64_t*>(s.d_res.p + 32 * s.n);
+  if ((rc = identify_launch(c, s.d_blob.p, s.d_meta.p, s.d_meta.p + s.n, (uint32_t)s.n, sampled, dkeys, d32, nullptr,
+                            st)))
+    return rc;
+  if ((e = hipMemcpyAsync(s.res(), s.d_res.p, 40 * s.n, hipMemcpyDeviceToHost, st)) || (e = hipEventRecord(s.ev, st)))
+    return c->hip_fail(e, "D2H");
+  s.busy = true;
+  return SDCAS_OK;
+}
+
+int sdcas_identify_checksums(sdcas_ctx* c, const char* const* paths, const uint64_t* size_hints, size_t n,
+                             uint64_t* out_sizes, uint64_t* out_keys, uint8_t* out32, int32_t* out_status,
+                             uint8_t* out_flags) {
+  if (!c || (n && (!paths || !out_sizes || !out_keys || !out32 || !out_status || !out_flags))) return SDCAS_E_INVALID;
+  if (n > SDCAS_MAX_BATCH) return c->fail(SDCAS_E_CAPACITY, "batch of %zu files exceeds 2^31 - 1", n);
+  PathCall call(c);
+  if (call.rc) return call.rc;
+  std::fill(out_sizes, out_sizes + n, 0);
+  std::fill(out_keys, out_keys + n, 0);
+  std::fill(out_flags, out_flags + n, 0);
+  std::fill(out_status, out_status + n, 0);
+  memset(out32, 0, 32 * n);
+  const uint64_t cap = c->staging_bytes, big_cut = 1024ull * kTile;
+  const size_t cap_n = (size_t)(cap / 128) + 1;
+  int rc;
+  if ((rc = slots_prepare(c, cap, cap_n))) return rc;
+  // the staging plan: the caller's sizes (the indexer's), else one stat pass;
+  // a file planned above 1 MiB gets no room (it is streamed, or read again
+  // with room if it is smaller now)
+  std::vector<uint64_t> want(n);
+  if (size_hints) {
+    std::copy(size_hints, size_hints + n, want.begin());
+  } else {
+    c->pool->run(n, [&](size_t i) {
+      struct stat sb;
+      want[i] = stat(paths[i], &sb) == 0 && S_ISREG(sb.st_mode) ? (uint64_t)sb.st_size : 0;
+    });
+  }
+  Progress pr{c};
+  for (size_t i = 0; i < n; ++i) {
+    pr.total += want[i];
+    if (want[i] > big_cut) want[i] = 0;
+  }
+  struct Big {
+    size_t i;
+    uint64_t len;
+    int fd;
+    bool aligned;
+  };
+  std::vector<Big> bigs;
+  std::vector<size_t> todo(n);
+  for (size_t i = 0; i < n; ++i) todo[i] = i;
+  const uint64_t scap = split_cap(want.data(), nullptr, n, cap);
+  int cur = 0;
+  auto drain = [&](Slot& s) -> int {
+    if (!s.busy) return SDCAS_OK;
+    s.busy = false;
+    hipError_t e = hipEventSynchronize(s.ev);
+    if (e) return c->hip_fail(e, "identify batch");
+    for (size_t k = 0; k < s.n; ++k) {
+      const size_t i = s.idx[k];
+      memcpy(out32 + 32 * i, s.res() + 32 * k, 32);
+      out_flags[i] |= SDCAS_META_HAS_CHECKSUM;
+      if (s.lens()[k]) {
+        memcpy(&out_keys[i], s.res() + 32 * s.n + 8 * k, 8);
+        out_flags[i] |= SDCAS_META_HAS_CAS_ID;
+      }
+    }
+    pr.add(s.content);
+    return SDCAS_OK;
+  };
+  auto close_bigs = [&]() {
+    for (Big& b : bigs)
+      if (b.fd >= 0) close(b.fd), b.fd = -1;
+  };
+  bool cancelled = false;
+  for (int round = 0; round < 4 && !todo.empty() && !cancelled; ++round) {
+    std::vector<size_t> retry;
+    size_t p = 0;
+    while (p < todo.size()) {
+      Slot& s = c->slots[cur];
+      if ((rc = drain(s))) return close_bigs(), rc;
+      if ((cancelled = c->cancelled())) {
+        for (size_t k = p; k < todo.size(); ++k) out_status[todo[k]] = SDCAS_STATUS_CANCELLED;
+        for (size_t i : retry) out_status[i] = SDCAS_STATUS_CANCELLED;
+        retry.clear();
+        break;
+      }
+      std::vector<uint64_t> slot_off;
+      uint64_t used = 0;
+      const size_t q = plan_batch(want.data(), todo.data(), p, todo.size(), scap, cap_n / 2, slot_off, &used);
+      if ((rc = slot_prepare(c, s, std::max<uint64_t>(used, cap), cap_n))) return close_bigs(), rc;
+      const size_t m = q - p;
+      std::vector<sdcas_io::IdentifyRead> rd(m);
+      std::vector<int32_t> st(m);
+      c->pool->run(m, [&](size_t k) {
+        const size_t i = todo[p + k];
+        st[k] = sdcas_io::read_identify(paths[i], c->direct_io, s.h + slot_off[k], align16(want[i]), big_cut, &rd[k]);
+      });
+      s.n = 0, s.chunks = 0, s.used = used, s.content = 0;
+      s.idx.clear();
+      for (size_t k = 0; k < m; ++k) {
+        const size_t i = todo[p + k];
+        const sdcas_io::IdentifyRead& r = rd[k];
+        if (!st[k] && r.need) {
+          want[i] = r.need;
+          retry.push_back(i);
+          continue;
+        }
+        out_status[i] = st[k];
+        out_sizes[i] = r.size;
+        if (r.kind == sdcas_io::kKindDir) out_flags[i] = SDCAS_META_DIR;
+        if (r.fd >= 0) {
+          bigs.push_back(Big{i, r.size, r.fd, r.aligned});
+          continue;
+        }
+        s.content += r.size;
+        if (st[k] || r.kind != sdcas_io::kKindRegular || !r.opened) continue;
+        s.offs()[s.n] = slot_off[k];
+        s.lens()[s.n] = r.size;
+        s.idx.push_back(i);
+        s.n++;
+      }
+      if ((rc = identify_submit(c, s))) return close_bigs(), rc;
+      if (!s.n) pr.add(s.content);
+      cur ^= 1;
+      p = q;
+    }
+    for (Slot& s : c->slots)
+      if ((rc = drain(s))) return close_bigs(), rc;
+    todo.swap(retry);
+  }
+  for (size_t i : todo) out_status[i] = cancelled ? SDCAS_STATUS_CANCELLED : EAGAIN;  // EAGAIN: kept changing size
+  if (cancelled) {
+    for (Big& b : bigs) out_status[b.i] = SDCAS_STATUS_CANCELLED;
+    close_bigs();
+    return c->fail(SDCAS_E_CANCELLED, "cancelled");
+  }
+  if (bigs.empty()) return SDCAS_OK;
+  // Files above 1 MiB: the cas message (cas.rs:35-58's windows) is read
+  // through the file's descriptor into a normal slot, the checksum streams
+  // through run_big from the same descriptor (every such file stays open
+  // until then, as sdcas_checksums keeps its big files open).
+  {
+    std::vector<uint64_t> mwant(bigs.size(), SDCAS_SAMPLED_MESSAGE_LEN);
+    auto kdrain = [&](Slot& s) -> int {
+      return slot_complete(c, s, [&](size_t k, const uint8_t* r) {
+        const size_t i = bigs[s.idx[k]].i;
+        memcpy(&out_keys[i], r, 8);
+        out_flags[i] |= SDCAS_META_HAS_CAS_ID;
+      });
+    };
+    size_t p = 0;
+    while (p < bigs.size()) {
+      Slot& s = c->slots[cur];
+      if ((rc = kdrain(s))) return close_bigs(), rc;
+      std::vector<uint64_t> slot_off;
+      uint64_t used = 0;
+      const size_t q = plan_batch(mwant.data(), nullptr, p, bigs.size(), cap, cap_n, slot_off, &used);
+      const size_t m = q - p;
+      std::vector<uint64_t> mlen(m), rl(m);
+      std::vector<int32_t> st(m);
+      c->pool->run(m, [&](size_t k) {
+        const Big& b = bigs[p + k];
+        st[k] = sdcas_io::read_cas_message_fd(b.fd, b.aligned, b.len, s.h + slot_off[k],
+                                              align16(SDCAS_SAMPLED_MESSAGE_LEN), &mlen[k], &rl[k]);
+      });
+      s.n = 0, s.chunks = 0, s.used = used, s.content = 0;
+      s.idx.clear();
+      for (size_t k = 0; k < m; ++k) {
+        const Big& b = bigs[p + k];
+        out_status[b.i] = st[k];
+        if (st[k]) continue;
+        s.offs()[s.n] = slot_off[k];
+        s.lens()[s.n] = mlen[k];
+        s.idx.push_back(p + k);
+        s.n++;
+        s.chunks += chunks_of(mlen[k]);
+      }
+      if ((rc = slot_submit(c, s, false))) return close_bigs(), rc;
+      cur ^= 1;
+      p = q;
+    }
+    for (Slot& s : c->slots)
+      if ((rc = kdrain(s))) return close_bigs(), rc;
+  }
+  std::vector<BigItem> items;
+  std::vector<size_t> item_big;
+  for (size_t k = 0; k < bigs.size(); ++k)
+    if (!out_status[bigs[k].i]) items.push_back({bigs[k].len, bigs[k].i}), item_big.push_back(k);
+  std::vector<uint8_t> d32(32 * n);
+  rc = run_big(c, items, d32.data(),
+               [&](size_t k, uint8_t* dst, uint64_t off, uint32_t len) -> int {
+                 const Big& b = bigs[item_big[k]];
+                 return b.aligned ? pread_direct(b.fd, dst, len, off) : pread_exact(b.fd, dst, len, off);
+               },
+               out_status, pr, &cancelled);
+  close_bigs();
+  if (rc) return rc;
+  for (const BigItem& it : items) {
+    const size_t i = it.out_index;
+    if (!out_status[i]) {
+      memcpy(out32 + 32 * i, &d32[32 * i], 32);
+      out_flags[i] |= SDCAS_META_HAS_CHECKSUM;
+    } else {
+      out_flags[i] = 0;  // a status means neither result
+      out_keys[i] = 0;
+    }
   }
   return cancelled ? c->fail(SDCAS_E_CANCELLED, "cancelled") : SDCAS_OK;
 }

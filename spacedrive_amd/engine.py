@@ -176,6 +176,26 @@ class Engine:
         del buf
         return sizes, keys, st, fl
 
+    def identify_checksums(self, paths, size_hints=None):
+        """file_metadata followed by file_checksums from ONE open and ONE read
+        of each file (sdcas_identify_checksums) -> (sizes uint64[n], keys
+        uint64[n], digests uint8[n, 32], status int32[n], flags uint8[n]:
+        SDCAS_META_HAS_CAS_ID | SDCAS_META_DIR | SDCAS_META_HAS_CHECKSUM)"""
+        n = len(paths)
+        buf, parr = _cpaths(paths)
+        hints = _arr(size_hints, np.uint64) if size_hints is not None else None
+        sizes = np.zeros(n, np.uint64)
+        keys = np.zeros(n, np.uint64)
+        out = np.zeros((n, 32), np.uint8)
+        st = np.zeros(n, np.int32)
+        fl = np.zeros(n, np.uint8)
+        self._check(self.L.sdcas_identify_checksums(self.ctx, _ptr(parr),
+                                                    _ptr(hints) if hints is not None else None, n, _ptr(sizes),
+                                                    _ptr(keys), _ptr(out), _ptr(st), _ptr(fl)),
+                    "sdcas_identify_checksums", (sizes, keys, out, st, fl))
+        del buf
+        return sizes, keys, out, st, fl
+
     def file_checksums(self, paths):
         """hash.rs:11-25 for many files -> (digests uint8[n, 32], status int32[n])"""
         n = len(paths)
@@ -261,6 +281,12 @@ class Engine:
     def dev_hash_messages(self, blob, offs, lens, n, out32=0, keys=0, stream=0):
         self._check(self.L.sdcas_dev_hash_messages(self.ctx, blob, offs, lens, int(n), out32 or None,
                                                    keys or None, stream or None), "dev_hash_messages")
+
+    def dev_identify(self, blob, offs, lens, n, keys=0, out32=0, has_key=0, stream=0):
+        """cas keys and content digests of n content-resident files from one
+        pass over their bytes (sdcas_dev_identify); any output may be 0"""
+        self._check(self.L.sdcas_dev_identify(self.ctx, blob, offs, lens, int(n), keys or None, out32 or None,
+                                              has_key or None, stream or None), "dev_identify")
 
     def dev_sync(self, stream=0):
         self._check(self.L.sdcas_dev_sync(self.ctx, stream or None), "dev_sync")

@@ -285,6 +285,50 @@ int read_file_metadata(const char* path, bool direct, uint8_t* dst, uint64_t cap
   return st;
 }
 
+int read_identify(const char* path, bool direct, uint8_t* dst, uint64_t cap, uint64_t max_len, IdentifyRead* out) {
+  *out = IdentifyRead{};
+  struct stat sb;
+  if (stat(path, &sb) != 0) return errno;  // fs::metadata fails (mod.rs:63-65)
+  if (S_ISDIR(sb.st_mode)) {
+    out->kind = kKindDir;
+    out->size = (uint64_t)sb.st_size;
+    return 0;
+  }
+  if (!S_ISREG(sb.st_mode)) {
+    out->kind = kKindOther;
+    return 0;
+  }
+  bool aligned = false;
+  const int fd = open_for_read(path, direct, &aligned);
+  if (fd < 0) {
+    out->size = (uint64_t)sb.st_size;
+    return sb.st_size == 0 ? 0 : -fd;
+  }
+  out->opened = true;
+  if (fstat(fd, &sb) != 0) {
+    const int e = errno;
+    close(fd);
+    return e;
+  }
+  if (!S_ISREG(sb.st_mode)) {  // replaced between the stat and the open
+    close(fd);
+    out->kind = S_ISDIR(sb.st_mode) ? kKindDir : kKindOther;
+    return 0;
+  }
+  const uint64_t L = (uint64_t)sb.st_size;
+  out->size = L;
+  if (L > max_len) {
+    out->fd = fd;
+    out->aligned = aligned;
+    return 0;
+  }
+  int st = 0;
+  if (L > cap) out->need = L;
+  else if (L) st = read_exact_any(fd, aligned, dst, L, 0);
+  close(fd);
+  return st;
+}
+
 size_t plan_batch(const uint64_t* need, const size_t* order, size_t p, size_t end, uint64_t cap, size_t cap_n,
                   std::vector<uint64_t>& offs, uint64_t* used) {
   offs.clear();

@@ -86,6 +86,31 @@ int read_cas_message_fd(int fd, bool aligned, uint64_t size, uint8_t* dst, uint6
 int read_file_metadata(const char* path, bool direct, uint8_t* dst, uint64_t cap, uint64_t* len,
                        uint64_t* retry_len, uint64_t* size, bool* is_dir);
 
+// sdcas_identify_checksums' one open and one read of a file, for both its
+// cas_id and its checksum. The path is stat'ed FIRST and opened only when it
+// names a regular file: a FIFO, socket or device node (kKindOther: size 0,
+// status 0) is never opened, so a FIFO without a writer cannot block the
+// reader. Then the metadata is fstat of the descriptor (*size = L) and
+//   L == 0        nothing is read;
+//   L > max_len   nothing is read and the descriptor is handed over (fd,
+//                 aligned): the caller streams the file and closes it;
+//   L > cap       nothing is read, need = L: read again with that much room;
+//   otherwise     the first L bytes go to dst, UnexpectedEof if the file
+//                 holds fewer by now.
+// `opened` is false when the open was refused: the return value is then the
+// open's errno for a non-empty file and 0 for an empty one (FileMetadata::new
+// never opens an empty file; its checksum is still missing).
+enum : int { kKindRegular = 0, kKindDir = 1, kKindOther = 2 };
+struct IdentifyRead {
+  uint64_t size = 0;
+  uint64_t need = 0;
+  int kind = kKindRegular;
+  int fd = -1;
+  bool aligned = false;
+  bool opened = false;
+};
+int read_identify(const char* path, bool direct, uint8_t* dst, uint64_t cap, uint64_t max_len, IdentifyRead* out);
+
 // The next staging batch: items order[p], order[p+1], ... of `need` bytes
 // each (line-aligned here) go to offsets in one slot of `cap` bytes and at
 // most cap_n items; the first item always fits (a message larger than the

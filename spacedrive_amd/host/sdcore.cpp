@@ -108,6 +108,22 @@ Engine::RawMetadata Engine::file_metadata(const std::vector<const char*>& paths,
   return m;
 }
 
+Engine::RawMetadata Engine::identify_checksums(const std::vector<const char*>& paths, const uint64_t* size_hints) {
+  const size_t n = paths.size();
+  RawMetadata m;
+  m.size.resize(n);
+  m.key.resize(n);
+  m.status.resize(n);
+  m.flags.resize(n);
+  m.digest.resize(32 * n);
+  if (n) {
+    const int rc = sdcas_identify_checksums(ctx_, paths.data(), size_hints, n, m.size.data(), m.key.data(),
+                                            m.digest.data(), m.status.data(), m.flags.data());
+    if (rc != SDCAS_OK) fail(rc, "sdcas_identify_checksums");
+  }
+  return m;
+}
+
 std::vector<Result<std::string>> Engine::generate_cas_ids(
     const std::vector<std::pair<std::string, uint64_t>>& files) {
   const size_t n = files.size();
@@ -415,15 +431,22 @@ static bool fold_stat() {
 std::vector<Result<FileMetadata>> file_metadata_batch(Engine& engine,
                                                       const std::vector<std::pair<std::string, ObjectKind>>& files,
                                                       const std::vector<uint64_t>* size_hints) {
+  return file_metadata_batch(engine, files, size_hints, false);
+}
+
+std::vector<Result<FileMetadata>> file_metadata_batch(Engine& engine,
+                                                      const std::vector<std::pair<std::string, ObjectKind>>& files,
+                                                      const std::vector<uint64_t>* size_hints, bool checksums) {
   const size_t n = files.size();
   if (size_hints && size_hints->size() != n) throw std::invalid_argument("file_metadata_batch: one size hint per file");
-  if (fold_stat()) {
+  if (checksums || fold_stat()) {
     // fs::metadata, the kind and generate_cas_id (mod.rs:63-86) in one library
     // call: the metadata is the fstat of the descriptor the reads use
     std::vector<const char*> paths(n);
     for (size_t i = 0; i < n; ++i) paths[i] = files[i].first.c_str();
     const auto t0 = std::chrono::steady_clock::now();
-    const Engine::RawMetadata raw = engine.file_metadata(paths, size_hints ? size_hints->data() : nullptr);
+    const uint64_t* hints = size_hints ? size_hints->data() : nullptr;
+    const Engine::RawMetadata raw = checksums ? engine.identify_checksums(paths, hints) : engine.file_metadata(paths, hints);
     static const bool trace = [] {
       const char* v = getenv("SDCORE_TRACE_JOB");
       return v && *v && strcmp(v, "0") != 0;
@@ -445,6 +468,11 @@ std::vector<Result<FileMetadata>> file_metadata_batch(Engine& engine,
         m.kind = files[i].second >= 0 ? files[i].second : object_kind_of(files[i].first);  // mod.rs:72-76
         m.len = raw.size[i];
         if (raw.flags[i] & SDCAS_META_HAS_CAS_ID) m.cas_id = key_to_hex(raw.key[i]);
+        if (raw.flags[i] & SDCAS_META_HAS_CHECKSUM) {
+          char h[65];
+          sdcas_digest_to_hex(&raw.digest[32 * i], h);
+          m.integrity_checksum = std::string(h, 64);
+        }
         out[i] = std::move(m);
       }
     };
@@ -760,6 +788,11 @@ static std::pair<size_t, size_t> step_db(Library& db, const std::vector<FilePath
   }();
   if (each) db.Library::set_cas_ids_and_connect(writes);
   else db.set_cas_ids_and_connect(writes);
+  // the checksum of the same read (FileIdentifierJobInit::checksums): every
+  // row the steps read, after its cas_id write
+  for (size_t i = 0; i < n; ++i)
+    if (step[i] != UINT64_MAX && md[i].ok() && md[i].value().integrity_checksum)
+      db.set_integrity_checksum(file_paths[i].id, *md[i].value().integrity_checksum);
   db.end_batch();
   trace_lap(JobTrace::kObjects);
   if (window) *window = win;
@@ -1156,10 +1189,21 @@ FileIdentifierJobRunMetadata run_file_identifier_job_with(Library& db, const Fil
   };
   const bool concurrent = db.concurrent_orphan_reads();
   trace.lap(JobTrace::kInit);
+  // without `checksums` the job writes none: a metadata function's are dropped
+  const MetadataFn no_checksums = [&](const std::vector<FilePathRow>& rows) {
+    auto md = metadata(rows);
+    for (auto& m : md)
+      if (m.ok() && m.value().integrity_checksum) {
+        FileMetadata v = m.value();
+        v.integrity_checksum.reset();
+        m = std::move(v);
+      }
+    return md;
+  };
   const StepLoop L = run_steps(
       db, task_count, meta.cursor, init.batch,
-      [&](int32_t cursor, size_t take) { return db.get_orphan_file_paths(loc, cursor, sub, take); }, metadata,
-      group_by, concurrent ? &ahead : nullptr);
+      [&](int32_t cursor, size_t take) { return db.get_orphan_file_paths(loc, cursor, sub, take); },
+      init.checksums ? metadata : no_checksums, group_by, concurrent ? &ahead : nullptr);
   meta.total_objects_created = L.created;
   meta.total_objects_linked = L.linked;
   meta.steps = L.steps;
@@ -1197,14 +1241,14 @@ ShallowIdentifierReport shallow_file_identifier_with(Library& db, const Location
 }
 
 static std::vector<Result<FileMetadata>> metadata_of(Engine& engine, const Location& location,
-                                                     const std::vector<FilePathRow>& rows) {
+                                                     const std::vector<FilePathRow>& rows, bool checksums = false) {
   std::vector<std::pair<std::string, ObjectKind>> files(rows.size());
   std::vector<uint64_t> hints(rows.size());
   for (size_t i = 0; i < rows.size(); ++i) {
     files[i] = {full_path(location, rows[i]), rows[i].kind};
     hints[i] = rows[i].size_in_bytes;
   }
-  return file_metadata_batch(engine, files, &hints);
+  return file_metadata_batch(engine, files, &hints, checksums);
 }
 
 static GroupBy gpu_group_by(Engine& engine) {
@@ -1222,9 +1266,30 @@ ShallowIdentifierReport shallow_file_identifier(Engine& engine, Library& db, con
 }
 
 FileIdentifierJobRunMetadata run_file_identifier_job(Engine& engine, Library& db, const FileIdentifierJobInit& init) {
-  return run_file_identifier_job_with(
-      db, init, [&](const std::vector<FilePathRow>& rows) { return metadata_of(engine, init.location, rows); },
+  const FileIdentifierJobRunMetadata meta = run_file_identifier_job_with(
+      db, init,
+      [&](const std::vector<FilePathRow>& rows) { return metadata_of(engine, init.location, rows, init.checksums); },
       gpu_group_by(engine));
+  if (!init.checksums) return meta;
+  // Files the indexer saw empty are never orphans (size_in_bytes != 0 in the
+  // filter of file_identifier_job.rs:251-278), so no step reads them, while
+  // the validator hashes them like any file: they get their checksum here,
+  // from the validator's own call. A file that fails keeps none.
+  std::vector<FilePathRow> rest;
+  for (auto& r : db.file_paths_without_checksum(init.location.id, init.sub_materialized_path))
+    if (r.size_in_bytes == 0) rest.push_back(std::move(r));
+  const size_t batch = std::max<size_t>(1, init.batch);
+  for (size_t lo = 0; lo < rest.size(); lo += batch) {
+    const size_t hi = std::min(rest.size(), lo + batch);
+    std::vector<std::string> paths;
+    for (size_t i = lo; i < hi; ++i) paths.push_back(full_path(init.location, rest[i]));
+    const auto sums = engine.file_checksums(paths);
+    db.begin_batch();
+    for (size_t i = lo; i < hi; ++i)
+      if (sums[i - lo].ok()) db.set_integrity_checksum(rest[i].id, sums[i - lo].value());
+    db.end_batch();
+  }
+  return meta;
 }
 
 // ---- object validator -----------------------------------------------------------------
