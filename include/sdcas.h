@@ -371,6 +371,58 @@ int sdcas_dedup(sdcas_ctx *ctx, const uint64_t *keys, const uint8_t *has_key, co
                 size_t n, size_t chunk_size, const uint64_t *existing_keys, size_t n_existing,
                 int64_t *out_link, int64_t *out_created, int64_t *out_linked);
 
+/* ---- duplicates confirmed by checksum ----------------------------------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7: new
+ * symbols alone are a compatible change).
+ *
+ * A cas_id above 100 KiB hashes 57,352 bytes of the file (cas.rs:23-62), so
+ * files of one length that agree in those windows share it whatever else they
+ * hold, and sdcas_dedup links them to one Object, as the reference does. This
+ * group-by over the pair (cas key, 32-byte checksum) — what
+ * sdcas_identify_checksums / sdcas_dev_identify return — says which files
+ * are equal and which cas keys collide. Files i with valid[i] == 0 take no
+ * part (valid may be NULL: all do). A CLASS is the valid files with one key
+ * and one digest. Any output may be NULL.
+ *   out_rep[i]     lowest valid j with keys[j] == keys[i] and all 32 digest
+ *                  bytes equal (i's class); -1 when !valid[i]
+ *   out_key_rep[i] lowest valid j with keys[j] == keys[i] (what the cas key
+ *                  alone says); -1 when !valid[i]
+ *   out_flags[i]   SDCAS_CONFIRM_DUPLICATE: out_rep[i] != i;
+ *                  SDCAS_CONFIRM_COLLISION: another valid file has the key
+ *                  with a different digest (set on EVERY valid file of such a
+ *                  key, also one alone in its class);
+ *                  SDCAS_CONFIRM_SKIPPED: !valid[i], no other bit
+ * The results are exact and do not depend on scheduling. At most 2^30 files
+ * per call (SDCAS_E_CAPACITY beyond); n == 0 is SDCAS_OK with zero counts. */
+#define SDCAS_CONFIRM_DUPLICATE 1u
+#define SDCAS_CONFIRM_COLLISION 2u
+#define SDCAS_CONFIRM_SKIPPED   4u
+typedef struct sdcas_confirm_counts {
+  uint64_t files;           /* valid files */
+  uint64_t classes;         /* distinct (key, digest) pairs */
+  uint64_t keys;            /* distinct keys */
+  uint64_t collided_keys;   /* keys with at least 2 classes */
+  uint64_t collided_files;  /* valid files of collided keys */
+  uint64_t duplicate_files; /* files - classes */
+} sdcas_confirm_counts;
+/* Host arrays: one upload, the group-by, one download. Holds the context as
+ * the path calls do (sdcas_dedup's rules). */
+int sdcas_confirm_duplicates(sdcas_ctx *ctx, const uint64_t *keys, const uint8_t *digests32, const uint8_t *valid,
+                             size_t n, int64_t *out_rep, int64_t *out_key_rep, uint8_t *out_flags,
+                             sdcas_confirm_counts *out_counts);
+/* Device arrays, asynchronous on `stream` with sdcas_dev_hash_messages's
+ * stream rules: takes sdcas_dev_identify's d_out_keys / d_out32 /
+ * d_out_has_key as they are. d_digests32 must be 16-byte aligned
+ * (SDCAS_E_INVALID otherwise, as for NULL keys or digests with n != 0).
+ * d_counts: six u64 in sdcas_confirm_counts' order, overwritten. The
+ * context's tables for n files (16 to 32 bytes per file, and 12 more) are
+ * allocated by the first call that needs them, which waits for the stream:
+ * warm up outside timed regions. */
+int sdcas_dev_confirm_duplicates(sdcas_ctx *ctx, const uint64_t *d_keys, const uint8_t *d_digests32,
+                                 const uint8_t *d_valid, size_t n, int64_t *d_out_rep, int64_t *d_out_key_rep,
+                                 uint8_t *d_out_flags, uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

@@ -124,6 +124,16 @@ class Engine {
               const std::vector<int32_t>& status, size_t chunk_size, const std::vector<uint64_t>& existing_keys,
               sdcas_job_window* window = nullptr);
 
+  // the group-by over (cas key, 32-byte checksum) (sdcas_confirm_duplicates):
+  // digests holds 32 bytes per key; valid may be empty (all files take part)
+  struct Confirm {
+    std::vector<int64_t> rep, key_rep;
+    std::vector<uint8_t> flags;  // SDCAS_CONFIRM_*
+    sdcas_confirm_counts counts{};
+  };
+  Confirm confirm_duplicates(const std::vector<uint64_t>& keys, const std::vector<uint8_t>& digests,
+                             const std::vector<uint8_t>& valid);
+
   sdcas_ctx* raw() { return ctx_; }
 
  private:
@@ -294,6 +304,12 @@ class Library {
   virtual std::vector<FilePathRow> file_paths_without_checksum(int32_t location_id,
                                                                const std::string& sub_materialized_path) = 0;
   virtual void set_integrity_checksum(int32_t file_path_id, const std::string& checksum) = 0;
+  // confirm_duplicates' rows: location_id = ? AND is_dir = false AND cas_id IS
+  // NOT NULL AND integrity_checksum IS NOT NULL [AND materialized_path LIKE
+  // sub%], ORDER BY id. A library that does not override it cannot be
+  // confirmed: the default throws LibraryError.
+  virtual std::vector<FilePathRow> file_paths_with_checksum(int32_t location_id,
+                                                            const std::string& sub_materialized_path);
   // the writes between these calls are one batch (sync.write_ops batches a
   // step's operations, core/crates/sync/src/manager.rs:70-93): one
   // transaction in a database; no-ops in memory
@@ -347,6 +363,7 @@ class MemoryLibrary : public Library {
   int32_t create_object(ObjectKind kind, int64_t date_created) override;
   void connect(int32_t file_path_id, int32_t object_id) override;
   std::vector<FilePathRow> file_paths_without_checksum(int32_t location_id, const std::string& sub) override;
+  std::vector<FilePathRow> file_paths_with_checksum(int32_t location_id, const std::string& sub) override;
   void set_integrity_checksum(int32_t file_path_id, const std::string& checksum) override;
 
  private:
@@ -403,6 +420,7 @@ class SqliteLibrary : public Library {
   std::vector<int32_t> create_objects(const std::vector<std::pair<ObjectKind, int64_t>>& kinds_dates) override;
   void connect(int32_t file_path_id, int32_t object_id) override;
   std::vector<FilePathRow> file_paths_without_checksum(int32_t location_id, const std::string& sub) override;
+  std::vector<FilePathRow> file_paths_with_checksum(int32_t location_id, const std::string& sub) override;
   void set_integrity_checksum(int32_t file_path_id, const std::string& checksum) override;
   void begin_batch() override;
   void end_batch() override;
@@ -585,5 +603,43 @@ struct ObjectValidatorReport {
 };
 
 ObjectValidatorReport run_object_validator_job(Engine& engine, Library& db, const ObjectValidatorJobInit& init);
+
+// ---- duplicates confirmed by checksum ----------------------------------------------
+//
+// The identifier links file_paths by cas_id, which above 100 KiB hashes
+// 57,352 bytes of the file (cas.rs:23-62): files of one length that agree in
+// those windows end on one Object whatever else they hold. Once the rows
+// carry their integrity_checksum too (FileIdentifierJobInit::checksums, or
+// the validator), the pair (cas_id, checksum) says which rows are the same
+// file and which cas_ids collide.
+struct DuplicateReport {
+  // rows with one cas_id and one checksum
+  struct Class {
+    std::string cas_id, checksum;
+    std::vector<int32_t> file_path_ids;  // ascending
+  };
+  // a cas_id whose rows carry more than one checksum
+  struct Collision {
+    std::string cas_id;
+    std::vector<std::vector<int32_t>> classes;  // file_path ids ascending, classes by their first id
+    std::vector<int32_t> object_ids;  // the distinct Objects those rows are linked to, ascending
+  };
+  std::vector<Class> confirmed;       // the classes of two or more rows, ordered by their first id
+  std::vector<Collision> collisions;  // one per collided cas_id, ordered by its first id
+  sdcas_confirm_counts counts{};
+};
+
+// The report's shaping, no GPU: rows in id order and the group-by's answer
+// for them (sdcas_confirm_duplicates' out_rep / out_key_rep / out_flags with
+// row i as file i); rows flagged SDCAS_CONFIRM_SKIPPED are left out. The
+// counts are taken from the three arrays.
+DuplicateReport duplicate_report_from(const std::vector<FilePathRow>& rows, const std::vector<int64_t>& rep,
+                                      const std::vector<int64_t>& key_rep, const std::vector<uint8_t>& flags);
+
+// Read-only: reads Library::file_paths_with_checksum, turns the hex strings
+// into keys and digests (a row whose cas_id is not 16 or whose checksum is not
+// 64 hex characters takes no part), groups them on the GPU
+// (Engine::confirm_duplicates) and shapes the report. Writes nothing.
+DuplicateReport confirm_duplicates(Engine& engine, Library& db, int32_t location_id, const std::string& sub = "");
 
 }  // namespace sdcore

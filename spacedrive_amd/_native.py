@@ -33,6 +33,9 @@ SDCAS_META_HAS_CHECKSUM = 4
 SDCAS_LINK_DROPPED = -(1 << 63)
 SDCAS_LINK_DEFERRED = SDCAS_LINK_DROPPED + 1
 SDCAS_PLAN_HEADER_WORDS = 12
+SDCAS_CONFIRM_DUPLICATE = 1
+SDCAS_CONFIRM_COLLISION = 2
+SDCAS_CONFIRM_SKIPPED = 4
 
 # every entry point include/sdcas.h and include/sdcas_bench.h declare
 ABI_SYMBOLS = [
@@ -40,6 +43,7 @@ ABI_SYMBOLS = [
     "sdcas_file_metadata", "sdcas_identify_checksums", "sdcas_dev_identify",
     "sdcas_checksums", "sdcas_hash_messages", "sdcas_cas_ids_from_messages", "sdcas_dev_reserve",
     "sdcas_dev_hash_messages", "sdcas_dev_sync", "sdcas_dev_bind_stream", "sdcas_dedup", "sdcas_dedup_window", "sdcas_job_plan",
+    "sdcas_confirm_duplicates", "sdcas_dev_confirm_duplicates",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -90,6 +94,16 @@ class JobWindow(ctypes.Structure):
     """sdcas_job_window"""
     _fields_ = [("max_steps", ctypes.c_uint64), ("more", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
                 ("steps", ctypes.c_uint64), ("rows", ctypes.c_uint64), ("rereads", ctypes.c_uint64)]
+
+
+class ConfirmCounts(ctypes.Structure):
+    """sdcas_confirm_counts"""
+    _fields_ = [("files", ctypes.c_uint64), ("classes", ctypes.c_uint64), ("keys", ctypes.c_uint64),
+                ("collided_keys", ctypes.c_uint64), ("collided_files", ctypes.c_uint64),
+                ("duplicate_files", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 _lib = None
@@ -150,6 +164,8 @@ def load():
     L.sdcas_job_plan.argtypes = [_vp, _vp, _sz, _sz, ctypes.POINTER(JobWindow), _vp, _vp]
     L.sdcas_dedup_window.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _sz, ctypes.POINTER(JobWindow), _vp, _vp,
                                      _vp]
+    L.sdcas_confirm_duplicates.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(ConfirmCounts)]
+    L.sdcas_dev_confirm_duplicates.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

@@ -30,6 +30,7 @@
 #include "../../include/sdcas_bench.h"
 #include "../host/cas_io.hpp"
 #include "b3_batch.h"
+#include "confirm.h"
 #include "dist_dedup.h"
 #include "synth.h"
 
@@ -179,6 +180,14 @@ struct sdcas_ctx {
   DevBuf<int32_t> dd_status;
   DevBuf<int64_t> dd_link;
   DevBuf<unsigned long long> dd_counts;
+
+  // the (cas key, checksum) group-by (confirm.hip): its tables, slots and
+  // counters, and sdcas_confirm_duplicates' device copies of the host arrays
+  DevBuf<uint32_t> cf_ws;
+  DevBuf<uint64_t> cf_keys;
+  DevBuf<uint8_t> cf_digests, cf_valid, cf_flags;
+  DevBuf<int64_t> cf_rep;  // rep | key_rep
+  DevBuf<unsigned long long> cf_counts;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -798,6 +807,11 @@ void sdcas_destroy(sdcas_ctx* c) {
   c->dd_status.release();
   c->dd_link.release();
   c->dd_counts.release();
+  c->cf_ws.release();
+  c->cf_keys.release();
+  for (auto* b : {&c->cf_digests, &c->cf_valid, &c->cf_flags}) b->release();
+  c->cf_rep.release();
+  c->cf_counts.release();
   c->dist.release();
   c->sm_d_files.release();
   c->sm_nodes.release();
@@ -1883,6 +1897,77 @@ int sdcas_dev_dedup(sdcas_ctx* c, const uint64_t* d_keys, const uint8_t* d_has_k
   e = dd_local(c->dist, d_keys, d_has_key, d_status, c->dd_ids.p, (uint32_t)n, nullptr, nullptr, 0, chunk_size,
                StepWindow{}, d_out_link, (unsigned long long*)d_counts, call.st);
   return e ? c->hip_fail(e, "dev_dedup") : SDCAS_OK;
+}
+
+// ---- duplicates confirmed by checksum (confirm.hip) ------------------------------
+
+// the group-by's workspace grown to n files; the stream waits first, as an
+// earlier call's kernels may still use the workspace about to be freed
+static int confirm_ws(sdcas_ctx* c, size_t n, hipStream_t st) {
+  const size_t need = (size_t)confirm_ws_words(n);
+  if (need <= c->cf_ws.cap) return SDCAS_OK;
+  hipError_t e = c->scratch_sync();
+  if (!e) e = hipStreamSynchronize(st);
+  if (!e) e = c->cf_ws.ensure(need);
+  return e ? c->hip_fail(e, "confirm workspace") : SDCAS_OK;
+}
+
+int sdcas_dev_confirm_duplicates(sdcas_ctx* c, const uint64_t* d_keys, const uint8_t* d_digests32,
+                                 const uint8_t* d_valid, size_t n, int64_t* d_out_rep, int64_t* d_out_key_rep,
+                                 uint8_t* d_out_flags, uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (n > kConfirmMaxFiles) return c->fail(SDCAS_E_CAPACITY, "dev_confirm_duplicates of %zu files exceeds 2^30", n);
+  if (n && (!d_keys || !d_digests32)) return c->fail(SDCAS_E_INVALID, "dev_confirm_duplicates: null keys or digests");
+  if (n && ((uintptr_t)d_digests32 & 15))
+    return c->fail(SDCAS_E_INVALID, "dev_confirm_duplicates: digests not 16-byte aligned");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  if (n == 0) {
+    if (d_counts && (e = hipMemsetAsync(d_counts, 0, kConfirmCounts * sizeof(uint64_t), call.st)))
+      return c->hip_fail(e, "counts");
+    return SDCAS_OK;
+  }
+  if (int rc = confirm_ws(c, n, call.st)) return rc;
+  e = confirm_duplicates(c->cf_ws.p, d_keys, d_digests32, d_valid, (uint32_t)n, d_out_rep, d_out_key_rep, d_out_flags,
+                         (unsigned long long*)d_counts, call.st);
+  return e ? c->hip_fail(e, "dev_confirm_duplicates") : SDCAS_OK;
+}
+
+int sdcas_confirm_duplicates(sdcas_ctx* c, const uint64_t* keys, const uint8_t* digests32, const uint8_t* valid,
+                             size_t n, int64_t* out_rep, int64_t* out_key_rep, uint8_t* out_flags,
+                             sdcas_confirm_counts* out_counts) {
+  static_assert(sizeof(sdcas_confirm_counts) == kConfirmCounts * sizeof(uint64_t), "six u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  if (n > kConfirmMaxFiles) return c->fail(SDCAS_E_CAPACITY, "confirm_duplicates of %zu files exceeds 2^30", n);
+  if (n && (!keys || !digests32)) return c->fail(SDCAS_E_INVALID, "confirm_duplicates: null keys or digests");
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  if (n == 0) return SDCAS_OK;
+  PathCall call(c);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = c->stream;
+  if ((e = c->cf_keys.ensure(n)) || (e = c->cf_digests.ensure(32 * n)) || (valid && (e = c->cf_valid.ensure(n))) ||
+      (e = c->cf_rep.ensure(2 * n)) || (e = c->cf_flags.ensure(n)) || (e = c->cf_counts.ensure(kConfirmCounts)))
+    return c->hip_fail(e, "confirm buffers");
+  if (int rc = confirm_ws(c, n, st)) return rc;
+  if ((e = hipMemcpyAsync(c->cf_keys.p, keys, 8 * n, hipMemcpyHostToDevice, st)) ||
+      (e = hipMemcpyAsync(c->cf_digests.p, digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
+      (valid && (e = hipMemcpyAsync(c->cf_valid.p, valid, n, hipMemcpyHostToDevice, st))))
+    return c->hip_fail(e, "confirm H2D");
+  int64_t* d_rep = out_rep ? c->cf_rep.p : nullptr;
+  int64_t* d_krep = out_key_rep ? c->cf_rep.p + n : nullptr;
+  if ((e = confirm_duplicates(c->cf_ws.p, c->cf_keys.p, c->cf_digests.p, valid ? c->cf_valid.p : nullptr, (uint32_t)n,
+                              d_rep, d_krep, out_flags ? c->cf_flags.p : nullptr,
+                              out_counts ? c->cf_counts.p : nullptr, st)))
+    return c->hip_fail(e, "confirm_duplicates");
+  if ((out_rep && (e = hipMemcpyAsync(out_rep, d_rep, 8 * n, hipMemcpyDeviceToHost, st))) ||
+      (out_key_rep && (e = hipMemcpyAsync(out_key_rep, d_krep, 8 * n, hipMemcpyDeviceToHost, st))) ||
+      (out_flags && (e = hipMemcpyAsync(out_flags, c->cf_flags.p, n, hipMemcpyDeviceToHost, st))) ||
+      (out_counts && (e = hipMemcpyAsync(out_counts, c->cf_counts.p, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
+    return c->hip_fail(e, "confirm D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "confirm sync");
+  return SDCAS_OK;
 }
 
 int sdcas_dev_set_sort(sdcas_ctx* c, int enable) {

@@ -274,6 +274,42 @@ class Engine:
                                               ctypes.byref(linked)), "sdcas_dedup_window")
         return out, created.value, linked.value, {"steps": win.steps, "rows": win.rows, "rereads": win.rereads}
 
+    # -- duplicates confirmed by checksum -----------------------------------------------
+    def confirm_duplicates(self, keys, digests, valid=None):
+        """the group-by over (cas key, 32-byte checksum) (sdcas_confirm_duplicates):
+        files with one key and one digest are a class, a key with two classes
+        collides -> (rep int64[n]: the class's lowest valid file, key_rep
+        int64[n]: the key's, both -1 for a file with valid == 0, flags uint8[n]:
+        SDCAS_CONFIRM_DUPLICATE | SDCAS_CONFIRM_COLLISION | SDCAS_CONFIRM_SKIPPED,
+        counts: dict of sdcas_confirm_counts' six fields)"""
+        keys = _arr(keys, np.uint64)
+        n = keys.size
+        digests = _arr(digests, np.uint8)
+        if digests.size != 32 * n:
+            raise ValueError(f"confirm_duplicates: {n} keys, {digests.size} digest bytes")
+        va = None if valid is None else _arr(valid, np.uint8)
+        if va is not None and va.size != n:
+            raise ValueError(f"confirm_duplicates: {n} keys, {va.size} valid flags")
+        rep = np.zeros(n, np.int64)
+        key_rep = np.zeros(n, np.int64)
+        flags = np.zeros(n, np.uint8)
+        counts = N.ConfirmCounts()
+        self._check(self.L.sdcas_confirm_duplicates(self.ctx, _ptr(keys), _ptr(digests), _ptr(va), n, _ptr(rep),
+                                                    _ptr(key_rep), _ptr(flags), ctypes.byref(counts)),
+                    "sdcas_confirm_duplicates")
+        return rep, key_rep, flags, counts.as_dict()
+
+    def identify_confirmed(self, paths, size_hints=None):
+        """scan these files and say which are really duplicates:
+        identify_checksums, then confirm_duplicates over the files that have a
+        cas_id and a checksum and were read without error -> (identify_checksums'
+        tuple, confirm_duplicates' tuple)"""
+        ident = self.identify_checksums(paths, size_hints)
+        _, keys, digests, st, fl = ident
+        both = N.SDCAS_META_HAS_CAS_ID | N.SDCAS_META_HAS_CHECKSUM
+        valid = (((fl & both) == both) & (st == 0)).astype(np.uint8)
+        return ident, self.confirm_duplicates(keys, digests, valid)
+
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
     def dev_reserve(self, max_msgs, max_chunks):
         self._check(self.L.sdcas_dev_reserve(self.ctx, int(max_msgs), int(max_chunks)), "dev_reserve")
@@ -287,6 +323,14 @@ class Engine:
         pass over their bytes (sdcas_dev_identify); any output may be 0"""
         self._check(self.L.sdcas_dev_identify(self.ctx, blob, offs, lens, int(n), keys or None, out32 or None,
                                               has_key or None, stream or None), "dev_identify")
+
+    def dev_confirm_duplicates(self, keys, digests, valid, n, rep=0, key_rep=0, flags=0, counts=0, stream=0):
+        """confirm_duplicates over device arrays (sdcas_dev_confirm_duplicates),
+        e.g. dev_identify's keys / out32 / has_key as they are; valid and any
+        output may be 0; counts: six uint64"""
+        self._check(self.L.sdcas_dev_confirm_duplicates(self.ctx, keys or None, digests or None, valid or None,
+                                                        int(n), rep or None, key_rep or None, flags or None,
+                                                        counts or None, stream or None), "dev_confirm_duplicates")
 
     def dev_sync(self, stream=0):
         self._check(self.L.sdcas_dev_sync(self.ctx, stream or None), "dev_sync")

@@ -1320,4 +1320,114 @@ ObjectValidatorReport run_object_validator_job(Engine& engine, Library& db, cons
   return rep;
 }
 
+// ---- duplicates confirmed by checksum -----------------------------------------------
+
+static int hex_nibble(char ch) {
+  if (ch >= '0' && ch <= '9') return ch - '0';
+  if (ch >= 'a' && ch <= 'f') return ch - 'a' + 10;
+  if (ch >= 'A' && ch <= 'F') return ch - 'A' + 10;
+  return -1;
+}
+
+// `bytes` bytes from 2 * bytes hex characters; false when s is anything else
+static bool hex_to_bytes(const std::string& s, uint8_t* out, size_t bytes) {
+  if (s.size() != 2 * bytes) return false;
+  for (size_t i = 0; i < bytes; ++i) {
+    const int hi = hex_nibble(s[2 * i]), lo = hex_nibble(s[2 * i + 1]);
+    if (hi < 0 || lo < 0) return false;
+    out[i] = (uint8_t)(hi << 4 | lo);
+  }
+  return true;
+}
+
+DuplicateReport duplicate_report_from(const std::vector<FilePathRow>& rows, const std::vector<int64_t>& rep,
+                                      const std::vector<int64_t>& key_rep, const std::vector<uint8_t>& flags) {
+  const size_t n = rows.size();
+  if (rep.size() != n || key_rep.size() != n || flags.size() != n)
+    throw std::invalid_argument("duplicate_report_from: rows / rep / key_rep / flags lengths differ");
+  DuplicateReport out;
+  // rows come in id order, so a class's (key's) lowest file is its first row
+  // and walking the rows in order gives every list ascending
+  std::vector<std::vector<int32_t>> members(n);  // at a class's first row: its rows
+  std::vector<std::vector<size_t>> classes(n);   // at a collided key's first row: its classes' first rows
+  for (size_t i = 0; i < n; ++i) {
+    if (flags[i] & SDCAS_CONFIRM_SKIPPED) continue;
+    if (rep[i] < 0 || (size_t)rep[i] > i || key_rep[i] < 0 || key_rep[i] > rep[i])
+      throw std::invalid_argument("duplicate_report_from: row " + std::to_string(i) + " has no valid rep");
+    const bool collided = flags[i] & SDCAS_CONFIRM_COLLISION;
+    ++out.counts.files;
+    out.counts.classes += (size_t)rep[i] == i;
+    out.counts.keys += (size_t)key_rep[i] == i;
+    out.counts.collided_keys += (size_t)key_rep[i] == i && collided;
+    out.counts.collided_files += collided;
+    out.counts.duplicate_files += (size_t)rep[i] != i;
+    members[(size_t)rep[i]].push_back(rows[i].id);
+    if (collided && (size_t)rep[i] == i) classes[(size_t)key_rep[i]].push_back(i);
+  }
+  for (size_t i = 0; i < n; ++i) {
+    if (members[i].size() >= 2)
+      out.confirmed.push_back({rows[i].cas_id.value_or(""), rows[i].integrity_checksum.value_or(""), members[i]});
+    if (classes[i].empty()) continue;
+    DuplicateReport::Collision c;
+    c.cas_id = rows[i].cas_id.value_or("");
+    for (size_t first : classes[i]) c.classes.push_back(members[first]);
+    out.collisions.push_back(std::move(c));
+  }
+  // the Objects the cas-only link merged each collided cas_id's rows into
+  std::vector<std::set<int32_t>> objects(n);
+  for (size_t i = 0; i < n; ++i)
+    if (!(flags[i] & SDCAS_CONFIRM_SKIPPED) && (flags[i] & SDCAS_CONFIRM_COLLISION) && rows[i].object_id)
+      objects[(size_t)key_rep[i]].insert(*rows[i].object_id);
+  size_t next = 0;
+  for (size_t i = 0; i < n; ++i)
+    if (!classes[i].empty()) out.collisions[next++].object_ids.assign(objects[i].begin(), objects[i].end());
+  return out;
+}
+
+Engine::Confirm Engine::confirm_duplicates(const std::vector<uint64_t>& keys, const std::vector<uint8_t>& digests,
+                                           const std::vector<uint8_t>& valid) {
+  const size_t n = keys.size();
+  if (digests.size() != 32 * n || (!valid.empty() && valid.size() != n))
+    throw std::invalid_argument("confirm_duplicates: keys / digests / valid lengths differ");
+  Confirm r;
+  r.rep.assign(n, 0);
+  r.key_rep.assign(n, 0);
+  r.flags.assign(n, 0);
+  const int rc = sdcas_confirm_duplicates(ctx_, keys.data(), digests.data(), valid.empty() ? nullptr : valid.data(), n,
+                                          r.rep.data(), r.key_rep.data(), r.flags.data(), &r.counts);
+  if (rc != SDCAS_OK) fail(rc, "sdcas_confirm_duplicates");
+  return r;
+}
+
+std::vector<FilePathRow> Library::file_paths_with_checksum(int32_t, const std::string&) {
+  throw LibraryError(SDCAS_E_INVALID, "this Library does not implement file_paths_with_checksum");
+}
+
+std::vector<FilePathRow> MemoryLibrary::file_paths_with_checksum(int32_t location_id, const std::string& sub) {
+  std::vector<FilePathRow> out;
+  for (const auto& r : file_paths)
+    if (r.location_id == location_id && !r.is_dir && r.cas_id && r.integrity_checksum && under(r, sub))
+      out.push_back(r);
+  return out;
+}
+
+DuplicateReport confirm_duplicates(Engine& engine, Library& db, int32_t location_id, const std::string& sub) {
+  const std::vector<FilePathRow> rows = db.file_paths_with_checksum(location_id, sub);
+  const size_t n = rows.size();
+  std::vector<uint64_t> keys(n, 0);
+  std::vector<uint8_t> digests(32 * n, 0), valid(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    uint8_t k[8];
+    if (!rows[i].cas_id || !rows[i].integrity_checksum || !hex_to_bytes(*rows[i].cas_id, k, 8) ||
+        !hex_to_bytes(*rows[i].integrity_checksum, &digests[32 * i], 32))
+      continue;
+    keys[i] = hex_to_key(*rows[i].cas_id);
+    valid[i] = 1;
+  }
+  const Engine::Confirm c = engine.confirm_duplicates(keys, digests, valid);
+  DuplicateReport out = duplicate_report_from(rows, c.rep, c.key_rep, c.flags);
+  out.counts = c.counts;
+  return out;
+}
+
 }  // namespace sdcore
