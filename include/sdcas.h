@@ -241,8 +241,11 @@ int sdcas_dev_reserve(sdcas_ctx *ctx, size_t max_msgs, uint64_t max_chunks);
 /* Enqueue the hash of n device-resident messages on `stream` (a hipStream_t,
  * NULL = the context's stream). Requirements: every offset 16-byte aligned,
  * and the blob readable for at least 64 bytes past the end of every message.
- * Either output may be NULL. Asynchronous; sdcas_dev_sync() reports a
- * capacity overflow detected on the device. */
+ * Either output may be NULL. d_blob and d_out32 must be 16-byte aligned and
+ * d_out_keys 8-byte aligned (the kernels load the messages and store the
+ * digests 16 bytes at a time): SDCAS_E_INVALID otherwise, before anything is
+ * enqueued. Asynchronous; sdcas_dev_sync() reports a capacity overflow
+ * detected on the device. */
 int sdcas_dev_hash_messages(sdcas_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_offsets,
                             const uint64_t *d_lens, size_t n, uint8_t *d_out32, uint64_t *d_out_keys,
                             void *stream);
@@ -254,7 +257,9 @@ int sdcas_dev_sync(sdcas_ctx *ctx, void *stream);
  * its bytes; a longer one has its cas message (size, header, four samples,
  * footer) gathered on the device and both messages hashed by the batch
  * kernels; an empty one gets no key and the empty-input digest.
- * d_out_has_key[i] = (d_lens[i] != 0). Any output may be NULL. Asynchronous,
+ * d_out_has_key[i] = (d_lens[i] != 0). Any output may be NULL. d_blob and
+ * d_out32 must be 16-byte aligned and d_out_keys 8-byte aligned
+ * (SDCAS_E_INVALID otherwise, before anything is enqueued). Asynchronous,
  * with sdcas_dev_hash_messages's stream rules; sdcas_dev_sync() reports a
  * capacity overflow detected on the device. Workspace (sdcas_dev_reserve):
  * max_msgs >= n, and max_chunks >= the larger of 2 * (A + 2048) and B, where
@@ -300,7 +305,9 @@ int sdcas_dev_bind_stream(sdcas_ctx *ctx, void *stream, uint64_t token);
  *           message. Every byte of every message exactly once over the
  *           session. Enqueued on `stream`; the segments must stay resident
  *           until the stream has passed this call. Use one stream per session.
- *   finish: 32-byte digests to d_out32 (device, 32*nfiles), on `stream`. */
+ *   finish: 32-byte digests to d_out32 (device, 32*nfiles, 16-byte aligned:
+ *           SDCAS_E_INVALID otherwise, and the session stays open), on
+ *           `stream`. */
 int sdcas_dev_stream_begin(sdcas_ctx *ctx, const uint64_t *lens, size_t nfiles);
 int sdcas_dev_stream_update(sdcas_ctx *ctx, size_t nseg, const uint64_t *h_file, const uint64_t *h_msg_off,
                             const uint64_t *h_len, const uint64_t *h_dev_addr, void *stream);

@@ -951,6 +951,8 @@ int sdcas_dev_hash_messages(sdcas_ctx* c, const uint8_t* d_blob, const uint64_t*
                             size_t n, uint8_t* d_out32, uint64_t* d_out_keys, void* stream) {
   if (!c || (n && (!d_blob || !d_offsets || !d_lens))) return SDCAS_E_INVALID;
   if (n == 0) return SDCAS_OK;
+  if (((uintptr_t)d_blob & 15) || ((uintptr_t)d_out32 & 15) || ((uintptr_t)d_out_keys & 7))
+    return c->fail(SDCAS_E_INVALID, "dev_hash_messages: blob, digests (16 B) or keys (8 B) misaligned");
   DevCall call(c, stream);
   if (call.rc) return call.rc;
   if (n > c->ws.cap_msgs || !c->ws.S)
@@ -979,6 +981,8 @@ int sdcas_dev_identify(sdcas_ctx* c, const uint8_t* d_blob, const uint64_t* d_of
                        uint64_t* d_out_keys, uint8_t* d_out32, uint8_t* d_out_has_key, void* stream) {
   if (!c || (n && (!d_blob || !d_offsets || !d_lens))) return SDCAS_E_INVALID;
   if (n == 0) return SDCAS_OK;
+  if (((uintptr_t)d_blob & 15) || ((uintptr_t)d_out32 & 15) || ((uintptr_t)d_out_keys & 7))
+    return c->fail(SDCAS_E_INVALID, "dev_identify: blob, digests (16 B) or keys (8 B) misaligned");
   DevCall call(c, stream);
   if (call.rc) return call.rc;
   if (n > c->ws.cap_msgs || !c->ws.S || c->ws.cap_slots < 2 * kTile)
@@ -2286,6 +2290,7 @@ int sdcas_dev_stream_update(sdcas_ctx* c, size_t nseg, const uint64_t* h_file, c
 
 int sdcas_dev_stream_finish(sdcas_ctx* c, uint8_t* d_out32, void* stream) {
   if (!c || !d_out32) return SDCAS_E_INVALID;
+  if ((uintptr_t)d_out32 & 15) return c->fail(SDCAS_E_INVALID, "stream_finish: digests not 16-byte aligned");
   DevCall call(c, stream);
   if (call.rc) return call.rc;
   if (!c->sm_active) return c->fail(SDCAS_E_INVALID, "stream_finish without stream_begin");
