@@ -430,6 +430,58 @@ int sdcas_dev_confirm_duplicates(sdcas_ctx *ctx, const uint64_t *d_keys, const u
                                  const uint8_t *d_valid, size_t n, int64_t *d_out_rep, int64_t *d_out_key_rep,
                                  uint8_t *d_out_flags, uint64_t *d_counts, void *stream);
 
+/* ---- duplicate sets: members, sizes and reclaimable bytes ----------------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * The grouped, ordered form of sdcas_confirm_duplicates' out_rep, in
+ * compressed-row layout. The group-by is over the VALUE rep[i]: files with
+ * equal rep[i] carry one label. A file whose rep[i] lies outside [0, n) takes
+ * no part (-1, what confirm writes for a skipped file, or anything else; such
+ * a value is never used as an index). A SET is a label carried by at least
+ * two participating files. sizes[i] is file i's length in bytes; sizes may be
+ * NULL (every set_bytes and reclaimable_bytes are then 0), but not with
+ * SDCAS_SETS_BY_RECLAIMABLE (SDCAS_E_INVALID, as for an unknown order).
+ *   out_set_rep[s]      the set's lowest member
+ *   out_set_bytes[s]    sizes[out_set_rep[s]]: the bytes of one copy
+ *   out_set_offsets[s]  the members of set s are out_members[out_set_offsets[s]
+ *                       .. out_set_offsets[s + 1]), ascending by file index;
+ *                       out_set_offsets[0] == 0, out_set_offsets[sets] == members
+ * Any output may be NULL. The caller provides n / 2 entries for set_rep and
+ * set_bytes, n / 2 + 1 for set_offsets and n for members; entries past sets,
+ * sets + 1 and members are left as they were. The results are exact and do
+ * not depend on scheduling: two calls on one input give the same bytes. At
+ * most 2^30 files per call (SDCAS_E_CAPACITY beyond); n == 0 is SDCAS_OK with
+ * zero counts (and out_set_offsets[0] == 0). */
+#define SDCAS_SETS_BY_REP          0u  /* sets ordered by their lowest member, ascending */
+#define SDCAS_SETS_BY_RECLAIMABLE  1u  /* by reclaimable bytes descending, ties by lowest member ascending */
+typedef struct sdcas_sets_counts {
+  uint64_t files;             /* files that take part */
+  uint64_t sets;              /* labels carried by >= 2 files */
+  uint64_t members;           /* files in those sets */
+  uint64_t duplicate_files;   /* members - sets */
+  uint64_t reclaimable_bytes; /* sum over sets of (count - 1) * set_bytes, modulo 2^64 */
+  uint64_t largest_set;       /* members of the largest set, 0 when there is none */
+} sdcas_sets_counts;
+/* Host arrays: one upload, the device call, the counts down, then exactly
+ * sets / members entries down. Holds the context as the path calls do
+ * (sdcas_dedup's rules). */
+int sdcas_duplicate_sets(sdcas_ctx *ctx, const int64_t *rep, const uint64_t *sizes, size_t n, uint32_t order,
+                         int64_t *out_set_rep, uint64_t *out_set_offsets, uint64_t *out_set_bytes,
+                         int64_t *out_members, sdcas_sets_counts *out_counts);
+/* Device arrays, asynchronous on `stream` with sdcas_dev_hash_messages's
+ * stream rules: takes sdcas_dev_confirm_duplicates' d_out_rep as it is, and
+ * never waits for the device (the numbers of sets and members stay there;
+ * everything sized from them is sized from the bounds n / 2 and n). Every
+ * array must be 8-byte aligned (SDCAS_E_INVALID otherwise, as for a NULL
+ * d_rep with n != 0). d_counts: six u64 in sdcas_sets_counts' order,
+ * overwritten. The context's workspace for n files (36 bytes per file, plus
+ * 1 KiB per 4096 files) is allocated by the first call that needs it, which
+ * waits for the stream: warm up outside timed regions. */
+int sdcas_dev_duplicate_sets(sdcas_ctx *ctx, const int64_t *d_rep, const uint64_t *d_sizes, size_t n, uint32_t order,
+                             int64_t *d_set_rep, uint64_t *d_set_offsets, uint64_t *d_set_bytes,
+                             int64_t *d_members, uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

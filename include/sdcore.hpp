@@ -134,6 +134,18 @@ class Engine {
   Confirm confirm_duplicates(const std::vector<uint64_t>& keys, const std::vector<uint8_t>& digests,
                              const std::vector<uint8_t>& valid);
 
+  // the files grouped by the value rep[i] into sets of two or more
+  // (sdcas_duplicate_sets), trimmed to the counts: set s is
+  // members[set_offsets[s] .. set_offsets[s + 1]), ascending. sizes may be
+  // empty (set_bytes are 0; not with SDCAS_SETS_BY_RECLAIMABLE)
+  struct Sets {
+    std::vector<int64_t> set_rep, members;
+    std::vector<uint64_t> set_offsets, set_bytes;
+    sdcas_sets_counts counts{};
+  };
+  Sets duplicate_sets(const std::vector<int64_t>& rep, const std::vector<uint64_t>& sizes,
+                      uint32_t order = SDCAS_SETS_BY_REP);
+
   sdcas_ctx* raw() { return ctx_; }
 
  private:
@@ -641,5 +653,32 @@ DuplicateReport duplicate_report_from(const std::vector<FilePathRow>& rows, cons
 // 64 hex characters takes no part), groups them on the GPU
 // (Engine::confirm_duplicates) and shapes the report. Writes nothing.
 DuplicateReport confirm_duplicates(Engine& engine, Library& db, int32_t location_id, const std::string& sub = "");
+
+// ---- duplicate sets: what deleting the extra copies gives back ---------------------
+struct ReclaimReport {
+  struct Set {
+    std::vector<int32_t> file_path_ids;  // ascending
+    uint64_t bytes = 0;                  // one copy (the first row's size_in_bytes)
+    uint64_t reclaimable_bytes = 0;      // (rows - 1) * bytes, modulo 2^64
+    bool operator==(const Set& o) const {
+      return file_path_ids == o.file_path_ids && bytes == o.bytes && reclaimable_bytes == o.reclaimable_bytes;
+    }
+  };
+  std::vector<Set> sets;  // in the order of the arrays they were shaped from
+  sdcas_sets_counts counts{};
+};
+
+// The report's shaping, no GPU: rows in id order and sdcas_duplicate_sets'
+// answer for them with row i as file i (Engine::Sets' arrays, trimmed). Throws
+// std::invalid_argument when the arrays do not describe sets of these rows.
+ReclaimReport reclaim_report_from(const std::vector<FilePathRow>& rows, const std::vector<int64_t>& set_rep,
+                                  const std::vector<uint64_t>& set_offsets, const std::vector<uint64_t>& set_bytes,
+                                  const std::vector<int64_t>& members, const sdcas_sets_counts& counts);
+
+// Read-only: reads Library::file_paths_with_checksum, confirms the rows'
+// (cas_id, checksum) pairs (Engine::confirm_duplicates), groups the answer
+// into sets with the rows' size_in_bytes, the most reclaimable bytes first
+// (Engine::duplicate_sets, SDCAS_SETS_BY_RECLAIMABLE). Writes nothing.
+ReclaimReport reclaim_report(Engine& engine, Library& db, int32_t location_id, const std::string& sub = "");
 
 }  // namespace sdcore

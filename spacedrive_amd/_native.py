@@ -36,6 +36,8 @@ SDCAS_PLAN_HEADER_WORDS = 12
 SDCAS_CONFIRM_DUPLICATE = 1
 SDCAS_CONFIRM_COLLISION = 2
 SDCAS_CONFIRM_SKIPPED = 4
+SDCAS_SETS_BY_REP = 0
+SDCAS_SETS_BY_RECLAIMABLE = 1
 
 # every entry point include/sdcas.h and include/sdcas_bench.h declare
 ABI_SYMBOLS = [
@@ -44,6 +46,7 @@ ABI_SYMBOLS = [
     "sdcas_checksums", "sdcas_hash_messages", "sdcas_cas_ids_from_messages", "sdcas_dev_reserve",
     "sdcas_dev_hash_messages", "sdcas_dev_sync", "sdcas_dev_bind_stream", "sdcas_dedup", "sdcas_dedup_window", "sdcas_job_plan",
     "sdcas_confirm_duplicates", "sdcas_dev_confirm_duplicates",  # added after ABI 7
+    "sdcas_duplicate_sets", "sdcas_dev_duplicate_sets",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -101,6 +104,16 @@ class ConfirmCounts(ctypes.Structure):
     _fields_ = [("files", ctypes.c_uint64), ("classes", ctypes.c_uint64), ("keys", ctypes.c_uint64),
                 ("collided_keys", ctypes.c_uint64), ("collided_files", ctypes.c_uint64),
                 ("duplicate_files", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class SetsCounts(ctypes.Structure):
+    """sdcas_sets_counts"""
+    _fields_ = [("files", ctypes.c_uint64), ("sets", ctypes.c_uint64), ("members", ctypes.c_uint64),
+                ("duplicate_files", ctypes.c_uint64), ("reclaimable_bytes", ctypes.c_uint64),
+                ("largest_set", ctypes.c_uint64)]
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
@@ -166,6 +179,9 @@ def load():
                                      _vp]
     L.sdcas_confirm_duplicates.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(ConfirmCounts)]
     L.sdcas_dev_confirm_duplicates.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
+    L.sdcas_duplicate_sets.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_uint32, _vp, _vp, _vp, _vp,
+                                       ctypes.POINTER(SetsCounts)]
+    L.sdcas_dev_duplicate_sets.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "dist_dedup.h"
+#include "wg_scan.h"
 
 namespace sdcas {
 
@@ -238,30 +239,7 @@ __global__ void __launch_bounds__(kStayWG) k_stays_count(const uint8_t* __restri
 // one workgroup: bcnt[b] <- its exclusive prefix; *total <- the sum
 __global__ void __launch_bounds__(1024) k_stays_scan(uint32_t* __restrict__ bcnt, uint32_t nb,
                                                      uint32_t* __restrict__ total) {
-  __shared__ uint32_t ws[16];
-  __shared__ uint32_t carry;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (uint32_t base = 0; base < nb; base += 1024) {
-    const uint32_t i = base + tid;
-    const uint32_t v = i < nb ? bcnt[i] : 0u;
-    uint32_t inc = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-      const uint32_t t = __shfl_up(inc, d);
-      if (lane >= d) inc += t;
-    }
-    if (lane == 63) ws[wave] = inc;
-    __syncthreads();
-    uint32_t before = carry;
-    for (uint32_t w = 0; w < wave; ++w) before += ws[w];
-    if (i < nb) bcnt[i] = before + inc - v;
-    __syncthreads();
-    if (tid == 1023) carry = before + inc;
-    __syncthreads();
-  }
-  if (tid == 0) *total = carry;
+  wg_scan_exclusive_1024(bcnt, nb, total);
 }
 
 __global__ void __launch_bounds__(kStayWG) k_stays_write(const uint8_t* __restrict__ has_key,

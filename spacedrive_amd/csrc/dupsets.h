@@ -1,0 +1,69 @@
+// dupsets.h — duplicate sets from a per-file label (dupsets.hip): the grouped,
+// ordered form of sdcas_confirm_duplicates' rep, with the bytes of one copy
+// and what deleting the extra copies gives back.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace sdcas {
+
+constexpr uint64_t kDupsetsMaxFiles = 1ull << 30;  // file indices and set ranks are 32-bit
+constexpr uint32_t kDupsetsCounts = 6;             // sdcas_sets_counts' words
+constexpr uint32_t kDupsetsTile = 4096;            // files (sets, histogram words) per workgroup
+constexpr uint32_t kDupsetsBySetRep = 0, kDupsetsByReclaimable = 1;  // SDCAS_SETS_BY_*
+
+// The workspace for n files, in u32 words from its start (every offset even,
+// so the u64 parts are 8-byte aligned when the workspace is):
+//   cnt, low, rank      n each      per label: files, lowest file, final set rank
+//   hd_file/cnt/label   h each      per set in rep order (h = n / 2 + 1)
+//   fcnt                h           per set in final order: files, then their offsets
+//   key_a, key_b        n + 2 each  the sorts' keys, ping and pong (u64 per set or u32 per member)
+//   val_a, val_b        n each      the sorts' values
+//   hist                256 per tile of n
+//   bsum, tcnt          per-tile sums of the scans and of the compactions
+//   tot                 4           sets, members in sets, a scan's unused total
+//   counts              6 u64
+// 9 words = 36 bytes per file, plus 1/16 word per file of histogram.
+struct DupsetsLayout {
+  uint64_t cnt, low, rank, hd_file, hd_cnt, hd_label, fcnt, key_a, key_b, val_a, val_b, hist, bsum, tcnt, tot, counts,
+      words;
+  uint32_t h, tiles;
+};
+inline uint32_t dupsets_tiles(uint64_t m) { return m ? (uint32_t)((m + kDupsetsTile - 1) / kDupsetsTile) : 1u; }
+inline DupsetsLayout dupsets_layout(uint64_t n) {
+  DupsetsLayout l{};
+  const uint64_t ne = (n + 1) & ~1ull;
+  l.h = (uint32_t)(n / 2 + 1);
+  const uint64_t he = ((uint64_t)l.h + 1) & ~1ull;
+  l.tiles = dupsets_tiles(n);
+  uint64_t o = 0;
+  auto take = [&o](uint64_t words) {
+    const uint64_t at = o;
+    o += (words + 1) & ~1ull;
+    return at;
+  };
+  l.cnt = take(ne), l.low = take(ne), l.rank = take(ne);
+  l.hd_file = take(he), l.hd_cnt = take(he), l.hd_label = take(he), l.fcnt = take(he);
+  l.key_a = take(ne + 2), l.key_b = take(ne + 2), l.val_a = take(ne), l.val_b = take(ne);
+  l.hist = take(256ull * l.tiles);
+  l.bsum = take((uint64_t)dupsets_tiles(256ull * l.tiles) + dupsets_tiles(l.h) + 2);
+  l.tcnt = take((uint64_t)l.tiles + 2);
+  l.tot = take(4);
+  l.counts = take(2 * kDupsetsCounts);
+  l.words = o;
+  return l;
+}
+inline uint64_t dupsets_ws_words(uint64_t n) { return dupsets_layout(n).words; }
+
+// rep[n] (i64) and sizes[n] (u64, may be null): device inputs. set_rep /
+// set_bytes (n / 2 entries), set_offsets (n / 2 + 1), members (n) and counts
+// (u64[kDupsetsCounts], overwritten) may each be null; entries past the number
+// of sets / members are not written. ws: dupsets_ws_words(n) words, 8-byte
+// aligned. Enqueues on st and never waits for it; n in [1, kDupsetsMaxFiles],
+// order a kDupsetsBy* with sizes non-null for kDupsetsByReclaimable.
+hipError_t duplicate_sets(uint32_t* ws, const int64_t* rep, const uint64_t* sizes, uint32_t n, uint32_t order,
+                          int64_t* set_rep, uint64_t* set_offsets, uint64_t* set_bytes, int64_t* members,
+                          unsigned long long* counts, hipStream_t st);
+
+}  // namespace sdcas

@@ -31,6 +31,7 @@
 #include "../host/cas_io.hpp"
 #include "b3_batch.h"
 #include "confirm.h"
+#include "dupsets.h"
 #include "dist_dedup.h"
 #include "synth.h"
 
@@ -188,6 +189,13 @@ struct sdcas_ctx {
   DevBuf<uint8_t> cf_digests, cf_valid, cf_flags;
   DevBuf<int64_t> cf_rep;  // rep | key_rep
   DevBuf<unsigned long long> cf_counts;
+
+  // duplicate sets (dupsets.hip): the workspace, and sdcas_duplicate_sets'
+  // device copies of the host arrays
+  DevBuf<uint32_t> ds_ws;
+  DevBuf<int64_t> ds_in;   // rep | sizes
+  DevBuf<int64_t> ds_out;  // set_rep | set_offsets | set_bytes | members
+  DevBuf<unsigned long long> ds_counts;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -812,6 +820,9 @@ void sdcas_destroy(sdcas_ctx* c) {
   for (auto* b : {&c->cf_digests, &c->cf_valid, &c->cf_flags}) b->release();
   c->cf_rep.release();
   c->cf_counts.release();
+  c->ds_ws.release();
+  for (auto* b : {&c->ds_in, &c->ds_out}) b->release();
+  c->ds_counts.release();
   c->dist.release();
   c->sm_d_files.release();
   c->sm_nodes.release();
@@ -1971,6 +1982,106 @@ int sdcas_confirm_duplicates(sdcas_ctx* c, const uint64_t* keys, const uint8_t* 
       (out_counts && (e = hipMemcpyAsync(out_counts, c->cf_counts.p, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
     return c->hip_fail(e, "confirm D2H");
   if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "confirm sync");
+  return SDCAS_OK;
+}
+
+// ---- duplicate sets (dupsets.hip) ----------------------------------------------
+
+// the workspace grown to n files; the stream waits first, as an earlier call's
+// kernels may still use the workspace about to be freed
+static int dupsets_ws(sdcas_ctx* c, size_t n, hipStream_t st) {
+  const size_t need = (size_t)dupsets_ws_words(n);
+  if (need <= c->ds_ws.cap) return SDCAS_OK;
+  hipError_t e = c->scratch_sync();
+  if (!e) e = hipStreamSynchronize(st);
+  if (!e) e = c->ds_ws.ensure(need);
+  return e ? c->hip_fail(e, "duplicate sets workspace") : SDCAS_OK;
+}
+
+static int dupsets_args(sdcas_ctx* c, const char* who, const void* rep, const void* sizes, size_t n, uint32_t order) {
+  if (order != SDCAS_SETS_BY_REP && order != SDCAS_SETS_BY_RECLAIMABLE)
+    return c->fail(SDCAS_E_INVALID, "%s: unknown order %u", who, order);
+  if (order == SDCAS_SETS_BY_RECLAIMABLE && !sizes)
+    return c->fail(SDCAS_E_INVALID, "%s: the order by reclaimable bytes needs sizes", who);
+  if (n > kDupsetsMaxFiles) return c->fail(SDCAS_E_CAPACITY, "%s of %zu files exceeds 2^30", who, n);
+  if (n && !rep) return c->fail(SDCAS_E_INVALID, "%s: null rep", who);
+  return SDCAS_OK;
+}
+
+int sdcas_dev_duplicate_sets(sdcas_ctx* c, const int64_t* d_rep, const uint64_t* d_sizes, size_t n, uint32_t order,
+                             int64_t* d_set_rep, uint64_t* d_set_offsets, uint64_t* d_set_bytes, int64_t* d_members,
+                             uint64_t* d_counts, void* stream) {
+  static_assert(SDCAS_SETS_BY_REP == kDupsetsBySetRep && SDCAS_SETS_BY_RECLAIMABLE == kDupsetsByReclaimable, "orders");
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = dupsets_args(c, "dev_duplicate_sets", d_rep, d_sizes, n, order)) return rc;
+  if (((uintptr_t)d_rep | (uintptr_t)d_sizes | (uintptr_t)d_set_rep | (uintptr_t)d_set_offsets |
+       (uintptr_t)d_set_bytes | (uintptr_t)d_members | (uintptr_t)d_counts) & 7)
+    return c->fail(SDCAS_E_INVALID, "dev_duplicate_sets: an array is not 8-byte aligned");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  if (n == 0) {
+    if (d_counts && (e = hipMemsetAsync(d_counts, 0, kDupsetsCounts * sizeof(uint64_t), call.st)))
+      return c->hip_fail(e, "counts");
+    if (d_set_offsets && (e = hipMemsetAsync(d_set_offsets, 0, sizeof(uint64_t), call.st)))
+      return c->hip_fail(e, "set_offsets");
+    return SDCAS_OK;
+  }
+  if (int rc = dupsets_ws(c, n, call.st)) return rc;
+  e = duplicate_sets(c->ds_ws.p, d_rep, d_sizes, (uint32_t)n, order, d_set_rep, d_set_offsets, d_set_bytes, d_members,
+                     (unsigned long long*)d_counts, call.st);
+  return e ? c->hip_fail(e, "dev_duplicate_sets") : SDCAS_OK;
+}
+
+int sdcas_duplicate_sets(sdcas_ctx* c, const int64_t* rep, const uint64_t* sizes, size_t n, uint32_t order,
+                         int64_t* out_set_rep, uint64_t* out_set_offsets, uint64_t* out_set_bytes,
+                         int64_t* out_members, sdcas_sets_counts* out_counts) {
+  static_assert(sizeof(sdcas_sets_counts) == kDupsetsCounts * sizeof(uint64_t), "six u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = dupsets_args(c, "duplicate_sets", rep, sizes, n, order)) return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  if (n == 0) {
+    if (out_set_offsets) out_set_offsets[0] = 0;
+    return SDCAS_OK;
+  }
+  PathCall call(c);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = c->stream;
+  const size_t h = n / 2;
+  if ((e = c->ds_in.ensure(2 * n)) || (e = c->ds_out.ensure(3 * h + 1 + n)) ||
+      (e = c->ds_counts.ensure(kDupsetsCounts)))
+    return c->hip_fail(e, "duplicate sets buffers");
+  if (int rc = dupsets_ws(c, n, st)) return rc;
+  int64_t* d_rep = c->ds_in.p;
+  uint64_t* d_sizes = sizes ? reinterpret_cast<uint64_t*>(c->ds_in.p + n) : nullptr;
+  if ((e = hipMemcpyAsync(d_rep, rep, 8 * n, hipMemcpyHostToDevice, st)) ||
+      (sizes && (e = hipMemcpyAsync(d_sizes, sizes, 8 * n, hipMemcpyHostToDevice, st))))
+    return c->hip_fail(e, "duplicate sets H2D");
+  int64_t* d_set_rep = c->ds_out.p;
+  uint64_t* d_set_offsets = reinterpret_cast<uint64_t*>(c->ds_out.p + h);
+  uint64_t* d_set_bytes = reinterpret_cast<uint64_t*>(c->ds_out.p + 2 * h + 1);
+  int64_t* d_members = c->ds_out.p + 3 * h + 1;
+  if ((e = duplicate_sets(c->ds_ws.p, d_rep, d_sizes, (uint32_t)n, order, out_set_rep ? d_set_rep : nullptr,
+                          out_set_offsets ? d_set_offsets : nullptr, out_set_bytes ? d_set_bytes : nullptr,
+                          out_members ? d_members : nullptr, c->ds_counts.p, st)))
+    return c->hip_fail(e, "duplicate_sets");
+  // the counts down first: they say how many entries of each array follow
+  sdcas_sets_counts cts;
+  if ((e = hipMemcpyAsync(&cts, c->ds_counts.p, sizeof cts, hipMemcpyDeviceToHost, st)) ||
+      (e = hipStreamSynchronize(st)))
+    return c->hip_fail(e, "duplicate sets counts");
+  if (cts.sets > h || cts.members > n) return c->fail(SDCAS_E_HIP, "duplicate_sets: counts out of range");
+  if ((out_set_rep && cts.sets && (e = hipMemcpyAsync(out_set_rep, d_set_rep, 8 * cts.sets, hipMemcpyDeviceToHost, st))) ||
+      (out_set_offsets &&
+       (e = hipMemcpyAsync(out_set_offsets, d_set_offsets, 8 * (cts.sets + 1), hipMemcpyDeviceToHost, st))) ||
+      (out_set_bytes && cts.sets &&
+       (e = hipMemcpyAsync(out_set_bytes, d_set_bytes, 8 * cts.sets, hipMemcpyDeviceToHost, st))) ||
+      (out_members && cts.members &&
+       (e = hipMemcpyAsync(out_members, d_members, 8 * cts.members, hipMemcpyDeviceToHost, st))))
+    return c->hip_fail(e, "duplicate sets D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "duplicate sets sync");
+  if (out_counts) *out_counts = cts;
   return SDCAS_OK;
 }
 

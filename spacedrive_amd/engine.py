@@ -310,6 +310,43 @@ class Engine:
         valid = (((fl & both) == both) & (st == 0)).astype(np.uint8)
         return ident, self.confirm_duplicates(keys, digests, valid)
 
+    # -- duplicate sets ---------------------------------------------------------------
+    def duplicate_sets(self, rep, sizes=None, order=N.SDCAS_SETS_BY_REP):
+        """the files grouped by the value rep[i] (confirm_duplicates' rep;
+        values outside [0, n) take no part) into sets of two or more
+        (sdcas_duplicate_sets) -> (set_rep int64[S]: each set's lowest member,
+        set_offsets uint64[S + 1], set_bytes uint64[S]: sizes[set_rep],
+        members int64[M]: set s is members[set_offsets[s]:set_offsets[s + 1]],
+        ascending, counts: dict of sdcas_sets_counts' six fields). order:
+        SDCAS_SETS_BY_REP, or SDCAS_SETS_BY_RECLAIMABLE (needs sizes): most
+        reclaimable bytes first, ties by set_rep"""
+        rep = _arr(rep, np.int64)
+        n = rep.size
+        sz = None if sizes is None else _arr(sizes, np.uint64)
+        if sz is not None and sz.size != n:
+            raise ValueError(f"duplicate_sets: {n} reps, {sz.size} sizes")
+        set_rep = np.zeros(n // 2, np.int64)
+        set_offsets = np.zeros(n // 2 + 1, np.uint64)
+        set_bytes = np.zeros(n // 2, np.uint64)
+        members = np.zeros(n, np.int64)
+        counts = N.SetsCounts()
+        # (an empty sizes array is still "sizes given": never dereferenced with n == 0)
+        self._check(self.L.sdcas_duplicate_sets(self.ctx, _ptr(rep), None if sz is None else _ptr(sz) or 8, n,
+                                                int(order), _ptr(set_rep),
+                                                _ptr(set_offsets), _ptr(set_bytes), _ptr(members),
+                                                ctypes.byref(counts)), "sdcas_duplicate_sets")
+        s, m = int(counts.sets), int(counts.members)
+        return set_rep[:s].copy(), set_offsets[:s + 1].copy(), set_bytes[:s].copy(), members[:m].copy(), \
+            counts.as_dict()
+
+    def identify_duplicate_sets(self, paths, size_hints=None, order=N.SDCAS_SETS_BY_RECLAIMABLE):
+        """scan these files and list the sets of equal ones, the biggest win
+        first: identify_confirmed, then duplicate_sets over its rep and the
+        sizes identify_checksums returned -> (identify_checksums' tuple,
+        confirm_duplicates' tuple, duplicate_sets' tuple)"""
+        ident, confirm = self.identify_confirmed(paths, size_hints)
+        return ident, confirm, self.duplicate_sets(confirm[0], ident[0], order)
+
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
     def dev_reserve(self, max_msgs, max_chunks):
         self._check(self.L.sdcas_dev_reserve(self.ctx, int(max_msgs), int(max_chunks)), "dev_reserve")
@@ -331,6 +368,17 @@ class Engine:
         self._check(self.L.sdcas_dev_confirm_duplicates(self.ctx, keys or None, digests or None, valid or None,
                                                         int(n), rep or None, key_rep or None, flags or None,
                                                         counts or None, stream or None), "dev_confirm_duplicates")
+
+    def dev_duplicate_sets(self, rep, sizes, n, set_rep=0, set_offsets=0, set_bytes=0, members=0, counts=0, order=0,
+                           stream=0):
+        """duplicate_sets over device arrays (sdcas_dev_duplicate_sets), e.g.
+        dev_confirm_duplicates' rep as it is; sizes and any output may be 0;
+        set_rep / set_bytes hold n // 2 entries, set_offsets n // 2 + 1,
+        members n, counts six uint64; nothing waits for the device"""
+        self._check(self.L.sdcas_dev_duplicate_sets(self.ctx, rep or None, sizes or None, int(n), int(order),
+                                                    set_rep or None, set_offsets or None, set_bytes or None,
+                                                    members or None, counts or None, stream or None),
+                    "dev_duplicate_sets")
 
     def dev_sync(self, stream=0):
         self._check(self.L.sdcas_dev_sync(self.ctx, stream or None), "dev_sync")

@@ -1430,4 +1430,78 @@ DuplicateReport confirm_duplicates(Engine& engine, Library& db, int32_t location
   return out;
 }
 
+Engine::Sets Engine::duplicate_sets(const std::vector<int64_t>& rep, const std::vector<uint64_t>& sizes,
+                                    uint32_t order) {
+  const size_t n = rep.size();
+  if (!sizes.empty() && sizes.size() != n) throw std::invalid_argument("duplicate_sets: rep / sizes lengths differ");
+  Sets r;
+  r.set_rep.assign(n / 2, 0);
+  r.set_offsets.assign(n / 2 + 1, 0);
+  r.set_bytes.assign(n / 2, 0);
+  r.members.assign(n, 0);
+  const int rc = sdcas_duplicate_sets(ctx_, rep.data(), sizes.empty() ? nullptr : sizes.data(), n, order,
+                                      r.set_rep.data(), r.set_offsets.data(), r.set_bytes.data(), r.members.data(),
+                                      &r.counts);
+  if (rc != SDCAS_OK) fail(rc, "sdcas_duplicate_sets");
+  r.set_rep.resize(r.counts.sets);
+  r.set_offsets.resize(r.counts.sets + 1);
+  r.set_bytes.resize(r.counts.sets);
+  r.members.resize(r.counts.members);
+  return r;
+}
+
+ReclaimReport reclaim_report_from(const std::vector<FilePathRow>& rows, const std::vector<int64_t>& set_rep,
+                                  const std::vector<uint64_t>& set_offsets, const std::vector<uint64_t>& set_bytes,
+                                  const std::vector<int64_t>& members, const sdcas_sets_counts& counts) {
+  const size_t sets = set_rep.size();
+  if (sets == 0 && set_offsets.empty() && set_bytes.empty() && members.empty()) {  // nothing at all: no sets
+    ReclaimReport none;
+    none.counts = counts;
+    return none;
+  }
+  if (set_bytes.size() != sets || set_offsets.size() != sets + 1 || set_offsets.front() != 0 ||
+      set_offsets.back() != members.size())
+    throw std::invalid_argument("reclaim_report_from: set_rep / set_offsets / set_bytes / members lengths differ");
+  ReclaimReport out;
+  out.counts = counts;
+  out.sets.resize(sets);
+  for (size_t s = 0; s < sets; ++s) {
+    if (set_offsets[s] > set_offsets[s + 1] || set_offsets[s + 1] > members.size())
+      throw std::invalid_argument("reclaim_report_from: set_offsets do not ascend");
+    ReclaimReport::Set& set = out.sets[s];
+    for (uint64_t j = set_offsets[s]; j < set_offsets[s + 1]; ++j) {
+      if (members[j] < 0 || (uint64_t)members[j] >= rows.size())
+        throw std::invalid_argument("reclaim_report_from: member " + std::to_string(j) + " is no row");
+      set.file_path_ids.push_back(rows[(size_t)members[j]].id);
+    }
+    if (set.file_path_ids.empty()) throw std::invalid_argument("reclaim_report_from: an empty set");
+    // rows are in id order, so ascending members are ascending ids; a caller's
+    // rows in another order still get what the header promises
+    std::sort(set.file_path_ids.begin(), set.file_path_ids.end());
+    set.bytes = set_bytes[s];
+    set.reclaimable_bytes = (uint64_t)(set.file_path_ids.size() - 1) * set.bytes;
+  }
+  return out;
+}
+
+ReclaimReport reclaim_report(Engine& engine, Library& db, int32_t location_id, const std::string& sub) {
+  const std::vector<FilePathRow> rows = db.file_paths_with_checksum(location_id, sub);
+  const size_t n = rows.size();
+  std::vector<uint64_t> keys(n, 0), sizes(n, 0);
+  std::vector<uint8_t> digests(32 * n, 0), valid(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    sizes[i] = rows[i].size_in_bytes;
+    uint8_t k[8];
+    if (!rows[i].cas_id || !rows[i].integrity_checksum || !hex_to_bytes(*rows[i].cas_id, k, 8) ||
+        !hex_to_bytes(*rows[i].integrity_checksum, &digests[32 * i], 32))
+      continue;
+    keys[i] = hex_to_key(*rows[i].cas_id);
+    valid[i] = 1;
+  }
+  if (n == 0) return ReclaimReport{};
+  const Engine::Confirm c = engine.confirm_duplicates(keys, digests, valid);
+  const Engine::Sets s = engine.duplicate_sets(c.rep, sizes, SDCAS_SETS_BY_RECLAIMABLE);
+  return reclaim_report_from(rows, s.set_rep, s.set_offsets, s.set_bytes, s.members, s.counts);
+}
+
 }  // namespace sdcore
