@@ -482,6 +482,120 @@ int sdcas_dev_duplicate_sets(sdcas_ctx *ctx, const int64_t *d_rep, const uint64_
                              int64_t *d_set_rep, uint64_t *d_set_offsets, uint64_t *d_set_bytes,
                              int64_t *d_members, uint64_t *d_counts, void *stream);
 
+/* ---- duplicate directories: tree digests and top-most sets ----------------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * A tree is n ENTRIES, files and directories in any order: parent[i] is the
+ * index of the directory that holds entry i, or -1 for a root (several roots
+ * are allowed); is_dir[i] says which kind it is; name32[i] is BLAKE3 of the
+ * entry's name bytes (sdcas_hash_messages / sdcas_dev_hash_messages: these
+ * calls never see strings). A file takes part with digests32[i] when
+ * valid[i] != 0 (valid NULL: every file does). A directory is COMPLETE when
+ * every file entry below it, at any depth, is valid; one with no file entry
+ * below it is complete and EMPTY. A complete directory d with k direct
+ * children has the digest T(d) = BLAKE3(M(d)):
+ *   M(d) = "SDTREE01" || le64(k) || R(c_0) || ... || R(c_{k-1})   16 + 72 k bytes
+ *   R(c) = name32[c] || content(c) || le64(kind(c))               kind: 0 file, 1 directory
+ *   content(c) = digests32[c] for a file, T(c) for a directory
+ * with the children in ascending order of name32 compared as 32 bytes
+ * (memcmp), equal name32 by ascending entry index. The TREE KEY of d is the
+ * u64 whose big-endian bytes are T(d)[0..8), the convention of the cas keys.
+ * tree_bytes[i] is sizes[i] for a file and, for a directory, the sum of sizes
+ * over every file entry below it modulo 2^64, valid or not (sizes NULL: 0
+ * everywhere); tree_files[i] is 1 for a file and the number of file entries
+ * below for a directory. The results are exact and do not depend on
+ * scheduling: two calls on one input give the same bytes. At most 2^30
+ * entries per call; n == 0 is SDCAS_OK with zero counts; any output may be
+ * NULL. */
+#define SDCAS_TREE_MAX_DEPTH 4096
+/* GPU-free, like sdcas_job_plan: checks the shape and describes it.
+ * SDCAS_E_CAPACITY for n > 2^30; SDCAS_E_INVALID for a parent outside
+ * [-1, n), a parent that is not a directory or an entry that is its own
+ * ancestor (a cycle); SDCAS_E_CAPACITY for more than SDCAS_TREE_MAX_DEPTH
+ * levels. out_depth[i]: 0 for a root; out_children[i]: direct children;
+ * *out_levels: 1 + the largest depth (0 for n == 0). */
+int sdcas_tree_plan(const int64_t *parent, const uint8_t *is_dir, size_t n, uint32_t *out_depth,
+                    uint64_t *out_children, uint64_t *out_levels);
+
+#define SDCAS_TREE_DIR        1u  /* the entry is a directory */
+#define SDCAS_TREE_INCOMPLETE 2u  /* a directory with an invalid file below it: no digest */
+#define SDCAS_TREE_EMPTY      4u  /* a directory with no file entry below it */
+typedef struct sdcas_tree_counts {
+  uint64_t entries;
+  uint64_t dirs;
+  uint64_t complete_dirs;
+  uint64_t empty_dirs;
+  uint64_t levels;
+  uint64_t largest_dir; /* most direct children */
+} sdcas_tree_counts;
+/* keys, digests32 and valid are IN for file entries and OUT for directory
+ * entries, so that the three arrays go into sdcas_confirm_duplicates as they
+ * are:
+ *   directory, complete, not empty: digests32 = T(d), keys = tree key, valid = 1
+ *   directory, complete, empty:     digests32 = T(d), keys = tree key, valid = 0
+ *                                   (takes no part in a group-by)
+ *   directory, incomplete:          digests32 = 32 zero bytes, keys = 0, valid = 0
+ * File entries' slots are never changed. valid may be NULL (all files valid;
+ * nothing is written for directories then: pass out_flags to tell them
+ * apart); keys may be NULL; name32 and digests32 may not (SDCAS_E_INVALID with
+ * n != 0), and shape errors are sdcas_tree_plan's. Host arrays: one upload,
+ * the device call, one download. */
+int sdcas_tree_digests(sdcas_ctx *ctx, const int64_t *parent, const uint8_t *is_dir, const uint8_t *name32,
+                       const uint64_t *sizes, size_t n, uint64_t *keys, uint8_t *digests32, uint8_t *valid,
+                       uint64_t *out_tree_bytes, uint64_t *out_tree_files, uint8_t *out_flags,
+                       sdcas_tree_counts *out_counts);
+/* parent / is_dir stay HOST arrays (the shape comes from the indexer or the
+ * database in every caller, as sdcas_dev_stream_update's descriptors do): the
+ * call reads them before it returns. Everything else is device memory.
+ * Asynchronous on `stream` with sdcas_dev_hash_messages's stream rules. The
+ * shape is checked, and misalignment refused (d_name32 / d_digests32 16-byte
+ * aligned, the u64 arrays 8-byte aligned, SDCAS_E_INVALID otherwise), before
+ * anything is enqueued. d_counts: six u64 in sdcas_tree_counts' order,
+ * overwritten. One hash batch is enqueued per level of directories, deepest
+ * first. The context's workspace (52 bytes per entry, 64 per directory of the
+ * fullest level, that level's messages, and the batch workspace for them) is
+ * grown by the first call that needs it, which waits for the stream: warm up
+ * outside timed regions. After that the call waits for the device only when
+ * the shape upload of its fourth-last predecessor has not finished. */
+int sdcas_dev_tree_digests(sdcas_ctx *ctx, const int64_t *parent, const uint8_t *is_dir, const uint8_t *d_name32,
+                           const uint64_t *d_sizes, size_t n, uint64_t *d_keys, uint8_t *d_digests32,
+                           uint8_t *d_valid, uint64_t *d_out_tree_bytes, uint64_t *d_out_tree_files,
+                           uint8_t *d_out_flags, uint64_t *d_counts, void *stream);
+
+/* Top-most duplicates. rep[i] is any per-entry label, e.g. what
+ * sdcas_confirm_duplicates writes when it is run once over ALL entries,
+ * directories included; a label outside [0, n) takes no part.
+ *   DUP(i):     rep[i] is carried by at least 2 participating entries
+ *   NESTED(i):  DUP(i), parent[i] >= 0 and DUP(parent[i]): the entry lies
+ *               inside a directory that is itself a duplicate
+ *   out_top_rep[i]: rep[i] if DUP(i) and at least one carrier of that label
+ *               is not NESTED, else -1
+ *   out_flags[i]: SDCAS_TOP_DUP | SDCAS_TOP_NESTED
+ * A class whose members are all nested is implied by a set above it and is
+ * dropped; a class with a member outside any duplicate directory is kept
+ * whole. sdcas_duplicate_sets(out_top_rep, tree_bytes, BY_RECLAIMABLE) is then
+ * the report. */
+#define SDCAS_TOP_DUP    1u
+#define SDCAS_TOP_NESTED 2u
+typedef struct sdcas_top_counts {
+  uint64_t entries;         /* participating */
+  uint64_t dup_entries;
+  uint64_t nested_entries;
+  uint64_t top_entries;     /* out_top_rep != -1 */
+  uint64_t kept_classes;
+  uint64_t dropped_classes;
+} sdcas_top_counts;
+/* Host arrays; a parent outside [-1, n) is SDCAS_E_INVALID here. */
+int sdcas_tree_top(sdcas_ctx *ctx, const int64_t *parent, const int64_t *rep, size_t n, int64_t *out_top_rep,
+                   uint8_t *out_flags, sdcas_top_counts *out_counts);
+/* All device arrays (parent too), 8-byte aligned; a parent outside [-1, n)
+ * is treated as -1 and never used as an index, as sdcas_dev_duplicate_sets
+ * treats a stray rep. Never waits for the device once the workspace (12
+ * bytes per entry) exists. d_counts: six u64 in sdcas_top_counts' order. */
+int sdcas_dev_tree_top(sdcas_ctx *ctx, const int64_t *d_parent, const int64_t *d_rep, size_t n,
+                       int64_t *d_out_top_rep, uint8_t *d_out_flags, uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

@@ -146,6 +146,30 @@ class Engine {
   Sets duplicate_sets(const std::vector<int64_t>& rep, const std::vector<uint64_t>& sizes,
                       uint32_t order = SDCAS_SETS_BY_REP);
 
+  // BLAKE3 of each string (sdcas_hash_messages): 32 bytes per string, the
+  // name digests the tree calls take
+  std::vector<uint8_t> hash_strings(const std::vector<std::string>& strings);
+
+  // a digest per directory (sdcas_tree_digests): keys / digests / valid hold
+  // the FILE entries' values and come back with the directory entries' slots
+  // filled; sizes may be empty (every tree_bytes is 0)
+  struct TreeDigests {
+    std::vector<uint64_t> keys, tree_bytes, tree_files;
+    std::vector<uint8_t> digests, valid, flags;  // flags: SDCAS_TREE_*
+    sdcas_tree_counts counts{};
+  };
+  TreeDigests tree_digests(const std::vector<int64_t>& parent, const std::vector<uint8_t>& is_dir,
+                           const std::vector<uint8_t>& name32, const std::vector<uint64_t>& sizes,
+                           const std::vector<uint64_t>& keys, const std::vector<uint8_t>& digests,
+                           const std::vector<uint8_t>& valid);
+  // the top-most duplicates (sdcas_tree_top) of a label per entry
+  struct TreeTop {
+    std::vector<int64_t> top_rep;
+    std::vector<uint8_t> flags;  // SDCAS_TOP_*
+    sdcas_top_counts counts{};
+  };
+  TreeTop tree_top(const std::vector<int64_t>& parent, const std::vector<int64_t>& rep);
+
   sdcas_ctx* raw() { return ctx_; }
 
  private:
@@ -325,6 +349,10 @@ class Library {
   // the writes between these calls are one batch (sync.write_ops batches a
   // step's operations, core/crates/sync/src/manager.rs:70-93): one
   // transaction in a database; no-ops in memory
+  // tree_report's rows: location_id = ? [AND materialized_path LIKE sub%],
+  // files and directories, ORDER BY id (the default throws LibraryError)
+  virtual std::vector<FilePathRow> file_paths_in_location(int32_t location_id,
+                                                          const std::string& sub_materialized_path);
   virtual void begin_batch() {}
   virtual void end_batch() {}
   // A job about to identify `orphans` rows may let the database keep what
@@ -376,6 +404,7 @@ class MemoryLibrary : public Library {
   void connect(int32_t file_path_id, int32_t object_id) override;
   std::vector<FilePathRow> file_paths_without_checksum(int32_t location_id, const std::string& sub) override;
   std::vector<FilePathRow> file_paths_with_checksum(int32_t location_id, const std::string& sub) override;
+  std::vector<FilePathRow> file_paths_in_location(int32_t location_id, const std::string& sub) override;
   void set_integrity_checksum(int32_t file_path_id, const std::string& checksum) override;
 
  private:
@@ -433,6 +462,7 @@ class SqliteLibrary : public Library {
   void connect(int32_t file_path_id, int32_t object_id) override;
   std::vector<FilePathRow> file_paths_without_checksum(int32_t location_id, const std::string& sub) override;
   std::vector<FilePathRow> file_paths_with_checksum(int32_t location_id, const std::string& sub) override;
+  std::vector<FilePathRow> file_paths_in_location(int32_t location_id, const std::string& sub) override;
   void set_integrity_checksum(int32_t file_path_id, const std::string& checksum) override;
   void begin_batch() override;
   void end_batch() override;
@@ -680,5 +710,53 @@ ReclaimReport reclaim_report_from(const std::vector<FilePathRow>& rows, const st
 // into sets with the rows' size_in_bytes, the most reclaimable bytes first
 // (Engine::duplicate_sets, SDCAS_SETS_BY_RECLAIMABLE). Writes nothing.
 ReclaimReport reclaim_report(Engine& engine, Library& db, int32_t location_id, const std::string& sub = "");
+
+// ---- duplicate directories: the top-most duplicate sets of a location ---------------
+// The tree of a location's rows, no GPU: parent[i] is the index of the
+// directory row whose own path (materialized_path + name + "/") is row i's
+// materialized_path, or -1 when that row is absent (the location's root, or
+// the directory a `sub` scope starts at); of several directory rows with one
+// path the first counts.
+struct TreeShape {
+  std::vector<int64_t> parent;
+  std::vector<uint8_t> is_dir;
+};
+TreeShape tree_shape_from(const std::vector<FilePathRow>& rows);
+// the name a row stands under in its directory: a directory's name, a file's
+// name with "." and its extension when it has one
+std::string entry_name(const FilePathRow& row);
+
+struct TreeReport {
+  struct Set {
+    std::vector<int32_t> file_path_ids;  // ascending
+    bool is_dir = false;                 // the kind of the set's first row
+    uint64_t tree_bytes = 0;             // one copy: a file's size, or all file bytes below a directory
+    uint64_t tree_files = 0;             // 1, or the files below a directory
+    uint64_t reclaimable_bytes = 0;      // (rows - 1) * tree_bytes, modulo 2^64
+    bool operator==(const Set& o) const {
+      return file_path_ids == o.file_path_ids && is_dir == o.is_dir && tree_bytes == o.tree_bytes &&
+             tree_files == o.tree_files && reclaimable_bytes == o.reclaimable_bytes;
+    }
+  };
+  std::vector<Set> sets;  // in the order of the arrays they were shaped from
+  sdcas_tree_counts tree{};
+  sdcas_top_counts top{};
+  sdcas_sets_counts counts{};
+};
+// The report's shaping, no GPU: rows and, with row i as entry i, the per-entry
+// rollups (Engine::TreeDigests) and the sets of Engine::duplicate_sets over
+// top_rep and tree_bytes. Throws std::invalid_argument when the arrays do not
+// fit the rows or each other.
+TreeReport tree_report_from(const std::vector<FilePathRow>& rows, const std::vector<uint64_t>& tree_bytes,
+                            const std::vector<uint64_t>& tree_files, const std::vector<int64_t>& set_rep,
+                            const std::vector<uint64_t>& set_offsets, const std::vector<uint64_t>& set_bytes,
+                            const std::vector<int64_t>& members, const sdcas_sets_counts& counts);
+// Read-only: reads Library::file_paths_in_location (files and directories),
+// hashes the names, gives every directory its digest (a file without a
+// 64-hex integrity_checksum is invalid and makes its ancestors INCOMPLETE; a
+// file's key is its checksum's first 8 bytes), confirms all entries at once,
+// keeps the top-most duplicates and lists them, directories and files mixed,
+// the most reclaimable first. Writes nothing.
+TreeReport tree_report(Engine& engine, Library& db, int32_t location_id, const std::string& sub = "");
 
 }  // namespace sdcore

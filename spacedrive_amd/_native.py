@@ -38,6 +38,12 @@ SDCAS_CONFIRM_COLLISION = 2
 SDCAS_CONFIRM_SKIPPED = 4
 SDCAS_SETS_BY_REP = 0
 SDCAS_SETS_BY_RECLAIMABLE = 1
+SDCAS_TREE_MAX_DEPTH = 4096
+SDCAS_TREE_DIR = 1
+SDCAS_TREE_INCOMPLETE = 2
+SDCAS_TREE_EMPTY = 4
+SDCAS_TOP_DUP = 1
+SDCAS_TOP_NESTED = 2
 
 # every entry point include/sdcas.h and include/sdcas_bench.h declare
 ABI_SYMBOLS = [
@@ -47,6 +53,8 @@ ABI_SYMBOLS = [
     "sdcas_dev_hash_messages", "sdcas_dev_sync", "sdcas_dev_bind_stream", "sdcas_dedup", "sdcas_dedup_window", "sdcas_job_plan",
     "sdcas_confirm_duplicates", "sdcas_dev_confirm_duplicates",  # added after ABI 7
     "sdcas_duplicate_sets", "sdcas_dev_duplicate_sets",  # added after ABI 7
+    "sdcas_tree_plan", "sdcas_tree_digests", "sdcas_dev_tree_digests", "sdcas_tree_top",
+    "sdcas_dev_tree_top",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -119,6 +127,25 @@ class SetsCounts(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class TreeCounts(ctypes.Structure):
+    """sdcas_tree_counts"""
+    _fields_ = [("entries", ctypes.c_uint64), ("dirs", ctypes.c_uint64), ("complete_dirs", ctypes.c_uint64),
+                ("empty_dirs", ctypes.c_uint64), ("levels", ctypes.c_uint64), ("largest_dir", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class TopCounts(ctypes.Structure):
+    """sdcas_top_counts"""
+    _fields_ = [("entries", ctypes.c_uint64), ("dup_entries", ctypes.c_uint64), ("nested_entries", ctypes.c_uint64),
+                ("top_entries", ctypes.c_uint64), ("kept_classes", ctypes.c_uint64),
+                ("dropped_classes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _lib_path = LIB_PATH
 
@@ -182,6 +209,12 @@ def load():
     L.sdcas_duplicate_sets.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_uint32, _vp, _vp, _vp, _vp,
                                        ctypes.POINTER(SetsCounts)]
     L.sdcas_dev_duplicate_sets.argtypes = [_vp, _vp, _vp, _sz, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.sdcas_tree_plan.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp]
+    L.sdcas_tree_digests.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     ctypes.POINTER(TreeCounts)]
+    L.sdcas_dev_tree_digests.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.sdcas_tree_top.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, ctypes.POINTER(TopCounts)]
+    L.sdcas_dev_tree_top.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

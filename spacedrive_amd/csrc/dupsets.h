@@ -66,4 +66,22 @@ hipError_t duplicate_sets(uint32_t* ws, const int64_t* rep, const uint64_t* size
                           int64_t* set_rep, uint64_t* set_offsets, uint64_t* set_bytes, int64_t* members,
                           unsigned long long* counts, hipStream_t st);
 
+// ---- the passes dirtree.hip shares -----------------------------------------------
+// The stable LSD radix sort (k_ds_hist / k_ds_scatter and the scan between
+// them): the first *m_p of at most `bound` (key, value) pairs by the keys' low
+// 8 * passes bits; the result is in (ka, va) after an even number of passes,
+// else in (kb, vb). hist: 256 words per tile of `bound`; bsum:
+// dupsets_tiles(256 * dupsets_tiles(bound)) + 2 words; scan_total: one word.
+hipError_t dupsets_sort_u64(uint64_t* ka, uint64_t* kb, uint32_t* va, uint32_t* vb, uint32_t bound,
+                            const uint32_t* m_p, uint32_t passes, uint32_t* hist, uint32_t* bsum,
+                            uint32_t* scan_total, hipStream_t st);
+hipError_t dupsets_sort_u32(uint32_t* ka, uint32_t* kb, uint32_t* va, uint32_t* vb, uint32_t bound,
+                            const uint32_t* m_p, uint32_t passes, uint32_t* hist, uint32_t* bsum,
+                            uint32_t* scan_total, hipStream_t st);
+// k_ds_count: cnt[label] += the entries that carry it, low[label] = the lowest
+// of them (cnt zeroed and low filled with 0xFF by the caller), counts[0] += the
+// entries whose label lies in [0, n)
+hipError_t dupsets_label_counts(const int64_t* rep, uint32_t n, uint32_t* cnt, uint32_t* low,
+                                unsigned long long* counts, hipStream_t st);
+
 }  // namespace sdcas

@@ -583,4 +583,21 @@ hipError_t duplicate_sets(uint32_t* ws, const int64_t* rep, const uint64_t* size
   return hipSuccess;
 }
 
+// what dirtree.hip shares (dupsets.h)
+hipError_t dupsets_sort_u64(uint64_t* ka, uint64_t* kb, uint32_t* va, uint32_t* vb, uint32_t bound,
+                            const uint32_t* m_p, uint32_t passes, uint32_t* hist, uint32_t* bsum,
+                            uint32_t* scan_total, hipStream_t st) {
+  return ds_sort<uint64_t>(ka, kb, va, vb, bound, m_p, passes, hist, bsum, scan_total, st);
+}
+hipError_t dupsets_sort_u32(uint32_t* ka, uint32_t* kb, uint32_t* va, uint32_t* vb, uint32_t bound,
+                            const uint32_t* m_p, uint32_t passes, uint32_t* hist, uint32_t* bsum,
+                            uint32_t* scan_total, hipStream_t st) {
+  return ds_sort<uint32_t>(ka, kb, va, vb, bound, m_p, passes, hist, bsum, scan_total, st);
+}
+hipError_t dupsets_label_counts(const int64_t* rep, uint32_t n, uint32_t* cnt, uint32_t* low,
+                                unsigned long long* counts, hipStream_t st) {
+  hipLaunchKernelGGL(k_ds_count, dim3(dupsets_tiles(n)), dim3(kDsTB), 0, st, rep, n, cnt, low, counts);
+  return hipGetLastError();
+}
+
 }  // namespace sdcas

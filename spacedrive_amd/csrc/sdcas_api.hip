@@ -32,6 +32,7 @@
 #include "b3_batch.h"
 #include "confirm.h"
 #include "dupsets.h"
+#include "dirtree.h"
 #include "dist_dedup.h"
 #include "synth.h"
 
@@ -114,10 +115,10 @@ struct HostStage {
   hipEvent_t ev[kN] = {};
   bool recorded[kN] = {};
   int next = 0;
-  hipError_t put(const void* src, size_t bytes, void* d_dst, hipStream_t st) {
-    if (!bytes) return hipSuccess;
+  // the next buffer, free and of at least `bytes` bytes, for a caller that
+  // builds its array in place; send() uploads it
+  hipError_t reserve(size_t bytes, uint8_t** out) {
     const int i = next;
-    next = (next + 1) % kN;
     hipError_t e;
     if (recorded[i] && (e = hipEventSynchronize(ev[i]))) return e;
     recorded[i] = false;
@@ -130,11 +131,25 @@ struct HostStage {
       cap[i] = want;
     }
     if (!ev[i] && (e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming))) return e;
-    memcpy(h[i], src, bytes);
+    *out = h[i];
+    return hipSuccess;
+  }
+  // the reserved buffer's first `bytes` bytes to d_dst in stream order
+  hipError_t send(size_t bytes, void* d_dst, hipStream_t st) {
+    const int i = next;
+    next = (next + 1) % kN;
+    hipError_t e;
     if ((e = hipMemcpyAsync(d_dst, h[i], bytes, hipMemcpyHostToDevice, st))) return e;
     if ((e = hipEventRecord(ev[i], st))) return e;
     recorded[i] = true;
     return hipSuccess;
+  }
+  hipError_t put(const void* src, size_t bytes, void* d_dst, hipStream_t st) {
+    if (!bytes) return hipSuccess;
+    uint8_t* buf = nullptr;
+    if (hipError_t e = reserve(bytes, &buf)) return e;
+    memcpy(buf, src, bytes);
+    return send(bytes, d_dst, st);
   }
   void release() {
     for (int i = 0; i < kN; ++i) {
@@ -196,6 +211,13 @@ struct sdcas_ctx {
   DevBuf<int64_t> ds_in;   // rep | sizes
   DevBuf<int64_t> ds_out;  // set_rep | set_offsets | set_bytes | members
   DevBuf<unsigned long long> ds_counts;
+
+  // directory digests and top-most duplicates (dirtree.hip): the workspaces,
+  // the shape's upload, and the host calls' device copies of their arrays
+  DevBuf<uint8_t> tr_ws, tr_io;
+  HostStage tr_stage;
+  DevBuf<uint32_t> tt_ws;
+  DevBuf<int64_t> tt_io;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -823,6 +845,11 @@ void sdcas_destroy(sdcas_ctx* c) {
   c->ds_ws.release();
   for (auto* b : {&c->ds_in, &c->ds_out}) b->release();
   c->ds_counts.release();
+  c->tr_ws.release();
+  c->tr_io.release();
+  c->tr_stage.release();
+  c->tt_ws.release();
+  c->tt_io.release();
   c->dist.release();
   c->sm_d_files.release();
   c->sm_nodes.release();
@@ -2082,6 +2109,221 @@ int sdcas_duplicate_sets(sdcas_ctx* c, const int64_t* rep, const uint64_t* sizes
     return c->hip_fail(e, "duplicate sets D2H");
   if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "duplicate sets sync");
   if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+// ---- directory digests and top-most duplicates (dirtree.hip) ---------------------
+
+int sdcas_tree_plan(const int64_t* parent, const uint8_t* is_dir, size_t n, uint32_t* out_depth,
+                    uint64_t* out_children, uint64_t* out_levels) {
+  static_assert(SDCAS_TREE_MAX_DEPTH == kTreeMaxDepth, "depth limit");
+  TreeShape s;
+  const TreeShapeError err = tree_shape(parent, is_dir, n, false, s, nullptr);
+  if (err) return err == kTreeCapacity ? SDCAS_E_CAPACITY : SDCAS_E_INVALID;
+  if (out_depth && n) memcpy(out_depth, s.depth.data(), n * sizeof(uint32_t));
+  if (out_children && n) memcpy(out_children, s.children.data(), n * sizeof(uint64_t));
+  if (out_levels) *out_levels = s.levels;
+  return SDCAS_OK;
+}
+
+static int tree_shape_checked(sdcas_ctx* c, const char* who, const int64_t* parent, const uint8_t* is_dir, size_t n,
+                              TreeShape& s) {
+  const char* why = "";
+  const TreeShapeError err = tree_shape(parent, is_dir, n, true, s, &why);
+  if (err) return c->fail(err == kTreeCapacity ? SDCAS_E_CAPACITY : SDCAS_E_INVALID, "%s: %s", who, why);
+  return SDCAS_OK;
+}
+
+// Enqueue the whole of tree_digests on st (device arrays, a checked shape, n != 0).
+static int tree_enqueue(sdcas_ctx* c, const char* who, const TreeShape& s, const uint8_t* is_dir, TreeArgs a,
+                        uint64_t* d_counts, hipStream_t st) {
+  static_assert(SDCAS_TREE_DIR == kTreeDir && SDCAS_TREE_INCOMPLETE == kTreeIncomplete &&
+                    SDCAS_TREE_EMPTY == kTreeEmpty && SDCAS_TOP_DUP == kTopDup && SDCAS_TOP_NESTED == kTopNested,
+                "flags");
+  const TreeLayout l = tree_layout(s.n, s.dirs, s.max_level_dirs, s.max_level_bytes);
+  hipError_t e;
+  // an earlier call's kernels may still use what is about to be freed
+  const bool grow_ws = l.bytes > c->tr_ws.cap;
+  const bool grow_batch =
+      s.dirs && (!c->ws.S || s.max_level_dirs > c->ws.cap_msgs || s.max_level_chunks > c->ws.cap_chunks);
+  if (grow_ws || grow_batch) {
+    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st))) return c->hip_fail(e, "tree workspace");
+    if (grow_ws && (e = c->tr_ws.ensure(l.bytes))) return c->hip_fail(e, "tree workspace");
+    if (grow_batch)
+      if (int rc = reserve_ws(c, std::max<size_t>(s.max_level_dirs, c->ws.cap_msgs),
+                              std::max<uint64_t>(s.max_level_chunks, c->ws.cap_chunks)))
+        return rc;
+  }
+  a.ws = c->tr_ws.p;
+  {
+    // the shape's arrays are laid out in the pinned buffer itself
+    uint8_t* meta = nullptr;
+    if ((e = c->tr_stage.reserve(l.meta_bytes, &meta))) return c->hip_fail(e, "tree shape upload");
+    tree_meta_fill(s, is_dir, l, meta);
+    if ((e = c->tr_stage.send(l.meta_bytes, a.ws, st))) return c->hip_fail(e, "tree shape upload");
+  }
+  if ((e = tree_begin(s, l, a, st))) return c->hip_fail(e, who);
+  for (uint32_t depth = s.dir_levels; depth-- > 0;) {
+    const uint32_t nd = s.level_first[depth + 1] - s.level_first[depth];
+    if (!nd) continue;
+    if ((e = tree_level_gather(s, l, a, depth, st))) return c->hip_fail(e, who);
+    if (int rc = launch_batch(c, a.ws + l.blob, reinterpret_cast<const uint64_t*>(a.ws + l.offs),
+                              reinterpret_cast<const uint64_t*>(a.ws + l.lens), nd, a.ws + l.tdig, nullptr, st,
+                              s.level_chunks[depth]))
+      return rc;
+    if ((e = tree_level_finish(s, l, a, depth, st))) return c->hip_fail(e, who);
+  }
+  if (d_counts && (e = hipMemcpyAsync(d_counts, a.ws + l.counts, kTreeCounts * sizeof(uint64_t),
+                                      hipMemcpyDeviceToDevice, st)))
+    return c->hip_fail(e, who);
+  return SDCAS_OK;
+}
+
+int sdcas_dev_tree_digests(sdcas_ctx* c, const int64_t* parent, const uint8_t* is_dir, const uint8_t* d_name32,
+                           const uint64_t* d_sizes, size_t n, uint64_t* d_keys, uint8_t* d_digests32,
+                           uint8_t* d_valid, uint64_t* d_out_tree_bytes, uint64_t* d_out_tree_files,
+                           uint8_t* d_out_flags, uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  TreeShape s;
+  if (int rc = tree_shape_checked(c, "dev_tree_digests", parent, is_dir, n, s)) return rc;
+  if (n && (!d_name32 || !d_digests32)) return c->fail(SDCAS_E_INVALID, "dev_tree_digests: null name32 or digests32");
+  if (((uintptr_t)d_name32 | (uintptr_t)d_digests32) & 15)
+    return c->fail(SDCAS_E_INVALID, "dev_tree_digests: name32 or digests32 not 16-byte aligned");
+  if (((uintptr_t)d_sizes | (uintptr_t)d_keys | (uintptr_t)d_out_tree_bytes | (uintptr_t)d_out_tree_files |
+       (uintptr_t)d_counts) & 7)
+    return c->fail(SDCAS_E_INVALID, "dev_tree_digests: an array is not 8-byte aligned");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (n == 0) {
+    hipError_t e;
+    if (d_counts && (e = hipMemsetAsync(d_counts, 0, kTreeCounts * sizeof(uint64_t), call.st)))
+      return c->hip_fail(e, "counts");
+    return SDCAS_OK;
+  }
+  return tree_enqueue(c, "dev_tree_digests", s, is_dir,
+                      TreeArgs{nullptr, d_name32, d_sizes, d_keys, d_digests32, d_valid, d_out_tree_bytes,
+                               d_out_tree_files, d_out_flags},
+                      d_counts, call.st);
+}
+
+int sdcas_tree_digests(sdcas_ctx* c, const int64_t* parent, const uint8_t* is_dir, const uint8_t* name32,
+                       const uint64_t* sizes, size_t n, uint64_t* keys, uint8_t* digests32, uint8_t* valid,
+                       uint64_t* out_tree_bytes, uint64_t* out_tree_files, uint8_t* out_flags,
+                       sdcas_tree_counts* out_counts) {
+  static_assert(sizeof(sdcas_tree_counts) == kTreeCounts * sizeof(uint64_t), "six u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  TreeShape s;
+  if (int rc = tree_shape_checked(c, "tree_digests", parent, is_dir, n, s)) return rc;
+  if (n && (!name32 || !digests32)) return c->fail(SDCAS_E_INVALID, "tree_digests: null name32 or digests32");
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  if (n == 0) return SDCAS_OK;
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = call.st;
+  // name32 | digests32 | sizes | keys | tree_bytes | tree_files | counts | valid | flags
+  const size_t o_dig = 32 * n, o_sizes = 64 * n, o_keys = 72 * n, o_tb = 80 * n, o_tf = 88 * n, o_cts = 96 * n,
+               o_valid = o_cts + 64, o_flags = o_valid + n;
+  if (o_flags + n > c->tr_io.cap) {
+    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->tr_io.ensure(o_flags + n)))
+      return c->hip_fail(e, "tree_digests buffers");
+  }
+  uint8_t* io = c->tr_io.p;
+  if ((e = hipMemcpyAsync(io, name32, 32 * n, hipMemcpyHostToDevice, st)) ||
+      (e = hipMemcpyAsync(io + o_dig, digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
+      (sizes && (e = hipMemcpyAsync(io + o_sizes, sizes, 8 * n, hipMemcpyHostToDevice, st))) ||
+      (keys && (e = hipMemcpyAsync(io + o_keys, keys, 8 * n, hipMemcpyHostToDevice, st))) ||
+      (valid && (e = hipMemcpyAsync(io + o_valid, valid, n, hipMemcpyHostToDevice, st))))
+    return c->hip_fail(e, "tree_digests H2D");
+  TreeArgs a{nullptr,
+             io,
+             sizes ? reinterpret_cast<const uint64_t*>(io + o_sizes) : nullptr,
+             keys ? reinterpret_cast<uint64_t*>(io + o_keys) : nullptr,
+             io + o_dig,
+             valid ? io + o_valid : nullptr,
+             out_tree_bytes ? reinterpret_cast<uint64_t*>(io + o_tb) : nullptr,
+             out_tree_files ? reinterpret_cast<uint64_t*>(io + o_tf) : nullptr,
+             out_flags ? io + o_flags : nullptr};
+  if (int rc = tree_enqueue(c, "tree_digests", s, is_dir, a, reinterpret_cast<uint64_t*>(io + o_cts), st)) return rc;
+  // (the file entries' slots come back as they went up)
+  if ((e = hipMemcpyAsync(digests32, io + o_dig, 32 * n, hipMemcpyDeviceToHost, st)) ||
+      (keys && (e = hipMemcpyAsync(keys, io + o_keys, 8 * n, hipMemcpyDeviceToHost, st))) ||
+      (valid && (e = hipMemcpyAsync(valid, io + o_valid, n, hipMemcpyDeviceToHost, st))) ||
+      (out_tree_bytes && (e = hipMemcpyAsync(out_tree_bytes, io + o_tb, 8 * n, hipMemcpyDeviceToHost, st))) ||
+      (out_tree_files && (e = hipMemcpyAsync(out_tree_files, io + o_tf, 8 * n, hipMemcpyDeviceToHost, st))) ||
+      (out_flags && (e = hipMemcpyAsync(out_flags, io + o_flags, n, hipMemcpyDeviceToHost, st))) ||
+      (out_counts && (e = hipMemcpyAsync(out_counts, io + o_cts, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
+    return c->hip_fail(e, "tree_digests D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "tree_digests sync");
+  return SDCAS_OK;
+}
+
+// the workspace grown to n entries; the stream waits first, as an earlier
+// call's kernels may still use the workspace about to be freed
+static int tree_top_ws(sdcas_ctx* c, size_t n, hipStream_t st) {
+  const size_t need = (size_t)tree_top_ws_words(n);
+  if (need <= c->tt_ws.cap) return SDCAS_OK;
+  hipError_t e = c->scratch_sync();
+  if (!e) e = hipStreamSynchronize(st);
+  if (!e) e = c->tt_ws.ensure(need);
+  return e ? c->hip_fail(e, "tree_top workspace") : SDCAS_OK;
+}
+
+int sdcas_dev_tree_top(sdcas_ctx* c, const int64_t* d_parent, const int64_t* d_rep, size_t n, int64_t* d_out_top_rep,
+                       uint8_t* d_out_flags, uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (n > kTreeMaxEntries) return c->fail(SDCAS_E_CAPACITY, "dev_tree_top of %zu entries exceeds 2^30", n);
+  if (n && (!d_parent || !d_rep)) return c->fail(SDCAS_E_INVALID, "dev_tree_top: null parent or rep");
+  if (((uintptr_t)d_parent | (uintptr_t)d_rep | (uintptr_t)d_out_top_rep | (uintptr_t)d_counts) & 7)
+    return c->fail(SDCAS_E_INVALID, "dev_tree_top: an array is not 8-byte aligned");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  if (n == 0) {
+    if (d_counts && (e = hipMemsetAsync(d_counts, 0, kTreeCounts * sizeof(uint64_t), call.st)))
+      return c->hip_fail(e, "counts");
+    return SDCAS_OK;
+  }
+  if (int rc = tree_top_ws(c, n, call.st)) return rc;
+  e = tree_top(c->tt_ws.p, d_parent, d_rep, (uint32_t)n, d_out_top_rep, d_out_flags, (unsigned long long*)d_counts,
+               call.st);
+  return e ? c->hip_fail(e, "dev_tree_top") : SDCAS_OK;
+}
+
+int sdcas_tree_top(sdcas_ctx* c, const int64_t* parent, const int64_t* rep, size_t n, int64_t* out_top_rep,
+                   uint8_t* out_flags, sdcas_top_counts* out_counts) {
+  static_assert(sizeof(sdcas_top_counts) == kTreeCounts * sizeof(uint64_t), "six u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  if (n > kTreeMaxEntries) return c->fail(SDCAS_E_CAPACITY, "tree_top of %zu entries exceeds 2^30", n);
+  if (n && (!parent || !rep)) return c->fail(SDCAS_E_INVALID, "tree_top: null parent or rep");
+  for (size_t i = 0; i < n; ++i)
+    if (parent[i] < -1 || parent[i] >= (int64_t)n) return c->fail(SDCAS_E_INVALID, "tree_top: a parent outside [-1, n)");
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  if (n == 0) return SDCAS_OK;
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = call.st;
+  // parent | rep | top_rep | counts (8 words) | flags
+  const size_t words = 3 * n + 8 + (n + 7) / 8;
+  if (words > c->tt_io.cap) {
+    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->tt_io.ensure(words)))
+      return c->hip_fail(e, "tree_top buffers");
+  }
+  if (int rc = tree_top_ws(c, n, st)) return rc;
+  int64_t* io = c->tt_io.p;
+  uint8_t* d_flags = reinterpret_cast<uint8_t*>(io + 3 * n + 8);
+  if ((e = hipMemcpyAsync(io, parent, 8 * n, hipMemcpyHostToDevice, st)) ||
+      (e = hipMemcpyAsync(io + n, rep, 8 * n, hipMemcpyHostToDevice, st)))
+    return c->hip_fail(e, "tree_top H2D");
+  if ((e = tree_top(c->tt_ws.p, io, io + n, (uint32_t)n, out_top_rep ? io + 2 * n : nullptr,
+                    out_flags ? d_flags : nullptr, reinterpret_cast<unsigned long long*>(io + 3 * n), st)))
+    return c->hip_fail(e, "tree_top");
+  if ((out_top_rep && (e = hipMemcpyAsync(out_top_rep, io + 2 * n, 8 * n, hipMemcpyDeviceToHost, st))) ||
+      (out_flags && (e = hipMemcpyAsync(out_flags, d_flags, n, hipMemcpyDeviceToHost, st))) ||
+      (out_counts && (e = hipMemcpyAsync(out_counts, io + 3 * n, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
+    return c->hip_fail(e, "tree_top D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "tree_top sync");
   return SDCAS_OK;
 }
 

@@ -347,7 +347,158 @@ class Engine:
         ident, confirm = self.identify_confirmed(paths, size_hints)
         return ident, confirm, self.duplicate_sets(confirm[0], ident[0], order)
 
+    # -- duplicate directories ---------------------------------------------------------
+    @staticmethod
+    def tree_plan(parent, is_dir):
+        """sdcas_tree_plan (no GPU): checks the shape (SdcasError with
+        SDCAS_E_INVALID / SDCAS_E_CAPACITY) -> (depth uint32[n], children
+        uint64[n], levels)"""
+        parent, is_dir = _arr(parent, np.int64), _arr(is_dir, np.uint8)
+        n = parent.size
+        if is_dir.size != n:
+            raise ValueError(f"tree_plan: {n} parents, {is_dir.size} is_dir flags")
+        depth = np.zeros(n, np.uint32)
+        children = np.zeros(n, np.uint64)
+        levels = ctypes.c_uint64(0)
+        rc = N.load().sdcas_tree_plan(_ptr(parent), _ptr(is_dir), n, _ptr(depth), _ptr(children),
+                                      ctypes.byref(levels))
+        if rc != N.SDCAS_OK:
+            raise N.SdcasError(rc, "sdcas_tree_plan: the shape is refused")
+        return depth, children, int(levels.value)
+
+    def tree_digests(self, parent, is_dir, name32, digests, valid=None, sizes=None, keys=None):
+        """a digest per directory (sdcas_tree_digests; the definitions are in
+        include/sdcas.h). digests / valid / keys hold the FILE entries' values;
+        copies of them come back with the directory entries' slots filled ->
+        (keys uint64[n], digests uint8[n, 32], valid uint8[n] or None when none
+        was given, tree_bytes uint64[n], tree_files uint64[n], flags uint8[n]:
+        SDCAS_TREE_DIR | SDCAS_TREE_INCOMPLETE | SDCAS_TREE_EMPTY, counts: dict
+        of sdcas_tree_counts' six fields)"""
+        parent, is_dir = _arr(parent, np.int64), _arr(is_dir, np.uint8)
+        n = parent.size
+        name32 = _arr(name32, np.uint8)
+        digests = np.array(digests, dtype=np.uint8, order="C").reshape(n, 32)
+        va = None if valid is None else np.array(valid, dtype=np.uint8, order="C")
+        sz = None if sizes is None else _arr(sizes, np.uint64)
+        ks = np.zeros(n, np.uint64) if keys is None else np.array(keys, dtype=np.uint64, order="C")
+        for nm, a, want in (("is_dir", is_dir, n), ("name32", name32, 32 * n), ("valid", va, n), ("sizes", sz, n),
+                            ("keys", ks, n)):
+            if a is not None and a.size != want:
+                raise ValueError(f"tree_digests: {n} entries, {a.size} bytes or entries of {nm}")
+        tree_bytes = np.zeros(n, np.uint64)
+        tree_files = np.zeros(n, np.uint64)
+        flags = np.zeros(n, np.uint8)
+        counts = N.TreeCounts()
+        self._check(self.L.sdcas_tree_digests(self.ctx, _ptr(parent), _ptr(is_dir), _ptr(name32),
+                                              None if sz is None else _ptr(sz), n, _ptr(ks), _ptr(digests),
+                                              None if va is None else _ptr(va), _ptr(tree_bytes), _ptr(tree_files),
+                                              _ptr(flags), ctypes.byref(counts)), "sdcas_tree_digests")
+        return ks, digests, va, tree_bytes, tree_files, flags, counts.as_dict()
+
+    def tree_top(self, parent, rep):
+        """the top-most duplicates (sdcas_tree_top): rep is a label per entry,
+        e.g. confirm_duplicates' rep over ALL entries -> (top_rep int64[n]:
+        rep[i] when i's class is kept, else -1, flags uint8[n]: SDCAS_TOP_DUP |
+        SDCAS_TOP_NESTED, counts: dict of sdcas_top_counts' six fields)"""
+        parent, rep = _arr(parent, np.int64), _arr(rep, np.int64)
+        n = parent.size
+        if rep.size != n:
+            raise ValueError(f"tree_top: {n} parents, {rep.size} reps")
+        top = np.zeros(n, np.int64)
+        flags = np.zeros(n, np.uint8)
+        counts = N.TopCounts()
+        self._check(self.L.sdcas_tree_top(self.ctx, _ptr(parent), _ptr(rep), n, _ptr(top), _ptr(flags),
+                                          ctypes.byref(counts)), "sdcas_tree_top")
+        return top, flags, counts.as_dict()
+
+    @staticmethod
+    def walk_tree(root):
+        """the entries below root (root itself is none), a directory's entries
+        in name order, symlinks skipped and not followed -> (relative paths,
+        is_dir uint8[n], parent int64[n]: -1 directly under root)"""
+        rel, kinds, parents = [], [], []
+        stack = [(os.fspath(root), "", -1)]
+        while stack:
+            path, prefix, at = stack.pop()
+            with os.scandir(path) as it:
+                found = sorted(it, key=lambda e: os.fsencode(e.name))
+            for e in found:
+                if e.is_symlink():
+                    continue
+                d = e.is_dir(follow_symlinks=False)
+                if not d and not e.is_file(follow_symlinks=False):
+                    continue
+                rel.append(prefix + e.name)
+                kinds.append(1 if d else 0)
+                parents.append(at)
+                if d:
+                    stack.append((e.path, prefix + e.name + os.sep, len(rel) - 1))
+        return rel, np.array(kinds, np.uint8), np.array(parents, np.int64)
+
+    def identify_duplicate_trees(self, root, order=N.SDCAS_SETS_BY_RECLAIMABLE):
+        """scan a directory and list its top-most duplicates, directories and
+        files mixed, the biggest win first: walk_tree, identify_checksums over
+        the files, the names hashed by hash_messages, tree_digests, the file
+        entries keyed by their digests' first 8 bytes (one key rule for both
+        kinds), ONE confirm_duplicates over all entries, tree_top, then
+        duplicate_sets over top_rep and tree_bytes -> dict with "entries"
+        (relative path, is_dir), the per-entry arrays "parent", "is_dir",
+        "sizes", "status", "keys", "digests", "valid", "tree_bytes",
+        "tree_files", "tree_flags", "rep", "top_rep", "top_flags", the sets
+        "set_rep", "set_offsets", "set_bytes", "members" (duplicate_sets'
+        layout) and "tree_counts", "top_counts", "sets_counts"."""
+        root = os.fspath(root)
+        rel, is_dir, parent = self.walk_tree(root)
+        n = len(rel)
+        files = np.flatnonzero(is_dir == 0)
+        sizes = np.zeros(n, np.uint64)
+        status = np.zeros(n, np.int32)
+        digests = np.zeros((n, 32), np.uint8)
+        valid = np.zeros(n, np.uint8)
+        if files.size:
+            fs, _, fd, fst, ffl = self.identify_checksums([os.path.join(root, rel[i]) for i in files])
+            sizes[files], status[files], digests[files] = fs, fst, fd
+            valid[files] = ((ffl & N.SDCAS_META_HAS_CHECKSUM) != 0) & (fst == 0)
+        names = [os.fsencode(os.path.basename(r)) for r in rel]
+        name32 = self.hash_messages(*self.pack(names)) if n else np.zeros((0, 32), np.uint8)
+        keys = np.zeros(n, np.uint64)
+        keys[files] = digests[files, :8].copy().view(">u8").reshape(-1).astype(np.uint64)
+        keys, digests, valid, tree_bytes, tree_files, tflags, tcounts = self.tree_digests(
+            parent, is_dir, name32, digests, valid, sizes, keys)
+        rep, _, _, _ = self.confirm_duplicates(keys, digests, valid)
+        top_rep, top_flags, top_counts = self.tree_top(parent, rep)
+        set_rep, set_offsets, set_bytes, members, scounts = self.duplicate_sets(top_rep, tree_bytes, order)
+        return {"entries": list(zip(rel, (bool(d) for d in is_dir))), "parent": parent, "is_dir": is_dir,
+                "sizes": sizes, "status": status, "name32": name32, "keys": keys, "digests": digests, "valid": valid,
+                "tree_bytes": tree_bytes, "tree_files": tree_files, "tree_flags": tflags, "rep": rep,
+                "top_rep": top_rep, "top_flags": top_flags, "set_rep": set_rep, "set_offsets": set_offsets,
+                "set_bytes": set_bytes, "members": members, "tree_counts": tcounts, "top_counts": top_counts,
+                "sets_counts": scounts}
+
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
+    def dev_tree_digests(self, parent, is_dir, name32, sizes, n, keys=0, digests=0, valid=0, tree_bytes=0,
+                         tree_files=0, flags=0, counts=0, stream=0):
+        """tree_digests over device arrays (sdcas_dev_tree_digests): parent
+        (int64) and is_dir (uint8) are HOST numpy arrays, everything else a
+        device address; digests / keys / valid are read for the file entries
+        and written for the directory entries in place; sizes, keys, valid and
+        any output may be 0; counts six uint64"""
+        parent, is_dir = _arr(parent, np.int64), _arr(is_dir, np.uint8)
+        if parent.size != int(n) or is_dir.size != int(n):
+            raise ValueError(f"dev_tree_digests: {n} entries, {parent.size} parents, {is_dir.size} is_dir flags")
+        self._check(self.L.sdcas_dev_tree_digests(self.ctx, _ptr(parent), _ptr(is_dir), name32 or None,
+                                                  sizes or None, int(n), keys or None, digests or None,
+                                                  valid or None, tree_bytes or None, tree_files or None,
+                                                  flags or None, counts or None, stream or None),
+                    "dev_tree_digests")
+
+    def dev_tree_top(self, parent, rep, n, top_rep=0, flags=0, counts=0, stream=0):
+        """tree_top over device arrays (sdcas_dev_tree_top; parent too: a
+        parent outside [-1, n) counts as -1); any output may be 0; counts six
+        uint64; nothing waits for the device"""
+        self._check(self.L.sdcas_dev_tree_top(self.ctx, parent or None, rep or None, int(n), top_rep or None,
+                                              flags or None, counts or None, stream or None), "dev_tree_top")
+
     def dev_reserve(self, max_msgs, max_chunks):
         self._check(self.L.sdcas_dev_reserve(self.ctx, int(max_msgs), int(max_chunks)), "dev_reserve")
 

@@ -1504,4 +1504,146 @@ ReclaimReport reclaim_report(Engine& engine, Library& db, int32_t location_id, c
   return reclaim_report_from(rows, s.set_rep, s.set_offsets, s.set_bytes, s.members, s.counts);
 }
 
+// ---- duplicate directories ---------------------------------------------------------
+
+std::vector<uint8_t> Engine::hash_strings(const std::vector<std::string>& strings) {
+  const size_t n = strings.size();
+  std::vector<uint64_t> offs(n, 0), lens(n, 0);
+  std::string blob;
+  for (size_t i = 0; i < n; ++i) {
+    offs[i] = blob.size();
+    lens[i] = strings[i].size();
+    blob += strings[i];
+  }
+  blob.append(64, '\0');  // never empty, and readable past the last string
+  std::vector<uint8_t> out(32 * n, 0);
+  if (n == 0) return out;
+  const int rc = sdcas_hash_messages(ctx_, reinterpret_cast<const uint8_t*>(blob.data()), offs.data(), lens.data(), n,
+                                     out.data());
+  if (rc != SDCAS_OK) fail(rc, "sdcas_hash_messages");
+  return out;
+}
+
+Engine::TreeDigests Engine::tree_digests(const std::vector<int64_t>& parent, const std::vector<uint8_t>& is_dir,
+                                         const std::vector<uint8_t>& name32, const std::vector<uint64_t>& sizes,
+                                         const std::vector<uint64_t>& keys, const std::vector<uint8_t>& digests,
+                                         const std::vector<uint8_t>& valid) {
+  const size_t n = parent.size();
+  if (is_dir.size() != n || name32.size() != 32 * n || digests.size() != 32 * n || keys.size() != n ||
+      (!sizes.empty() && sizes.size() != n) || (!valid.empty() && valid.size() != n))
+    throw std::invalid_argument("tree_digests: the arrays' lengths differ");
+  TreeDigests r;
+  r.keys = keys, r.digests = digests, r.valid = valid;
+  r.tree_bytes.assign(n, 0);
+  r.tree_files.assign(n, 0);
+  r.flags.assign(n, 0);
+  const int rc = sdcas_tree_digests(ctx_, parent.data(), is_dir.data(), name32.data(),
+                                    sizes.empty() ? nullptr : sizes.data(), n, r.keys.data(), r.digests.data(),
+                                    r.valid.empty() ? nullptr : r.valid.data(), r.tree_bytes.data(),
+                                    r.tree_files.data(), r.flags.data(), &r.counts);
+  if (rc != SDCAS_OK) fail(rc, "sdcas_tree_digests");
+  return r;
+}
+
+Engine::TreeTop Engine::tree_top(const std::vector<int64_t>& parent, const std::vector<int64_t>& rep) {
+  const size_t n = parent.size();
+  if (rep.size() != n) throw std::invalid_argument("tree_top: parent / rep lengths differ");
+  TreeTop r;
+  r.top_rep.assign(n, -1);
+  r.flags.assign(n, 0);
+  const int rc = sdcas_tree_top(ctx_, parent.data(), rep.data(), n, r.top_rep.data(), r.flags.data(), &r.counts);
+  if (rc != SDCAS_OK) fail(rc, "sdcas_tree_top");
+  return r;
+}
+
+std::vector<FilePathRow> Library::file_paths_in_location(int32_t, const std::string&) {
+  throw LibraryError(SDCAS_E_INVALID, "this Library does not implement file_paths_in_location");
+}
+
+std::vector<FilePathRow> MemoryLibrary::file_paths_in_location(int32_t location_id, const std::string& sub) {
+  std::vector<FilePathRow> out;
+  for (const auto& r : file_paths)
+    if (r.location_id == location_id && under(r, sub)) out.push_back(r);
+  return out;
+}
+
+std::string entry_name(const FilePathRow& row) {
+  return row.is_dir || row.extension.empty() ? row.name : row.name + "." + row.extension;
+}
+
+TreeShape tree_shape_from(const std::vector<FilePathRow>& rows) {
+  const size_t n = rows.size();
+  TreeShape t;
+  t.parent.assign(n, -1);
+  t.is_dir.assign(n, 0);
+  std::map<std::string, int64_t> dir_at;  // a directory row's own path -> its index
+  for (size_t i = 0; i < n; ++i) {
+    t.is_dir[i] = rows[i].is_dir ? 1 : 0;
+    if (rows[i].is_dir) dir_at.emplace(rows[i].materialized_path + rows[i].name + "/", (int64_t)i);
+  }
+  for (size_t i = 0; i < n; ++i) {
+    const auto it = dir_at.find(rows[i].materialized_path);
+    if (it != dir_at.end() && it->second != (int64_t)i) t.parent[i] = it->second;
+  }
+  return t;
+}
+
+TreeReport tree_report_from(const std::vector<FilePathRow>& rows, const std::vector<uint64_t>& tree_bytes,
+                            const std::vector<uint64_t>& tree_files, const std::vector<int64_t>& set_rep,
+                            const std::vector<uint64_t>& set_offsets, const std::vector<uint64_t>& set_bytes,
+                            const std::vector<int64_t>& members, const sdcas_sets_counts& counts) {
+  if (tree_bytes.size() != rows.size() || tree_files.size() != rows.size())
+    throw std::invalid_argument("tree_report_from: tree_bytes / tree_files do not fit the rows");
+  // the sets' shape is reclaim_report_from's: the same checks, the same order
+  const ReclaimReport base = reclaim_report_from(rows, set_rep, set_offsets, set_bytes, members, counts);
+  TreeReport out;
+  out.counts = counts;
+  out.sets.resize(base.sets.size());
+  for (size_t s = 0; s < base.sets.size(); ++s) {
+    if (set_rep[s] < 0 || (uint64_t)set_rep[s] >= rows.size())
+      throw std::invalid_argument("tree_report_from: set_rep " + std::to_string(s) + " is no row");
+    const size_t first = (size_t)set_rep[s];
+    TreeReport::Set& set = out.sets[s];
+    set.file_path_ids = base.sets[s].file_path_ids;
+    set.is_dir = rows[first].is_dir;
+    set.tree_bytes = tree_bytes[first];
+    set.tree_files = tree_files[first];
+    if (set.tree_bytes != set_bytes[s])
+      throw std::invalid_argument("tree_report_from: set_bytes " + std::to_string(s) + " is not its first row's tree_bytes");
+    set.reclaimable_bytes = base.sets[s].reclaimable_bytes;
+  }
+  return out;
+}
+
+TreeReport tree_report(Engine& engine, Library& db, int32_t location_id, const std::string& sub) {
+  const std::vector<FilePathRow> rows = db.file_paths_in_location(location_id, sub);
+  const size_t n = rows.size();
+  if (n == 0) return TreeReport{};
+  const TreeShape shape = tree_shape_from(rows);
+  std::vector<std::string> names(n);
+  std::vector<uint64_t> keys(n, 0), sizes(n, 0);
+  std::vector<uint8_t> digests(32 * n, 0), valid(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    names[i] = entry_name(rows[i]);
+    if (rows[i].is_dir) continue;
+    sizes[i] = rows[i].size_in_bytes;
+    if (!rows[i].integrity_checksum || !hex_to_bytes(*rows[i].integrity_checksum, &digests[32 * i], 32)) {
+      std::fill(digests.begin() + 32 * i, digests.begin() + 32 * (i + 1), 0);
+      continue;
+    }
+    for (size_t b = 0; b < 8; ++b) keys[i] = keys[i] << 8 | digests[32 * i + b];  // one key rule for both kinds
+    valid[i] = 1;
+  }
+  const std::vector<uint8_t> name32 = engine.hash_strings(names);
+  const Engine::TreeDigests t = engine.tree_digests(shape.parent, shape.is_dir, name32, sizes, keys, digests, valid);
+  const Engine::Confirm c = engine.confirm_duplicates(t.keys, t.digests, t.valid);
+  const Engine::TreeTop top = engine.tree_top(shape.parent, c.rep);
+  const Engine::Sets s = engine.duplicate_sets(top.top_rep, t.tree_bytes, SDCAS_SETS_BY_RECLAIMABLE);
+  TreeReport out =
+      tree_report_from(rows, t.tree_bytes, t.tree_files, s.set_rep, s.set_offsets, s.set_bytes, s.members, s.counts);
+  out.tree = t.counts;
+  out.top = top.counts;
+  return out;
+}
+
 }  // namespace sdcore

@@ -51,7 +51,7 @@ struct SqliteLibrary::Impl {
   sqlite3* db = nullptr;
   Stmt count_orphans_dir, get_orphans_dir;
   Stmt count_orphans, get_orphans, set_cas, want_clear, want_add, existing, new_object, connect, no_checksum,
-      with_checksum, set_checksum, add_path, get_path, all_objects, first_object, set_cas_connect;
+      with_checksum, in_location, set_checksum, add_path, get_path, all_objects, first_object, set_cas_connect;
   Stmt row_state, set_cas_connect_free, count_cas, load_first;
   static constexpr int kManyObjects = 64;
   Stmt new_objects;  // kManyObjects rows of (id, pub_id, kind, date_created)
@@ -346,6 +346,9 @@ std::unique_ptr<SqliteLibrary> SqliteLibrary::open(const std::string& path, bool
   x.prepare(x.with_checksum,
             "SELECT " SD_COLS " FROM file_path WHERE location_id = ?1 AND is_dir = 0 AND cas_id IS NOT NULL"
             " AND integrity_checksum IS NOT NULL AND substr(materialized_path, 1, length(?2)) = ?2 ORDER BY id");
+  x.prepare(x.in_location,
+            "SELECT " SD_COLS " FROM file_path WHERE location_id = ?1"
+            " AND substr(materialized_path, 1, length(?2)) = ?2 ORDER BY id");
   x.prepare(x.set_checksum, "UPDATE file_path SET integrity_checksum = ?1 WHERE id = ?2");
   x.prepare(x.add_path,
             "INSERT INTO file_path (id, pub_id, location_id, materialized_path, name, extension, is_dir,"
@@ -744,6 +747,12 @@ std::vector<FilePathRow> SqliteLibrary::file_paths_with_checksum(int32_t locatio
   Impl& x = *d_;
   x.bind_scope(x.with_checksum, location_id, sub);
   return x.rows(x.with_checksum);
+}
+
+std::vector<FilePathRow> SqliteLibrary::file_paths_in_location(int32_t location_id, const std::string& sub) {
+  Impl& x = *d_;
+  x.bind_scope(x.in_location, location_id, sub);
+  return x.rows(x.in_location);
 }
 
 void SqliteLibrary::set_integrity_checksum(int32_t id, const std::string& checksum) {
