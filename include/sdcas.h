@@ -596,6 +596,143 @@ int sdcas_tree_top(sdcas_ctx *ctx, const int64_t *parent, const int64_t *rep, si
 int sdcas_dev_tree_top(sdcas_ctx *ctx, const int64_t *d_parent, const int64_t *d_rep, size_t n,
                        int64_t *d_out_top_rep, uint8_t *d_out_flags, uint64_t *d_counts, void *stream);
 
+/* ---- content-defined chunks: files that share most of their bytes ---------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * File contents resident in memory are cut into chunks at places that depend
+ * on the bytes, not on offsets, so that an insertion moves the cuts after it
+ * along with the bytes: equal content after a common cut gives equal chunks.
+ *   gear table   G[b] = (uint32)(sds_mix64(0x3130304344434453 + b) >> 32), b in
+ *                0..255 (include/sdcas_synth.h; the constant is "SDCDC001")
+ *   window hash  h(p) = sum over k in 0..min(31, p) of G[x[p - k]] << k mod 2^32:
+ *                h = (h << 1) + G[x[p]] run from the file's start. It depends
+ *                on at most the 32 bytes ending at p
+ *   parameters   (min_len, avg_bits, max_len), avg = 2^avg_bits, valid when
+ *                6 <= avg_bits <= 24 and 32 <= min_len < avg < max_len <= 2^28
+ *   STRICT(p)    the top avg_bits + 1 bits of h(p) are zero
+ *   LOOSE(p)     the top avg_bits - 1 bits of h(p) are zero
+ *   cuts         of a file of L bytes, from s = 0 while s < L: if L - s <=
+ *                min_len then e = L, else e is the smallest value in
+ *                [s + min_len, min(s + max_len, L)] with (e - s < avg and
+ *                STRICT(e - 1)) or (e - s >= avg and LOOSE(e - 1)), or
+ *                min(s + max_len, L) when there is none; the chunk is [s, e),
+ *                then s = e. An END chunk has e == L; any other is a HASH cut
+ *                when a candidate was found, else a MAX cut
+ * An empty file has no chunk; a file has at most ceil(L / min_len). Chunks
+ * are numbered file by file, in file order. A chunk's digest is BLAKE3 of its
+ * bytes and its key the digest's bytes 0..8 big-endian, the cas keys'
+ * convention, so sdcas_confirm_duplicates(chunk keys, chunk digests) gives
+ * rep[c], the lowest chunk with the same bytes. Results are exact and do not
+ * depend on scheduling. At most 2^30 chunks (by the bound below) and fewer
+ * than 2^32 files per call; the contents are resident as a whole. */
+typedef struct sdcas_chunk_params {
+  uint32_t min_len;
+  uint32_t avg_bits;
+  uint32_t max_len;
+  uint32_t reserved; /* 0 */
+} sdcas_chunk_params;
+#define SDCAS_CHUNK_PARAMS_DEFAULT {2048u, 13u, 65536u, 0u}
+#define SDCAS_CHUNK_MAX_CHUNKS (1ull << 30)
+/* the gear kernel's tile (bytes of one file per workgroup) and strip (bytes
+ * per lane): the sizes at which a test looks for a seam */
+#define SDCAS_CHUNK_GEAR_TILE 32768u
+#define SDCAS_CHUNK_GEAR_STRIP 128u
+typedef struct sdcas_chunk_counts {
+  uint64_t files;
+  uint64_t chunks;
+  uint64_t total_bytes; /* the sum of the lengths */
+  uint64_t hash_cuts;
+  uint64_t max_cuts;
+  uint64_t end_chunks; /* the files that are not empty */
+} sdcas_chunk_counts;
+/* GPU-free, like sdcas_tree_plan: SDCAS_E_INVALID for parameters that are not
+ * valid (params NULL: the default), *out_max_chunks = the sum of
+ * ceil(len / min_len), the entries a caller provides for every per-chunk
+ * array (SDCAS_E_CAPACITY above 2^30), *out_max_slots = the sum of
+ * ceil(len / 1024) + max_chunks, which sizes the workspace (256 B per 1 KiB of
+ * content for the candidate bitmap, 32 B per possible chunk). */
+int sdcas_chunk_plan(const uint64_t *lens, size_t n, const sdcas_chunk_params *params, uint64_t *out_max_chunks,
+                     uint64_t *out_max_slots);
+/* Host arrays: file i is blob[offsets[i] .. offsets[i] + lens[i]), at any
+ * offset. out_file_chunks: n + 1 entries, file i's chunks are
+ * [out_file_chunks[i], out_file_chunks[i + 1]); the per-chunk arrays hold
+ * max_chunks entries (sdcas_chunk_plan) and entries past counts.chunks are
+ * left as they were: out_chunk_off (the chunk's offset in the blob),
+ * out_chunk_len, out_chunk_file, out_keys, out_digests32 (32 B each). Any
+ * output may be NULL. n == 0 is SDCAS_OK with zero counts and
+ * out_file_chunks[0] == 0. One upload, the device call, the counts down, then
+ * exactly `chunks` entries of each array. */
+int sdcas_chunk_messages(sdcas_ctx *ctx, const uint8_t *blob, const uint64_t *offsets, const uint64_t *lens, size_t n,
+                         const sdcas_chunk_params *params, uint64_t *out_file_chunks, uint64_t *out_chunk_off,
+                         uint64_t *out_chunk_len, uint32_t *out_chunk_file, uint64_t *out_keys,
+                         uint8_t *out_digests32, sdcas_chunk_counts *out_counts);
+/* The same over device arrays, enqueued on `stream` with
+ * sdcas_dev_hash_messages's stream rules. sdcas_dev_identify's blob contract:
+ * d_blob and every offset 16-byte aligned, the blob readable 64 B past every
+ * file's end; nothing below d_blob + offsets[i] or at or past offsets[i] +
+ * lens[i] + 64 is read. max_chunks / max_slots: sdcas_chunk_plan's of these
+ * lengths (lengths on the device that need more are cut short at the bound;
+ * nothing is written past it). d_digests32 16-byte aligned, every other array
+ * 8-byte (d_chunk_file 4-byte) aligned: SDCAS_E_INVALID otherwise, before
+ * anything is enqueued. d_counts: six u64 in sdcas_chunk_counts' order,
+ * overwritten.
+ * THE CALL WAITS FOR THE DEVICE EXACTLY ONCE when d_keys or d_digests32 is
+ * given: after the cut pass it copies the counts and the chunk lengths (8 B
+ * per possible chunk) down and plans the hash batches on the host. Cut points
+ * fall on any byte and the batch hash takes 16-byte aligned messages, so each
+ * batch's chunks are first copied to aligned places in the context's scratch;
+ * the environment's SDCAS_CHUNK_PACK_BYTES (default 256 MiB, read per call)
+ * caps the packed bytes of a batch, which holds at least one chunk. With
+ * neither d_keys nor d_digests32 the call never waits. The workspace and the
+ * scratch are grown by the first call that needs them, which waits for the
+ * stream: warm up outside timed regions. */
+int sdcas_dev_chunk(sdcas_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_offsets, const uint64_t *d_lens, size_t n,
+                    const sdcas_chunk_params *params, uint64_t max_chunks, uint64_t max_slots,
+                    uint64_t *d_file_chunks, uint64_t *d_chunk_off, uint64_t *d_chunk_len, uint32_t *d_chunk_file,
+                    uint64_t *d_keys, uint8_t *d_digests32, uint64_t *d_counts, void *stream);
+
+/* Sharing: how many of a file's bytes already occur earlier in the corpus,
+ * and which earlier file holds most of them. chunk_file[c], chunk_len[c] and
+ * rep[c] describe m chunks of n_files files (sdcas_chunk_messages' arrays and
+ * sdcas_confirm_duplicates' out_rep over the chunks). A rep[c] outside [0, c]
+ * counts as c and is never used as an index; a chunk whose chunk_file is not
+ * below n_files takes no part, and a rep naming such a chunk counts as c.
+ *   origin(c) = chunk_file[rep[c]]
+ *   B(i, f)   = the sum of chunk_len[c] over file i's chunks with rep[c] != c
+ *               and origin(c) == f
+ *   out_new_bytes[i]   the sum of chunk_len[c] over i's chunks with rep[c] == c
+ *   out_self_bytes[i]  B(i, i)
+ *   out_other_bytes[i] the sum of B(i, f) over f != i
+ *   out_peer[i]        the f != i with the largest B(i, f) > 0, ties to the
+ *                      lowest f; -1 when there is none
+ *   out_peer_bytes[i]  B(i, out_peer[i]), or 0
+ * All sums are modulo 2^64; the results are exact and do not depend on
+ * scheduling. Any output may be NULL; m == 0 and n_files == 0 are SDCAS_OK.
+ * At most 2^30 chunks and fewer than 2^32 files (the pair (file, origin) is
+ * one 64-bit key): SDCAS_E_CAPACITY beyond. */
+typedef struct sdcas_sharing_counts {
+  uint64_t files;
+  uint64_t chunks;
+  uint64_t distinct_chunks; /* rep[c] == c */
+  uint64_t total_bytes;
+  uint64_t stored_bytes;    /* the sum of chunk_len over first occurrences: what a chunk store keeps */
+  uint64_t files_with_peer;
+} sdcas_sharing_counts;
+/* Host arrays: one upload, the device call, one download. */
+int sdcas_chunk_sharing(sdcas_ctx *ctx, const uint32_t *chunk_file, const uint64_t *chunk_len, const int64_t *rep,
+                        size_t m, size_t n_files, uint64_t *out_new_bytes, uint64_t *out_self_bytes,
+                        uint64_t *out_other_bytes, int64_t *out_peer, uint64_t *out_peer_bytes,
+                        sdcas_sharing_counts *out_counts);
+/* Device arrays, 8-byte aligned (d_chunk_file 4-byte): SDCAS_E_INVALID
+ * otherwise. Never waits for the device once the workspace (32 B per chunk
+ * rounded up to a power of two, 40 B per file) exists. d_counts: six u64 in
+ * sdcas_sharing_counts' order, overwritten. */
+int sdcas_dev_chunk_sharing(sdcas_ctx *ctx, const uint32_t *d_chunk_file, const uint64_t *d_chunk_len,
+                            const int64_t *d_rep, size_t m, size_t n_files, uint64_t *d_new_bytes,
+                            uint64_t *d_self_bytes, uint64_t *d_other_bytes, int64_t *d_peer, uint64_t *d_peer_bytes,
+                            uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

@@ -170,6 +170,30 @@ class Engine {
   };
   TreeTop tree_top(const std::vector<int64_t>& parent, const std::vector<int64_t>& rep);
 
+  // the files blob[offsets[i] .. offsets[i] + lens[i]) cut into content-defined
+  // chunks (sdcas_chunk_messages), every per-chunk array trimmed to the
+  // counts: file i's chunks are [file_chunks[i], file_chunks[i + 1]);
+  // chunk_off are offsets in the blob; digests holds 32 bytes per chunk.
+  // params null: SDCAS_CHUNK_PARAMS_DEFAULT
+  struct Chunks {
+    std::vector<uint64_t> file_chunks, chunk_off, chunk_len, keys;
+    std::vector<uint32_t> chunk_file;
+    std::vector<uint8_t> digests;
+    sdcas_chunk_counts counts{};
+  };
+  Chunks chunk_messages(const std::vector<uint8_t>& blob, const std::vector<uint64_t>& offsets,
+                        const std::vector<uint64_t>& lens, const sdcas_chunk_params* params = nullptr);
+  // per file, the bytes of its chunks seen first in it, earlier in it and in
+  // other files, and the other file that holds most of them
+  // (sdcas_chunk_sharing; rep: confirm_duplicates' rep over the chunks)
+  struct Sharing {
+    std::vector<uint64_t> new_bytes, self_bytes, other_bytes, peer_bytes;
+    std::vector<int64_t> peer;  // -1: none
+    sdcas_sharing_counts counts{};
+  };
+  Sharing chunk_sharing(const std::vector<uint32_t>& chunk_file, const std::vector<uint64_t>& chunk_len,
+                        const std::vector<int64_t>& rep, size_t n_files);
+
   sdcas_ctx* raw() { return ctx_; }
 
  private:
@@ -758,5 +782,34 @@ TreeReport tree_report_from(const std::vector<FilePathRow>& rows, const std::vec
 // keeps the top-most duplicates and lists them, directories and files mixed,
 // the most reclaimable first. Writes nothing.
 TreeReport tree_report(Engine& engine, Library& db, int32_t location_id, const std::string& sub = "");
+
+// ---- files that share most of their bytes ---------------------------------------------
+struct SimilarityReport {
+  struct Pair {
+    int32_t file_path_id = 0;
+    int32_t peer_id = 0;        // the other row that holds most of this row's repeated bytes
+    uint64_t shared_bytes = 0;  // the bytes of this row's chunks first seen in the peer
+    uint64_t size = 0;          // the bytes read from this row's file
+    bool operator==(const Pair& o) const {
+      return file_path_id == o.file_path_id && peer_id == o.peer_id && shared_bytes == o.shared_bytes && size == o.size;
+    }
+  };
+  std::vector<Pair> pairs;  // most shared bytes first, ties by file_path id ascending
+  sdcas_chunk_counts chunks{};
+  sdcas_sharing_counts counts{};
+};
+// The report's shaping, no GPU: rows and, with row i as file i, the bytes read
+// from each and Engine::Sharing's peer / peer_bytes. Throws
+// std::invalid_argument when the arrays do not fit the rows or name no other row.
+SimilarityReport similarity_report_from(const std::vector<FilePathRow>& rows, const std::vector<uint64_t>& sizes,
+                                        const std::vector<int64_t>& peer, const std::vector<uint64_t>& peer_bytes);
+// Read-only: reads the file rows of Library::file_paths_in_location(location.id,
+// sub) and their files' contents whole (a file that cannot be read counts as
+// empty; LibraryError with SDCAS_E_CAPACITY when they hold more than max_bytes
+// in all: the contents are resident at once), cuts them into content-defined
+// chunks, confirms the chunks' (key, digest) pairs, runs the sharing pass and
+// lists every row that has a peer. Writes nothing.
+SimilarityReport similarity_report(Engine& engine, Library& db, const Location& location, const std::string& sub = "",
+                                   uint64_t max_bytes = 1ull << 30);
 
 }  // namespace sdcore

@@ -44,6 +44,10 @@ SDCAS_TREE_INCOMPLETE = 2
 SDCAS_TREE_EMPTY = 4
 SDCAS_TOP_DUP = 1
 SDCAS_TOP_NESTED = 2
+SDCAS_CHUNK_PARAMS_DEFAULT = (2048, 13, 65536)
+SDCAS_CHUNK_MAX_CHUNKS = 1 << 30
+SDCAS_CHUNK_GEAR_TILE = 32768
+SDCAS_CHUNK_GEAR_STRIP = 128
 
 # every entry point include/sdcas.h and include/sdcas_bench.h declare
 ABI_SYMBOLS = [
@@ -55,6 +59,8 @@ ABI_SYMBOLS = [
     "sdcas_duplicate_sets", "sdcas_dev_duplicate_sets",  # added after ABI 7
     "sdcas_tree_plan", "sdcas_tree_digests", "sdcas_dev_tree_digests", "sdcas_tree_top",
     "sdcas_dev_tree_top",  # added after ABI 7
+    "sdcas_chunk_plan", "sdcas_chunk_messages", "sdcas_dev_chunk", "sdcas_chunk_sharing",
+    "sdcas_dev_chunk_sharing",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -146,6 +152,31 @@ class TopCounts(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class ChunkParams(ctypes.Structure):
+    """sdcas_chunk_params"""
+    _fields_ = [("min_len", ctypes.c_uint32), ("avg_bits", ctypes.c_uint32), ("max_len", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class ChunkCounts(ctypes.Structure):
+    """sdcas_chunk_counts"""
+    _fields_ = [("files", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("total_bytes", ctypes.c_uint64),
+                ("hash_cuts", ctypes.c_uint64), ("max_cuts", ctypes.c_uint64), ("end_chunks", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class SharingCounts(ctypes.Structure):
+    """sdcas_sharing_counts"""
+    _fields_ = [("files", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("distinct_chunks", ctypes.c_uint64),
+                ("total_bytes", ctypes.c_uint64), ("stored_bytes", ctypes.c_uint64),
+                ("files_with_peer", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _lib_path = LIB_PATH
 
@@ -215,6 +246,14 @@ def load():
     L.sdcas_dev_tree_digests.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.sdcas_tree_top.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, ctypes.POINTER(TopCounts)]
     L.sdcas_dev_tree_top.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]
+    L.sdcas_chunk_plan.argtypes = [_vp, _sz, ctypes.POINTER(ChunkParams), _vp, _vp]
+    L.sdcas_chunk_messages.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(ChunkParams), _vp, _vp, _vp, _vp, _vp,
+                                       _vp, ctypes.POINTER(ChunkCounts)]
+    L.sdcas_dev_chunk.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(ChunkParams), _u64, _u64, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp, _vp]
+    L.sdcas_chunk_sharing.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
+                                      ctypes.POINTER(SharingCounts)]
+    L.sdcas_dev_chunk_sharing.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

@@ -33,6 +33,7 @@
 #include "confirm.h"
 #include "dupsets.h"
 #include "dirtree.h"
+#include "cdc.h"
 #include "dist_dedup.h"
 #include "synth.h"
 
@@ -218,6 +219,12 @@ struct sdcas_ctx {
   HostStage tr_stage;
   DevBuf<uint32_t> tt_ws;
   DevBuf<int64_t> tt_io;
+
+  // content-defined chunks and their sharing (cdc.hip): the workspaces, the
+  // packed chunks of one hash batch, the packed offsets' upload, and the host
+  // calls' device copies of their arrays
+  DevBuf<uint8_t> cd_ws, cd_pack, cd_io, cs_ws, cs_io;
+  HostStage cd_stage;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -850,6 +857,8 @@ void sdcas_destroy(sdcas_ctx* c) {
   c->tr_stage.release();
   c->tt_ws.release();
   c->tt_io.release();
+  for (auto* b : {&c->cd_ws, &c->cd_pack, &c->cd_io, &c->cs_ws, &c->cs_io}) b->release();
+  c->cd_stage.release();
   c->dist.release();
   c->sm_d_files.release();
   c->sm_nodes.release();
@@ -2324,6 +2333,315 @@ int sdcas_tree_top(sdcas_ctx* c, const int64_t* parent, const int64_t* rep, size
       (out_counts && (e = hipMemcpyAsync(out_counts, io + 3 * n, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
     return c->hip_fail(e, "tree_top D2H");
   if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "tree_top sync");
+  return SDCAS_OK;
+}
+
+// ---- content-defined chunks and their sharing (cdc.hip) ---------------------------
+
+static CdcParams chunk_params(const sdcas_chunk_params* p) {
+  const sdcas_chunk_params d = SDCAS_CHUNK_PARAMS_DEFAULT;
+  if (!p) p = &d;
+  return CdcParams{p->min_len, p->avg_bits, p->max_len};
+}
+
+int sdcas_chunk_plan(const uint64_t* lens, size_t n, const sdcas_chunk_params* params, uint64_t* out_max_chunks,
+                     uint64_t* out_max_slots) {
+  static_assert(SDCAS_CHUNK_MAX_CHUNKS == kCdcMaxChunks && SDCAS_CHUNK_GEAR_TILE == kCdcTile &&
+                    SDCAS_CHUNK_GEAR_STRIP == kCdcStrip,
+                "chunk constants");
+  const CdcPlanError err = cdc_plan(lens, n, chunk_params(params), out_max_chunks, out_max_slots);
+  return err == kCdcOk ? SDCAS_OK : err == kCdcCapacity ? SDCAS_E_CAPACITY : SDCAS_E_INVALID;
+}
+
+// the packed bytes one hash batch may hold (SDCAS_CHUNK_PACK_BYTES, read per call)
+static uint64_t chunk_pack_cap() {
+  const char* v = getenv("SDCAS_CHUNK_PACK_BYTES");
+  const unsigned long long x = v ? strtoull(v, nullptr, 10) : 0;
+  return x ? x : 256ull << 20;
+}
+
+// Enqueue the whole of a chunk call on st (device arrays, valid parameters,
+// n != 0); waits for st once when keys or digests are asked for.
+static int chunk_enqueue(sdcas_ctx* c, const char* who, CdcArgs a, uint64_t* d_keys, uint8_t* d_digests32,
+                         uint64_t* d_counts, hipStream_t st) {
+  const CdcLayout l = cdc_layout(a.n, a.max_chunks, a.file_slots);
+  hipError_t e;
+  if (l.bytes > c->cd_ws.cap) {
+    // an earlier call's kernels may still use what is about to be freed
+    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->cd_ws.ensure(l.bytes)))
+      return c->hip_fail(e, "chunk workspace");
+  }
+  a.ws = c->cd_ws.p;
+  if ((e = cdc_chunk(l, a, st))) return c->hip_fail(e, who);
+  if (d_counts &&
+      (e = hipMemcpyAsync(d_counts, a.ws + l.counts, kCdcCounts * sizeof(uint64_t), hipMemcpyDeviceToDevice, st)))
+    return c->hip_fail(e, who);
+  if ((!d_keys && !d_digests32) || a.max_chunks == 0) return SDCAS_OK;
+
+  // the one wait: the counts and the chunk lengths down, the batches planned here
+  uint64_t cts[8] = {};
+  std::vector<uint64_t> len(a.max_chunks);
+  if ((e = hipMemcpyAsync(cts, a.ws + l.counts, sizeof cts, hipMemcpyDeviceToHost, st)) ||
+      (e = hipMemcpyAsync(len.data(), a.ws + l.wlen, 8 * a.max_chunks, hipMemcpyDeviceToHost, st)) ||
+      (e = hipStreamSynchronize(st)))
+    return c->hip_fail(e, "chunk lengths");
+  const uint64_t m = cts[1];
+  if (m > a.max_chunks || cts[7])
+    return c->fail(SDCAS_E_CAPACITY, "%s: the lengths on the device need more than max_chunks / max_slots", who);
+  if (m == 0) return SDCAS_OK;
+  // batches of consecutive chunks, each chunk at the next 16-byte boundary of its batch
+  struct Batch {
+    uint64_t c0, bytes, b3_chunks;
+    uint32_t nb;
+  };
+  const uint64_t cap = chunk_pack_cap();
+  std::vector<Batch> batches;
+  uint8_t* stage = nullptr;
+  if ((e = c->cd_stage.reserve(8 * m, &stage))) return c->hip_fail(e, "chunk pack upload");
+  uint64_t* po = reinterpret_cast<uint64_t*>(stage);
+  Batch b{0, 0, 0, 0};
+  uint64_t max_bytes = 0, max_b3 = 0;
+  uint32_t max_nb = 0;
+  for (uint64_t k = 0; k < m; ++k) {
+    const uint64_t padded = (len[k] + 15) & ~15ull;
+    if (b.nb && (b.bytes + padded > cap || b.nb == SDCAS_MAX_BATCH)) {
+      batches.push_back(b);
+      b = Batch{k, 0, 0, 0};
+    }
+    po[k] = b.bytes;
+    b.bytes += padded, b.b3_chunks += chunks_of(len[k]), ++b.nb;
+    max_bytes = std::max(max_bytes, b.bytes), max_b3 = std::max(max_b3, b.b3_chunks), max_nb = std::max(max_nb, b.nb);
+  }
+  batches.push_back(b);
+  if ((e = c->cd_stage.send(8 * m, a.ws + l.po, st))) return c->hip_fail(e, "chunk pack upload");
+  // (the stream is idle and waited for every earlier call: nothing uses what is freed here)
+  if (max_bytes + kSlack > c->cd_pack.cap && (e = c->cd_pack.ensure(max_bytes + kSlack)))
+    return c->hip_fail(e, "chunk pack scratch");
+  if (!c->ws.S || max_nb > c->ws.cap_msgs || max_b3 > c->ws.cap_chunks)
+    if (int rc = reserve_ws(c, std::max<size_t>(max_nb, c->ws.cap_msgs), std::max<uint64_t>(max_b3, c->ws.cap_chunks)))
+      return rc;
+  for (const Batch& x : batches) {
+    if ((e = cdc_pack(l, a, x.c0, x.nb, x.bytes, c->cd_pack.p, st))) return c->hip_fail(e, who);
+    if (int rc = launch_batch(c, c->cd_pack.p, reinterpret_cast<const uint64_t*>(a.ws + l.po) + x.c0,
+                              reinterpret_cast<const uint64_t*>(a.ws + l.wlen) + x.c0, x.nb,
+                              d_digests32 ? d_digests32 + 32 * x.c0 : nullptr, d_keys ? d_keys + x.c0 : nullptr, st,
+                              x.b3_chunks))
+      return rc;
+  }
+  return SDCAS_OK;
+}
+
+// the checks both chunk calls share; *slots <- max_slots - max_chunks
+static int chunk_args(sdcas_ctx* c, const char* who, const void* offs, const void* lens, size_t n, const CdcParams& p,
+                      uint64_t max_chunks, uint64_t max_slots, uint64_t* slots) {
+  if (!cdc_params_valid(p)) return c->fail(SDCAS_E_INVALID, "%s: invalid chunk parameters", who);
+  if (n && (!offs || !lens)) return c->fail(SDCAS_E_INVALID, "%s: null offsets or lens", who);
+  if (n >= 0xFFFFFFFFull) return c->fail(SDCAS_E_CAPACITY, "%s of %zu files exceeds 2^32 - 2", who, n);
+  if (max_chunks > kCdcMaxChunks) return c->fail(SDCAS_E_CAPACITY, "%s: more than 2^30 chunks", who);
+  if (max_slots < max_chunks || max_slots - max_chunks > 0xFFFFFFFEull)
+    return c->fail(SDCAS_E_CAPACITY, "%s: max_slots is below max_chunks or above 2^32", who);
+  *slots = max_slots - max_chunks;
+  return SDCAS_OK;
+}
+
+int sdcas_dev_chunk(sdcas_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, const uint64_t* d_lens, size_t n,
+                    const sdcas_chunk_params* params, uint64_t max_chunks, uint64_t max_slots, uint64_t* d_file_chunks,
+                    uint64_t* d_chunk_off, uint64_t* d_chunk_len, uint32_t* d_chunk_file, uint64_t* d_keys,
+                    uint8_t* d_digests32, uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  const CdcParams p = chunk_params(params);
+  uint64_t slots = 0;
+  if (int rc = chunk_args(c, "dev_chunk", d_offsets, d_lens, n, p, max_chunks, max_slots, &slots)) return rc;
+  if (n && !d_blob) return c->fail(SDCAS_E_INVALID, "dev_chunk: null blob");
+  if (((uintptr_t)d_blob | (uintptr_t)d_digests32) & 15)
+    return c->fail(SDCAS_E_INVALID, "dev_chunk: blob or digests not 16-byte aligned");
+  if ((((uintptr_t)d_offsets | (uintptr_t)d_lens | (uintptr_t)d_file_chunks | (uintptr_t)d_chunk_off |
+        (uintptr_t)d_chunk_len | (uintptr_t)d_keys | (uintptr_t)d_counts) & 7) || ((uintptr_t)d_chunk_file & 3))
+    return c->fail(SDCAS_E_INVALID, "dev_chunk: an array is not 8-byte (chunk_file: 4-byte) aligned");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (n == 0) {
+    hipError_t e;
+    if ((d_counts && (e = hipMemsetAsync(d_counts, 0, kCdcCounts * sizeof(uint64_t), call.st))) ||
+        (d_file_chunks && (e = hipMemsetAsync(d_file_chunks, 0, sizeof(uint64_t), call.st))))
+      return c->hip_fail(e, "dev_chunk");
+    return SDCAS_OK;
+  }
+  return chunk_enqueue(c, "dev_chunk",
+                       CdcArgs{nullptr, d_blob, d_offsets, d_lens, (uint32_t)n, p, max_chunks, slots, d_file_chunks,
+                               d_chunk_off, d_chunk_len, d_chunk_file},
+                       d_keys, d_digests32, d_counts, call.st);
+}
+
+int sdcas_chunk_messages(sdcas_ctx* c, const uint8_t* blob, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                         const sdcas_chunk_params* params, uint64_t* out_file_chunks, uint64_t* out_chunk_off,
+                         uint64_t* out_chunk_len, uint32_t* out_chunk_file, uint64_t* out_keys, uint8_t* out_digests32,
+                         sdcas_chunk_counts* out_counts) {
+  static_assert(sizeof(sdcas_chunk_counts) == kCdcCounts * sizeof(uint64_t), "six u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  const CdcParams p = chunk_params(params);
+  if (!cdc_params_valid(p)) return c->fail(SDCAS_E_INVALID, "chunk_messages: invalid chunk parameters");
+  if (n && (!offsets || !lens)) return c->fail(SDCAS_E_INVALID, "chunk_messages: null offsets or lens");
+  uint64_t max_chunks = 0, max_slots = 0, slots = 0;
+  if (cdc_plan(lens, n, p, &max_chunks, &max_slots) != kCdcOk)
+    return c->fail(SDCAS_E_CAPACITY, "chunk_messages: more than 2^30 chunks");
+  // every file at a 16-byte aligned place of the device copy, 64 readable bytes behind it
+  std::vector<uint64_t> at(n);
+  uint64_t bytes = 0, content = 0;
+  for (size_t i = 0; i < n; ++i) {
+    at[i] = bytes;
+    bytes += (lens[i] + kSlack + 15) & ~15ull;
+    content += lens[i];
+  }
+  if (content && !blob) return c->fail(SDCAS_E_INVALID, "chunk_messages: null blob");
+  if (int rc = chunk_args(c, "chunk_messages", offsets, lens, n, p, max_chunks, max_slots, &slots)) return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  if (n == 0) {
+    if (out_file_chunks) out_file_chunks[0] = 0;
+    return SDCAS_OK;
+  }
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = call.st;
+  // blob | offs | lens | file_chunks | chunk_off | chunk_len | keys | counts | digests | chunk_file
+  const uint64_t mc = max_chunks;
+  const uint64_t o_offs = bytes, o_lens = o_offs + 8 * n, o_fc = o_lens + 8 * n, o_off = o_fc + 8 * (n + 1),
+                 o_len = o_off + 8 * mc, o_keys = o_len + 8 * mc, o_cts = o_keys + 8 * mc, o_dig = o_cts + 64,
+                 o_file = o_dig + 32 * mc, total = o_file + 4 * mc;
+  if (total > c->cd_io.cap) {
+    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->cd_io.ensure(total)))
+      return c->hip_fail(e, "chunk_messages buffers");
+  }
+  uint8_t* io = c->cd_io.p;
+  {
+    // the files, packed on the host, in one upload
+    std::vector<uint8_t> img(bytes + 16 * n, 0);
+    uint64_t* hoffs = reinterpret_cast<uint64_t*>(img.data() + bytes);
+    for (size_t i = 0; i < n; ++i) {
+      if (lens[i]) memcpy(img.data() + at[i], blob + offsets[i], lens[i]);
+      hoffs[i] = at[i], hoffs[n + i] = lens[i];
+    }
+    if ((e = hipMemcpyAsync(io, img.data(), img.size(), hipMemcpyHostToDevice, st)) || (e = hipStreamSynchronize(st)))
+      return c->hip_fail(e, "chunk_messages H2D");
+  }
+  CdcArgs a{nullptr,
+            io,
+            reinterpret_cast<const uint64_t*>(io + o_offs),
+            reinterpret_cast<const uint64_t*>(io + o_lens),
+            (uint32_t)n,
+            p,
+            max_chunks,
+            slots,
+            reinterpret_cast<uint64_t*>(io + o_fc),
+            reinterpret_cast<uint64_t*>(io + o_off),
+            reinterpret_cast<uint64_t*>(io + o_len),
+            reinterpret_cast<uint32_t*>(io + o_file)};
+  if (int rc = chunk_enqueue(c, "chunk_messages", a, out_keys ? reinterpret_cast<uint64_t*>(io + o_keys) : nullptr,
+                             out_digests32 ? io + o_dig : nullptr, reinterpret_cast<uint64_t*>(io + o_cts), st))
+    return rc;
+  // the counts down first: they say how many entries of each array follow
+  sdcas_chunk_counts cts;
+  if ((e = hipMemcpyAsync(&cts, io + o_cts, sizeof cts, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
+    return c->hip_fail(e, "chunk_messages counts");
+  const uint64_t m = cts.chunks;
+  if (m > mc) return c->fail(SDCAS_E_HIP, "chunk_messages: counts out of range");
+  std::vector<uint32_t> file(out_chunk_off ? m : 0);
+  if ((out_file_chunks && (e = hipMemcpyAsync(out_file_chunks, io + o_fc, 8 * (n + 1), hipMemcpyDeviceToHost, st))) ||
+      (m && out_chunk_off && ((e = hipMemcpyAsync(out_chunk_off, io + o_off, 8 * m, hipMemcpyDeviceToHost, st)) ||
+                              (e = hipMemcpyAsync(file.data(), io + o_file, 4 * m, hipMemcpyDeviceToHost, st)))) ||
+      (m && out_chunk_len && (e = hipMemcpyAsync(out_chunk_len, io + o_len, 8 * m, hipMemcpyDeviceToHost, st))) ||
+      (m && out_chunk_file && (e = hipMemcpyAsync(out_chunk_file, io + o_file, 4 * m, hipMemcpyDeviceToHost, st))) ||
+      (m && out_keys && (e = hipMemcpyAsync(out_keys, io + o_keys, 8 * m, hipMemcpyDeviceToHost, st))) ||
+      (m && out_digests32 && (e = hipMemcpyAsync(out_digests32, io + o_dig, 32 * m, hipMemcpyDeviceToHost, st))))
+    return c->hip_fail(e, "chunk_messages D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_messages sync");
+  // offsets in the caller's blob, not in the device copy
+  if (out_chunk_off)
+    for (uint64_t k = 0; k < m; ++k)
+      if (file[k] < n) out_chunk_off[k] = out_chunk_off[k] - at[file[k]] + offsets[file[k]];
+  if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+static int sharing_args(sdcas_ctx* c, const char* who, const void* chunk_file, const void* chunk_len, const void* rep,
+                        size_t m, size_t n_files) {
+  if (m > kCdcMaxChunks) return c->fail(SDCAS_E_CAPACITY, "%s of %zu chunks exceeds 2^30", who, m);
+  if (n_files >= 0xFFFFFFFFull) return c->fail(SDCAS_E_CAPACITY, "%s of %zu files exceeds 2^32 - 2", who, n_files);
+  if (m && (!chunk_file || !chunk_len || !rep)) return c->fail(SDCAS_E_INVALID, "%s: null chunk_file, chunk_len or rep", who);
+  return SDCAS_OK;
+}
+
+// the workspace grown to m chunks of n_files files; the stream waits first, as
+// an earlier call's kernels may still use the workspace about to be freed
+static int sharing_ws(sdcas_ctx* c, size_t m, size_t n_files, hipStream_t st) {
+  const size_t need = (size_t)cdc_share_ws_bytes(m, n_files);
+  if (need <= c->cs_ws.cap) return SDCAS_OK;
+  hipError_t e = c->scratch_sync();
+  if (!e) e = hipStreamSynchronize(st);
+  if (!e) e = c->cs_ws.ensure(need);
+  return e ? c->hip_fail(e, "chunk sharing workspace") : SDCAS_OK;
+}
+
+int sdcas_dev_chunk_sharing(sdcas_ctx* c, const uint32_t* d_chunk_file, const uint64_t* d_chunk_len,
+                            const int64_t* d_rep, size_t m, size_t n_files, uint64_t* d_new_bytes,
+                            uint64_t* d_self_bytes, uint64_t* d_other_bytes, int64_t* d_peer, uint64_t* d_peer_bytes,
+                            uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = sharing_args(c, "dev_chunk_sharing", d_chunk_file, d_chunk_len, d_rep, m, n_files)) return rc;
+  if ((((uintptr_t)d_chunk_len | (uintptr_t)d_rep | (uintptr_t)d_new_bytes | (uintptr_t)d_self_bytes |
+        (uintptr_t)d_other_bytes | (uintptr_t)d_peer | (uintptr_t)d_peer_bytes | (uintptr_t)d_counts) & 7) ||
+      ((uintptr_t)d_chunk_file & 3))
+    return c->fail(SDCAS_E_INVALID, "dev_chunk_sharing: an array is not 8-byte (chunk_file: 4-byte) aligned");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = sharing_ws(c, m, n_files, call.st)) return rc;
+  hipError_t e = cdc_sharing(c->cs_ws.p, d_chunk_file, d_chunk_len, d_rep, (uint32_t)m, (uint32_t)n_files, d_new_bytes,
+                             d_self_bytes, d_other_bytes, d_peer, d_peer_bytes, (unsigned long long*)d_counts, call.st);
+  return e ? c->hip_fail(e, "dev_chunk_sharing") : SDCAS_OK;
+}
+
+int sdcas_chunk_sharing(sdcas_ctx* c, const uint32_t* chunk_file, const uint64_t* chunk_len, const int64_t* rep,
+                        size_t m, size_t n_files, uint64_t* out_new_bytes, uint64_t* out_self_bytes,
+                        uint64_t* out_other_bytes, int64_t* out_peer, uint64_t* out_peer_bytes,
+                        sdcas_sharing_counts* out_counts) {
+  static_assert(sizeof(sdcas_sharing_counts) == kCdcCounts * sizeof(uint64_t), "six u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = sharing_args(c, "chunk_sharing", chunk_file, chunk_len, rep, m, n_files)) return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = call.st;
+  // chunk_len | rep | new | self | other | peer | peer_bytes | counts | chunk_file
+  const size_t nf = n_files;
+  const size_t o_rep = 8 * m, o_new = 16 * m, o_self = o_new + 8 * nf, o_other = o_self + 8 * nf,
+               o_peer = o_other + 8 * nf, o_pb = o_peer + 8 * nf, o_cts = o_pb + 8 * nf, o_file = o_cts + 64,
+               total = o_file + 4 * m;
+  if (total > c->cs_io.cap) {
+    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->cs_io.ensure(total)))
+      return c->hip_fail(e, "chunk_sharing buffers");
+  }
+  if (int rc = sharing_ws(c, m, n_files, st)) return rc;
+  uint8_t* io = c->cs_io.p;
+  if (m && ((e = hipMemcpyAsync(io, chunk_len, 8 * m, hipMemcpyHostToDevice, st)) ||
+            (e = hipMemcpyAsync(io + o_rep, rep, 8 * m, hipMemcpyHostToDevice, st)) ||
+            (e = hipMemcpyAsync(io + o_file, chunk_file, 4 * m, hipMemcpyHostToDevice, st))))
+    return c->hip_fail(e, "chunk_sharing H2D");
+  if ((e = cdc_sharing(c->cs_ws.p, reinterpret_cast<const uint32_t*>(io + o_file), reinterpret_cast<const uint64_t*>(io),
+                       reinterpret_cast<const int64_t*>(io + o_rep), (uint32_t)m, (uint32_t)n_files,
+                       reinterpret_cast<uint64_t*>(io + o_new), reinterpret_cast<uint64_t*>(io + o_self),
+                       reinterpret_cast<uint64_t*>(io + o_other), reinterpret_cast<int64_t*>(io + o_peer),
+                       reinterpret_cast<uint64_t*>(io + o_pb), reinterpret_cast<unsigned long long*>(io + o_cts), st)))
+    return c->hip_fail(e, "chunk_sharing");
+  if ((nf && out_new_bytes && (e = hipMemcpyAsync(out_new_bytes, io + o_new, 8 * nf, hipMemcpyDeviceToHost, st))) ||
+      (nf && out_self_bytes && (e = hipMemcpyAsync(out_self_bytes, io + o_self, 8 * nf, hipMemcpyDeviceToHost, st))) ||
+      (nf && out_other_bytes && (e = hipMemcpyAsync(out_other_bytes, io + o_other, 8 * nf, hipMemcpyDeviceToHost, st))) ||
+      (nf && out_peer && (e = hipMemcpyAsync(out_peer, io + o_peer, 8 * nf, hipMemcpyDeviceToHost, st))) ||
+      (nf && out_peer_bytes && (e = hipMemcpyAsync(out_peer_bytes, io + o_pb, 8 * nf, hipMemcpyDeviceToHost, st))) ||
+      (out_counts && (e = hipMemcpyAsync(out_counts, io + o_cts, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
+    return c->hip_fail(e, "chunk_sharing D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_sharing sync");
   return SDCAS_OK;
 }
 

@@ -475,7 +475,128 @@ class Engine:
                 "set_bytes": set_bytes, "members": members, "tree_counts": tcounts, "top_counts": top_counts,
                 "sets_counts": scounts}
 
+    # -- content-defined chunks: files that share most of their bytes ---------------
+    @staticmethod
+    def _chunk_params(params):
+        mn, bits, mx = N.SDCAS_CHUNK_PARAMS_DEFAULT if params is None else (int(v) for v in params)
+        return N.ChunkParams(mn, bits, mx, 0)
+
+    @staticmethod
+    def chunk_plan(lens, params=None):
+        """sdcas_chunk_plan (no GPU): SdcasError with SDCAS_E_INVALID for
+        invalid parameters (min_len, avg_bits, max_len), SDCAS_E_CAPACITY above
+        2^30 chunks -> (max_chunks: the entries of every per-chunk array,
+        max_slots: what sizes dev_chunk's workspace)"""
+        lens = _arr(lens, np.uint64)
+        mc, ms = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        cp = Engine._chunk_params(params)
+        rc = N.load().sdcas_chunk_plan(_ptr(lens), lens.size, ctypes.byref(cp), ctypes.byref(mc), ctypes.byref(ms))
+        if rc != N.SDCAS_OK:
+            raise N.SdcasError(rc, "sdcas_chunk_plan: the parameters or the lengths are refused")
+        return int(mc.value), int(ms.value)
+
+    def chunk_messages(self, blob, offsets, lens, params=None, hashes=True):
+        """the files blob[offsets[i] : offsets[i] + lens[i]] cut into
+        content-defined chunks (sdcas_chunk_messages; the definition is in
+        include/sdcas.h) -> (file_chunks uint64[n + 1], chunk_off uint64[m]:
+        offsets in the blob, chunk_len uint64[m], chunk_file uint32[m], keys
+        uint64[m], digests uint8[m, 32], counts: dict of sdcas_chunk_counts'
+        six fields). hashes False: no keys and digests (None)"""
+        blob = _arr(blob, np.uint8)
+        offsets, lens = _arr(offsets, np.uint64), _arr(lens, np.uint64)
+        n = lens.size
+        if offsets.size != n:
+            raise ValueError(f"chunk_messages: {n} lens, {offsets.size} offsets")
+        if n and int((offsets + lens).max()) > blob.size:
+            raise ValueError("chunk_messages: a file ends past the blob")
+        mc, _ = self.chunk_plan(lens, params)
+        fc = np.zeros(n + 1, np.uint64)
+        off, ln = np.zeros(mc, np.uint64), np.zeros(mc, np.uint64)
+        fl = np.zeros(mc, np.uint32)
+        keys = np.zeros(mc, np.uint64) if hashes else None
+        dig = np.zeros((mc, 32), np.uint8) if hashes else None
+        counts = N.ChunkCounts()
+        cp = self._chunk_params(params)
+        self._check(self.L.sdcas_chunk_messages(self.ctx, _ptr(blob), _ptr(offsets), _ptr(lens), n, ctypes.byref(cp),
+                                                _ptr(fc), _ptr(off), _ptr(ln), _ptr(fl),
+                                                _ptr(keys) if hashes else None, _ptr(dig) if hashes else None,
+                                                ctypes.byref(counts)), "sdcas_chunk_messages")
+        m = int(counts.chunks)
+        return fc, off[:m].copy(), ln[:m].copy(), fl[:m].copy(), keys[:m].copy() if hashes else None, \
+            dig[:m].copy() if hashes else None, counts.as_dict()
+
+    def chunk_sharing(self, chunk_file, chunk_len, rep, n_files):
+        """per file, the bytes of its chunks seen first in it, earlier in it
+        and in other files, and the other file that holds most of them
+        (sdcas_chunk_sharing; rep: confirm_duplicates' rep over the chunks) ->
+        (new_bytes, self_bytes, other_bytes uint64[n_files], peer
+        int64[n_files]: -1 for none, peer_bytes uint64[n_files], counts: dict
+        of sdcas_sharing_counts' six fields)"""
+        chunk_file, chunk_len, rep = _arr(chunk_file, np.uint32), _arr(chunk_len, np.uint64), _arr(rep, np.int64)
+        m, nf = chunk_file.size, int(n_files)
+        if chunk_len.size != m or rep.size != m:
+            raise ValueError(f"chunk_sharing: {m} chunk files, {chunk_len.size} lengths, {rep.size} reps")
+        new, own, other = (np.zeros(nf, np.uint64) for _ in range(3))
+        peer, peer_bytes = np.zeros(nf, np.int64), np.zeros(nf, np.uint64)
+        counts = N.SharingCounts()
+        self._check(self.L.sdcas_chunk_sharing(self.ctx, _ptr(chunk_file), _ptr(chunk_len), _ptr(rep), m, nf,
+                                               _ptr(new), _ptr(own), _ptr(other), _ptr(peer), _ptr(peer_bytes),
+                                               ctypes.byref(counts)), "sdcas_chunk_sharing")
+        return new, own, other, peer, peer_bytes, counts.as_dict()
+
+    def similar_files(self, paths, params=None, max_bytes=1 << 30):
+        """which of these files share most of their bytes: the files are read
+        whole (ValueError when they hold more than max_bytes in total: the
+        contents must be resident at once), cut into content-defined chunks,
+        the chunks grouped by (key, digest) and the sharing pass run over them
+        -> dict with the per-file arrays "sizes", "new_bytes", "self_bytes",
+        "other_bytes", "peer", "peer_bytes", the chunk arrays "file_chunks",
+        "chunk_off" (offsets in the file), "chunk_len", "chunk_file", "keys",
+        "digests", "rep", and "chunk_counts", "sharing_counts"."""
+        paths = [os.fspath(p) for p in paths]
+        total = sum(os.path.getsize(p) for p in paths)
+        if total > int(max_bytes):
+            raise ValueError(f"similar_files: {total} bytes in {len(paths)} files exceed max_bytes = {int(max_bytes)}")
+        data = []
+        for p in paths:
+            with open(p, "rb") as f:
+                data.append(f.read())
+        if sum(len(d) for d in data) > int(max_bytes):
+            raise ValueError(f"similar_files: the files grew past max_bytes = {int(max_bytes)}")
+        blob, offs, lens = self.pack(data)
+        fc, off, ln, fl, keys, dig, ccounts = self.chunk_messages(blob, offs, lens, params)
+        rep = self.confirm_duplicates(keys, dig)[0]
+        new, own, other, peer, peer_bytes, scounts = self.chunk_sharing(fl, ln, rep, len(paths))
+        return {"sizes": lens, "new_bytes": new, "self_bytes": own, "other_bytes": other, "peer": peer,
+                "peer_bytes": peer_bytes, "file_chunks": fc, "chunk_off": off - offs[fl], "chunk_len": ln,
+                "chunk_file": fl, "keys": keys, "digests": dig, "rep": rep, "chunk_counts": ccounts,
+                "sharing_counts": scounts}
+
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
+    def dev_chunk(self, blob, offs, lens, n, max_chunks, max_slots, params=None, file_chunks=0, chunk_off=0,
+                  chunk_len=0, chunk_file=0, keys=0, digests=0, counts=0, stream=0):
+        """chunk_messages over device arrays (sdcas_dev_chunk): the blob and
+        every offset 16-byte aligned, the blob readable 64 B past every file's
+        end; max_chunks / max_slots: chunk_plan's of the lengths; any output
+        may be 0; counts six uint64. Waits for the device once when keys or
+        digests are asked for, never otherwise"""
+        cp = self._chunk_params(params)
+        self._check(self.L.sdcas_dev_chunk(self.ctx, blob or None, offs or None, lens or None, int(n),
+                                           ctypes.byref(cp), int(max_chunks), int(max_slots), file_chunks or None,
+                                           chunk_off or None, chunk_len or None, chunk_file or None, keys or None,
+                                           digests or None, counts or None, stream or None), "dev_chunk")
+
+    def dev_chunk_sharing(self, chunk_file, chunk_len, rep, m, n_files, new_bytes=0, self_bytes=0, other_bytes=0,
+                          peer=0, peer_bytes=0, counts=0, stream=0):
+        """chunk_sharing over device arrays (sdcas_dev_chunk_sharing), e.g.
+        dev_chunk's chunk_file / chunk_len and dev_confirm_duplicates' rep as
+        they are; any output may be 0; counts six uint64; nothing waits for
+        the device"""
+        self._check(self.L.sdcas_dev_chunk_sharing(self.ctx, chunk_file or None, chunk_len or None, rep or None,
+                                                   int(m), int(n_files), new_bytes or None, self_bytes or None,
+                                                   other_bytes or None, peer or None, peer_bytes or None,
+                                                   counts or None, stream or None), "dev_chunk_sharing")
+
     def dev_tree_digests(self, parent, is_dir, name32, sizes, n, keys=0, digests=0, valid=0, tree_bytes=0,
                          tree_files=0, flags=0, counts=0, stream=0):
         """tree_digests over device arrays (sdcas_dev_tree_digests): parent

@@ -1646,4 +1646,100 @@ TreeReport tree_report(Engine& engine, Library& db, int32_t location_id, const s
   return out;
 }
 
+// ---- files that share most of their bytes ---------------------------------------------
+
+Engine::Chunks Engine::chunk_messages(const std::vector<uint8_t>& blob, const std::vector<uint64_t>& offsets,
+                                      const std::vector<uint64_t>& lens, const sdcas_chunk_params* params) {
+  const size_t n = lens.size();
+  if (offsets.size() != n) throw std::invalid_argument("chunk_messages: offsets / lens lengths differ");
+  for (size_t i = 0; i < n; ++i)
+    if (offsets[i] > blob.size() || lens[i] > blob.size() - offsets[i])
+      throw std::invalid_argument("chunk_messages: file " + std::to_string(i) + " ends past the blob");
+  uint64_t max_chunks = 0;
+  int rc = sdcas_chunk_plan(lens.data(), n, params, &max_chunks, nullptr);
+  if (rc != SDCAS_OK) throw LibraryError(rc, "sdcas_chunk_plan: the parameters or the lengths are refused");
+  Chunks r;
+  r.file_chunks.assign(n + 1, 0);
+  r.chunk_off.assign(max_chunks, 0), r.chunk_len.assign(max_chunks, 0), r.keys.assign(max_chunks, 0);
+  r.chunk_file.assign(max_chunks, 0);
+  r.digests.assign(32 * max_chunks, 0);
+  rc = sdcas_chunk_messages(ctx_, blob.data(), offsets.data(), lens.data(), n, params, r.file_chunks.data(),
+                            r.chunk_off.data(), r.chunk_len.data(), r.chunk_file.data(), r.keys.data(),
+                            r.digests.data(), &r.counts);
+  if (rc != SDCAS_OK) fail(rc, "sdcas_chunk_messages");
+  const size_t m = r.counts.chunks;
+  r.chunk_off.resize(m), r.chunk_len.resize(m), r.keys.resize(m), r.chunk_file.resize(m), r.digests.resize(32 * m);
+  return r;
+}
+
+Engine::Sharing Engine::chunk_sharing(const std::vector<uint32_t>& chunk_file, const std::vector<uint64_t>& chunk_len,
+                                      const std::vector<int64_t>& rep, size_t n_files) {
+  const size_t m = chunk_file.size();
+  if (chunk_len.size() != m || rep.size() != m) throw std::invalid_argument("chunk_sharing: the arrays' lengths differ");
+  Sharing r;
+  r.new_bytes.assign(n_files, 0), r.self_bytes.assign(n_files, 0), r.other_bytes.assign(n_files, 0);
+  r.peer_bytes.assign(n_files, 0);
+  r.peer.assign(n_files, -1);
+  const int rc = sdcas_chunk_sharing(ctx_, chunk_file.data(), chunk_len.data(), rep.data(), m, n_files,
+                                     r.new_bytes.data(), r.self_bytes.data(), r.other_bytes.data(), r.peer.data(),
+                                     r.peer_bytes.data(), &r.counts);
+  if (rc != SDCAS_OK) fail(rc, "sdcas_chunk_sharing");
+  return r;
+}
+
+SimilarityReport similarity_report_from(const std::vector<FilePathRow>& rows, const std::vector<uint64_t>& sizes,
+                                        const std::vector<int64_t>& peer, const std::vector<uint64_t>& peer_bytes) {
+  const size_t n = rows.size();
+  if (sizes.size() != n || peer.size() != n || peer_bytes.size() != n)
+    throw std::invalid_argument("similarity_report_from: sizes / peer / peer_bytes do not fit the rows");
+  SimilarityReport out;
+  for (size_t i = 0; i < n; ++i) {
+    if (peer[i] == -1) {
+      if (peer_bytes[i]) throw std::invalid_argument("similarity_report_from: row " + std::to_string(i) + " shares bytes with no peer");
+      continue;
+    }
+    if (peer[i] < 0 || (uint64_t)peer[i] >= n || (size_t)peer[i] == i)
+      throw std::invalid_argument("similarity_report_from: the peer of row " + std::to_string(i) + " is no other row");
+    out.pairs.push_back(SimilarityReport::Pair{rows[i].id, rows[(size_t)peer[i]].id, peer_bytes[i], sizes[i]});
+  }
+  std::sort(out.pairs.begin(), out.pairs.end(), [](const SimilarityReport::Pair& a, const SimilarityReport::Pair& b) {
+    return a.shared_bytes != b.shared_bytes ? a.shared_bytes > b.shared_bytes : a.file_path_id < b.file_path_id;
+  });
+  return out;
+}
+
+SimilarityReport similarity_report(Engine& engine, Library& db, const Location& location, const std::string& sub,
+                                   uint64_t max_bytes) {
+  std::vector<FilePathRow> rows;
+  for (FilePathRow& r : db.file_paths_in_location(location.id, sub))
+    if (!r.is_dir) rows.push_back(std::move(r));
+  const size_t n = rows.size();
+  if (n == 0) return SimilarityReport{};
+  std::vector<uint8_t> blob;
+  std::vector<uint64_t> offsets(n, 0), lens(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    offsets[i] = blob.size();
+    std::FILE* f = std::fopen(full_path(location, rows[i]).c_str(), "rb");
+    if (!f) continue;
+    uint8_t buf[1 << 16];
+    for (size_t got; (got = std::fread(buf, 1, sizeof buf, f)) > 0;) {
+      if (blob.size() + got > max_bytes) {
+        std::fclose(f);
+        throw LibraryError(SDCAS_E_CAPACITY, "similarity_report: the files hold more than max_bytes = " +
+                                                 std::to_string(max_bytes) + " bytes");
+      }
+      blob.insert(blob.end(), buf, buf + got);
+    }
+    std::fclose(f);
+    lens[i] = blob.size() - offsets[i];
+  }
+  const Engine::Chunks ch = engine.chunk_messages(blob, offsets, lens);
+  const Engine::Confirm c = engine.confirm_duplicates(ch.keys, ch.digests, {});
+  const Engine::Sharing s = engine.chunk_sharing(ch.chunk_file, ch.chunk_len, c.rep, n);
+  SimilarityReport out = similarity_report_from(rows, lens, s.peer, s.peer_bytes);
+  out.chunks = ch.counts;
+  out.counts = s.counts;
+  return out;
+}
+
 }  // namespace sdcore
