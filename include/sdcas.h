@@ -692,6 +692,69 @@ int sdcas_dev_chunk(sdcas_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_off
                     uint64_t *d_file_chunks, uint64_t *d_chunk_off, uint64_t *d_chunk_len, uint32_t *d_chunk_file,
                     uint64_t *d_keys, uint8_t *d_digests32, uint64_t *d_counts, void *stream);
 
+/* ---- chunk windows: a file chunked piece by piece ---------------------------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * A window is W bytes of a file that begin at a cut of that file: at byte 0 or
+ * at a `consumed` returned for the window before. Its flag `final` says that
+ * the window ends where the file ends. The chain runs from s = 0 while s < W:
+ *   final        exactly the cuts above with L = W
+ *   not final    hi = min(s + max_len, W). If W - s >= min_len and there is a
+ *                candidate e in [s + min_len, hi] (the same STRICT / LOOSE
+ *                rule), cut at the smallest: a HASH cut. Else if s + max_len
+ *                <= W, cut at s + max_len: a MAX cut. Else stop. A window
+ *                that is not final never holds an END chunk
+ *   consumed     s when the chain stops; W for a final window
+ * h(p) depends on the 32 bytes ending at p and min_len >= 32: a chain that
+ * starts at a cut s looks at positions >= s + min_len - 1 only, whose 32 bytes
+ * lie in [s, ...). So a window gives the cuts the whole file gives from the
+ * window's start on, without any byte before it, and
+ *   - the caller's next window of that file starts at `consumed`: the bytes
+ *     behind it (fewer than max_len) are delivered again with what follows;
+ *   - a window of max_len bytes or more that is not final always advances;
+ *     a shorter one may return consumed == 0 and no chunk;
+ *   - the chunks of a file's windows, one after the other, are the chunks of
+ *     the whole file, and the six counts summed over the windows of a
+ *     sequence of files are sdcas_chunk_messages' counts over the files:
+ *     `files` counts the final windows, `total_bytes` is the sum of consumed;
+ *   - no byte at or past `consumed` of a window that is not final is hashed.
+ * A window of 2 * seg bytes or more is cut by many waves at once: one chain
+ * per segment of seg bytes, started at the segment's first byte, and one wave
+ * per window that walks the true chain only until it lands on a cut of the
+ * segment's own chain; from there on the two are one, since the chain from a
+ * position depends on that position alone. The results do not depend on seg. */
+/* GPU-free. The segment length the cut pass uses for these parameters (NULL:
+ * the default): SDCAS_CHUNK_SEG_BYTES from the environment (read per call,
+ * default 1 MiB), not below 2 * max_len, rounded up to a multiple of 64. 0 for
+ * invalid parameters. */
+uint64_t sdcas_chunk_seg_bytes(const sdcas_chunk_params *params);
+/* sdcas_chunk_messages over windows: final[i] != 0 marks a final window
+ * (final NULL: all are, and every output equals sdcas_chunk_messages');
+ * out_consumed: n entries. */
+int sdcas_chunk_windows(sdcas_ctx *ctx, const uint8_t *blob, const uint64_t *offsets, const uint64_t *lens,
+                        const uint8_t *final, size_t n, const sdcas_chunk_params *params, uint64_t *out_file_chunks,
+                        uint64_t *out_chunk_off, uint64_t *out_chunk_len, uint32_t *out_chunk_file,
+                        uint64_t *out_keys, uint8_t *out_digests32, uint64_t *out_consumed,
+                        sdcas_chunk_counts *out_counts);
+/* sdcas_dev_chunk over windows, with every contract of that call: the blob's
+ * alignment and its 64 readable bytes, nothing read below offsets[i] or at or
+ * past offsets[i] + lens[i] + 64, max_chunks / max_slots sdcas_chunk_plan's of
+ * the window lengths (a window has at most ceil(len / min_len) chunks too),
+ * entries past `chunks` left as they were, any output NULL, n == 0 SDCAS_OK,
+ * the alignments (d_consumed 8-byte, d_final any) checked before anything is
+ * enqueued, ONE WAIT when d_keys or d_digests32 is given and none otherwise:
+ * d_consumed is a device output and costs no wait. The workspace takes, above
+ * sdcas_dev_chunk's, about 12 B per possible chunk for the segments' lists (sized
+ * from max_chunks, max_slots and the parameters; every index is checked
+ * against its bound on the device). With d_final NULL every output equals
+ * sdcas_dev_chunk's. */
+int sdcas_dev_chunk_windows(sdcas_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_offsets, const uint64_t *d_lens,
+                            const uint8_t *d_final, size_t n, const sdcas_chunk_params *params, uint64_t max_chunks,
+                            uint64_t max_slots, uint64_t *d_file_chunks, uint64_t *d_chunk_off,
+                            uint64_t *d_chunk_len, uint32_t *d_chunk_file, uint64_t *d_keys, uint8_t *d_digests32,
+                            uint64_t *d_consumed, uint64_t *d_counts, void *stream);
+
 /* Sharing: how many of a file's bytes already occur earlier in the corpus,
  * and which earlier file holds most of them. chunk_file[c], chunk_len[c] and
  * rep[c] describe m chunks of n_files files (sdcas_chunk_messages' arrays and

@@ -193,6 +193,16 @@ class Engine {
   };
   Sharing chunk_sharing(const std::vector<uint32_t>& chunk_file, const std::vector<uint64_t>& chunk_len,
                         const std::vector<int64_t>& rep, size_t n_files);
+  // chunk_messages over windows (sdcas_chunk_windows): window i holds bytes of
+  // a file from one of its cuts on, final[i] != 0 says that it ends where the
+  // file ends (final empty: all do); consumed[i] is where the next window of
+  // that file begins, relative to this one
+  struct WindowChunks : Chunks {
+    std::vector<uint64_t> consumed;
+  };
+  WindowChunks chunk_windows(const std::vector<uint8_t>& blob, const std::vector<uint64_t>& offsets,
+                             const std::vector<uint64_t>& lens, const std::vector<uint8_t>& final,
+                             const sdcas_chunk_params* params = nullptr);
 
   sdcas_ctx* raw() { return ctx_; }
 
@@ -811,5 +821,44 @@ SimilarityReport similarity_report_from(const std::vector<FilePathRow>& rows, co
 // lists every row that has a peer. Writes nothing.
 SimilarityReport similarity_report(Engine& engine, Library& db, const Location& location, const std::string& sub = "",
                                    uint64_t max_bytes = 1ull << 30);
+
+
+// ---- the same for files that are not resident at once ----------------------------------
+// The windows of files of these sizes, taken in order (no GPU): consecutive
+// whole files while they fit in window_bytes together (streamed false); a
+// file larger than window_bytes alone, over consecutive windows (streamed
+// true, n_files 1). Throws std::invalid_argument for window_bytes == 0.
+struct WindowPlan {
+  size_t first_file = 0, n_files = 0;
+  bool streamed = false;
+  bool operator==(const WindowPlan& o) const {
+    return first_file == o.first_file && n_files == o.n_files && streamed == o.streamed;
+  }
+};
+std::vector<WindowPlan> plan_chunk_windows(const std::vector<uint64_t>& sizes, uint64_t window_bytes);
+// One window's result: its files are first_file .. first_file + offsets.size(),
+// offsets where each begins in the window's blob (Engine::chunk_windows'
+// argument), file_pos where a streamed file's window begins in the file.
+struct ChunkWindow {
+  size_t first_file = 0;
+  uint64_t file_pos = 0;
+  std::vector<uint64_t> offsets;
+  Engine::WindowChunks chunks;
+};
+// The windows' arrays as one call over the whole files would give them (no
+// GPU): chunk_file are indices into the n_files files, chunk_off offsets in
+// the file, file_chunks the files' first chunks, the counts summed;
+// sizes[i] the bytes consumed of file i. The windows come in file order:
+// throws std::invalid_argument for a window that goes back, names a file past
+// n_files, or whose arrays do not fit each other.
+Engine::Chunks merge_chunk_windows(const std::vector<ChunkWindow>& windows, size_t n_files,
+                                   std::vector<uint64_t>* sizes = nullptr);
+// similarity_report without the contents being resident at once: the files
+// go through windows of at most window_bytes (plan_chunk_windows; a streamed
+// file's window is grown when it consumed nothing), the chunk arrays, keys
+// and digests are kept, and one confirm and one sharing pass run over all of
+// them. The same report as similarity_report whenever that one can run.
+SimilarityReport similarity_report_streamed(Engine& engine, Library& db, const Location& location,
+                                            const std::string& sub = "", uint64_t window_bytes = 256ull << 20);
 
 }  // namespace sdcore

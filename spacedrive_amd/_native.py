@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "sdcas_dev_tree_top",  # added after ABI 7
     "sdcas_chunk_plan", "sdcas_chunk_messages", "sdcas_dev_chunk", "sdcas_chunk_sharing",
     "sdcas_dev_chunk_sharing",  # added after ABI 7
+    "sdcas_chunk_seg_bytes", "sdcas_chunk_windows", "sdcas_dev_chunk_windows",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -251,6 +252,12 @@ def load():
                                        _vp, ctypes.POINTER(ChunkCounts)]
     L.sdcas_dev_chunk.argtypes = [_vp, _vp, _vp, _vp, _sz, ctypes.POINTER(ChunkParams), _u64, _u64, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _vp, _vp]
+    L.sdcas_chunk_seg_bytes.argtypes = [ctypes.POINTER(ChunkParams)]
+    L.sdcas_chunk_seg_bytes.restype = _u64
+    L.sdcas_chunk_windows.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, ctypes.POINTER(ChunkParams), _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, ctypes.POINTER(ChunkCounts)]
+    L.sdcas_dev_chunk_windows.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, ctypes.POINTER(ChunkParams), _u64, _u64, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.sdcas_chunk_sharing.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
                                       ctypes.POINTER(SharingCounts)]
     L.sdcas_dev_chunk_sharing.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]

@@ -35,7 +35,7 @@ CdcPlanError cdc_plan(const uint64_t* lens, size_t n, const CdcParams& p, uint64
 // byte offsets from its start, each 16-byte aligned
 struct CdcLayout {
   uint64_t sb, tb, mcb, fcnt;  // u32[n + 1] each: slot, tile, chunk-bound and chunk bases (exclusive scans)
-  uint64_t counts;             // u64[8]: the six counts, [6] spare, [7] a bound was hit (never, with a true plan)
+  uint64_t counts;             // u64[8]: the six counts, [6] spare (a windows call: the windows not final), [7] a bound was hit (never, with a true plan)
   uint64_t ends;               // u64[max_chunks]: the cut pass's ends, file i's at mcb[i]
   uint64_t woff, wlen, po;     // u64[max_chunks] each: the chunks' blob offsets, lengths, packed offsets
   uint64_t bitmap;             // 256 B per slot: per 128 positions LOOSE (16 B) then STRICT (16 B)
@@ -64,6 +64,44 @@ hipError_t cdc_chunk(const CdcLayout& l, const CdcArgs& a, hipStream_t st);
 // 16 from 0 within the batch, total_bytes their padded sum).
 hipError_t cdc_pack(const CdcLayout& l, const CdcArgs& a, uint64_t c0, uint32_t nb, uint64_t total_bytes,
                     uint8_t* scratch, hipStream_t st);
+
+// ---- windows: chains that start at any cut and stop where they cannot decide ---------
+// (include/sdcas.h "chunk windows")
+constexpr uint64_t kCdcSegDefault = 1ull << 20;
+// the segment length of the cut pass: what was asked for (0: the default), not
+// below 2 * max_len, rounded up to a multiple of 64
+inline uint64_t cdc_seg_bytes(const CdcParams& p, uint64_t asked) {
+  uint64_t x = asked ? asked : kCdcSegDefault;
+  if (x > (1ull << 62)) x = 1ull << 62;
+  if (x < 2ull * p.max_len) x = 2ull * p.max_len;
+  return (x + 63) & ~63ull;
+}
+// A window of 2 * seg bytes or more is cut segment by segment. Its segments
+// number ceil(len / seg) <= len / seg + 1 <= 1.5 * len / seg, so that all the
+// segments of a call number at most 1.5 * (1024 * file_slots) / seg; a
+// segment's list holds at most ceil(seg / min_len) cuts (the cuts below the
+// segment's end lie min_len apart from seg_start + min_len on, and one more
+// reaches the end).
+struct CdcWinLayout {
+  CdcLayout l;
+  uint64_t gb;        // u32[n + 1]: the files' first segments (exclusive scan of their segment counts)
+  uint64_t scnt;      // u32[max_segs]: the cuts in a segment's speculative list
+  uint64_t srec;      // uint4[max_segs]: the stitch's record of a segment (k_cdc_stitch)
+  uint64_t spec;      // u64[max_segs * spl]: the lists, a cut's kind in its bits 62..63
+  uint64_t max_segs;  // 0: no window of this call can be segmented
+  uint64_t spl;       // entries per list
+  uint64_t bytes;
+};
+CdcWinLayout cdc_win_layout(uint64_t n, uint64_t max_chunks, uint64_t file_slots, const CdcParams& p, uint64_t seg);
+
+struct CdcWinArgs {
+  const uint8_t* final;  // u8[n], null: every window is final
+  uint64_t* consumed;    // u64[n] or null
+  uint64_t seg;
+};
+// cdc_chunk for windows: the same launches but for the cut pass, which is
+// k_cdc_cut_seg, k_cdc_stitch and k_cdc_gather. ws + w.l.counts etc. as there.
+hipError_t cdc_chunk_windows(const CdcWinLayout& w, const CdcArgs& a, const CdcWinArgs& wa, hipStream_t st);
 
 // ---- sharing -------------------------------------------------------------------------
 inline uint64_t cdc_share_cap(uint64_t m) {

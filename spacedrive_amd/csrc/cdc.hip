@@ -22,6 +22,13 @@
 //                 chunk_file (and the copies the pack and the host plan read)
 //   k_cdc_pack    a batch's chunks copied to 16-byte aligned places for the
 //                 batch hash (cut points fall on any byte)
+// windows (a file chunked piece by piece, a long piece cut by many waves;
+// DESIGN.md §3.6), in place of k_cdc_cut:
+//   k_cdc_cut_seg one wave per segment: the chain from the segment's start
+//   k_cdc_cut_win one wave per window below two segments: the whole chain
+//   k_cdc_stitch  one wave per longer window: the true chain, walked only
+//                 until it lands on a cut of the segment's own chain
+//   k_cdc_gather  the cuts taken from the segments' lists, to their places
 // sharing:
 //   k_cs_accum    per chunk: new / self / other bytes of its file and, for a
 //                 chunk first seen in another file, the bytes added to the
@@ -399,6 +406,424 @@ hipError_t cdc_pack(const CdcLayout& l, const CdcArgs& a, uint64_t c0, uint32_t 
   hipLaunchKernelGGL(k_cdc_pack, dim3(blocks_of(units, 256 * kPackPer)), dim3(256), 0, st, a.blob,
                      at<const uint64_t>(a.ws, l.woff) + c0, at<const uint64_t>(a.ws, l.po) + c0, nb, units,
                      reinterpret_cast<uint4*>(scratch));
+  return hipGetLastError();
+}
+
+// ---- windows ---------------------------------------------------------------------------
+// A window begins at a cut of its file and, unless it is final, ends before the
+// file does: its chain stops where the bytes it holds cannot decide the next
+// cut. A window of 2 * seg bytes or more is cut by one wave per segment of seg
+// bytes, each running the chain from its segment's start (the chain from a
+// position is a function of that position alone), and stitched by one wave
+// per file, which walks the true chain only until it lands on a cut the
+// segment's wave made too.
+//   k_cdc_cut_seg one wave per (file, segment): the cuts from the segment's
+//                 start up to and including the first at or past its end, into
+//                 the segment's own list, each with its kind
+//   k_cdc_cut_win one wave per window without segments: k_cdc_cut's chain
+//                 with the stop rule, into ends
+//   k_cdc_stitch  one wave per window with segments (the wave of its first
+//                 segment's slot). Segment by segment, from the true entry cut
+//                 c: c at the segment's start takes the whole list; otherwise
+//                 the chain is walked from c (its cuts go straight into ends)
+//                 until a cut equals a listed one, whose followers are then
+//                 taken, or until the segment's end. Writes per segment where
+//                 its chunks begin in the file, the walked cuts, the merge
+//                 index and the cuts taken from the list
+//   k_cdc_gather  one wave per segment: the cuts taken from its list, to
+//                 their places in ends; their kinds are counted
+// The wave that stitches a file goes over its segments in order, so the running
+// chunk count is the scan of the segments' counts. The true entry cut of
+// segment j + 1 is below (j + 1) * seg + max_len, and seg >= 2 * max_len, so
+// the chain never jumps a whole segment; k_cdc_stitch takes s / seg all the
+// same and leaves a jumped segment's record at zero.
+
+CdcWinLayout cdc_win_layout(uint64_t n, uint64_t max_chunks, uint64_t file_slots, const CdcParams& p, uint64_t seg) {
+  CdcWinLayout w{};
+  w.l = cdc_layout(n, max_chunks, file_slots);
+  const uint64_t bound = (uint64_t)kCdcSlot * file_slots;  // the bytes of all windows, each rounded up to a slot
+  w.max_segs = bound >= 2 * seg ? 3 * bound / (2 * seg) + 1 : 0;
+  w.spl = w.max_segs ? seg / p.min_len + (seg % p.min_len != 0) : 0;
+  uint64_t o = w.l.bytes;
+  auto take = [&o](uint64_t bytes) {
+    const uint64_t at = o;
+    o += (bytes + 15) & ~15ull;
+    return at;
+  };
+  w.gb = take(4 * (n + 1));
+  w.scnt = take(4 * w.max_segs);
+  w.srec = take(16 * w.max_segs);
+  w.spec = take(8 * w.max_segs * w.spl);
+  w.bytes = o;
+  return w;
+}
+
+namespace {
+
+constexpr uint32_t kStepHash = 0, kStepMax = 1, kStepEnd = 2, kStepStop = 3;  // the first three in counts[3..5]'s order
+constexpr uint64_t kCutMask = (1ull << 62) - 1;                                 // a listed cut without its kind
+
+// k_cdc_sizes and the windows' segment counts in one launch
+__global__ void __launch_bounds__(256) k_cdc_win_sizes(const uint64_t* __restrict__ lens, uint32_t n, uint32_t min_len,
+                                                       uint64_t seg, uint32_t* __restrict__ sb,
+                                                       uint32_t* __restrict__ tb, uint32_t* __restrict__ mcb,
+                                                       uint32_t* __restrict__ gb) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t len = lens[i];
+  sb[i] = cdc_ceil_u32(len, kCdcSlot);
+  tb[i] = cdc_ceil_u32(len, kCdcTile);
+  mcb[i] = cdc_ceil_u32(len, min_len);
+  const uint64_t q = len / seg + (len % seg != 0);
+  gb[i] = len < 2 * seg ? 0u : q > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)q;
+}
+
+// k_cdc_scan over four arrays
+__global__ void __launch_bounds__(1024) k_cdc_win_scan(uint32_t* __restrict__ a0, uint32_t* __restrict__ a1,
+                                                        uint32_t* __restrict__ a2, uint32_t* __restrict__ a3,
+                                                        uint32_t n) {
+  uint32_t* a = blockIdx.x == 0 ? a0 : blockIdx.x == 1 ? a1 : blockIdx.x == 2 ? a2 : a3;
+  wg_scan_exclusive_1024(a, n, a + n);
+}
+
+struct CdcChain {
+  const uint64_t* __restrict__ bitmap;
+  uint64_t ubase, cap_units, L, avg;
+  uint32_t min_len, max_len;
+  bool fin;
+};
+
+// The cut after s (< L), by every lane of one wave: k_cdc_cut's step with the
+// stop rule of a window that is not final. -> the kind; *out_e the cut unless
+// the kind is kStepStop.
+__device__ __forceinline__ uint32_t cdc_step(const CdcChain& c, uint64_t s, uint32_t lane, uint64_t* out_e) {
+  const uint64_t left = c.L - s;
+  *out_e = c.L;
+  if (c.fin ? left <= c.min_len : left < c.min_len) return c.fin ? kStepEnd : kStepStop;
+  const uint64_t hi = s + c.max_len < c.L ? s + c.max_len : c.L;
+  // candidate positions q = e - 1 in [q_lo, hi): STRICT below q_mid, LOOSE from there on
+  const uint64_t q_lo = s + c.min_len - 1, q_mid = s + c.avg - 1;
+  const uint64_t strict_to = q_mid < hi ? q_mid : hi;
+  for (uint64_t w0 = q_lo / 64; 64 * w0 < hi; w0 += 64) {
+    const uint64_t w = w0 + lane;
+    uint64_t word = 0;
+    const uint64_t unit = c.ubase + w / 2;
+    if (64 * w < hi && unit < c.cap_units) {
+      const uint64_t* p = c.bitmap + 4 * unit + (w & 1);
+      word = (p[2] & cdc_range(w, q_lo, strict_to)) | (p[0] & cdc_range(w, q_mid, hi));
+    }
+    const uint64_t any = __ballot(word != 0);
+    if (any) {
+      // (the ballot is the same in every lane: the winner's word comes down a scalar path)
+      const uint32_t first = (uint32_t)__builtin_ctzll(any);
+      const uint32_t wl = __builtin_amdgcn_readlane((uint32_t)word, first);
+      const uint32_t wh = __builtin_amdgcn_readlane((uint32_t)(word >> 32), first);
+      const uint64_t hit = (uint64_t)wh << 32 | wl;
+      const uint64_t e = 64 * (w0 + first) + (uint32_t)__builtin_ctzll(hit) + 1;
+      *out_e = e;
+      return c.fin && e == c.L ? kStepEnd : kStepHash;
+    }
+  }
+  if (s + c.max_len <= c.L) {
+    *out_e = s + c.max_len;
+    return c.fin && s + c.max_len == c.L ? kStepEnd : kStepMax;
+  }
+  return c.fin ? kStepEnd : kStepStop;  // the window ends before max_len does
+}
+
+struct CdcWinParams {
+  uint32_t min_len, avg_bits, max_len;
+  uint64_t seg, max_segs, spl, cap_units, max_chunks;
+};
+
+__device__ __forceinline__ CdcChain cdc_chain_of(const CdcWinParams& p, const uint64_t* __restrict__ bitmap,
+                                                 const uint32_t* __restrict__ sb, const uint64_t* __restrict__ lens,
+                                                 const uint8_t* __restrict__ final, uint32_t i) {
+  return CdcChain{bitmap, (uint64_t)kUnitsPerSlot * sb[i], p.cap_units, lens[i], 1ull << p.avg_bits,
+                  p.min_len, p.max_len, final ? final[i] != 0 : true};
+}
+
+__global__ void __launch_bounds__(kCutTB) k_cdc_cut_seg(const uint64_t* __restrict__ lens,
+                                                        const uint8_t* __restrict__ final, uint32_t n,
+                                                        const uint32_t* __restrict__ sb,
+                                                        const uint32_t* __restrict__ gb,
+                                                        const uint64_t* __restrict__ bitmap, CdcWinParams p,
+                                                        uint64_t* __restrict__ spec, uint32_t* __restrict__ scnt,
+                                                        uint4* __restrict__ srec,
+                                                        unsigned long long* __restrict__ counts) {
+  const uint64_t g = (uint64_t)blockIdx.x * (kCutTB / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t segs = gb[n] < p.max_segs ? gb[n] : p.max_segs;
+  if (g >= segs) return;  // the same for the whole wave
+  const uint32_t i = cdc_owner(gb, n, (uint32_t)g);
+  const CdcChain c = cdc_chain_of(p, bitmap, sb, lens, final, i);
+  uint64_t s = (g - gb[i]) * p.seg;
+  const uint64_t limit = s + p.seg;
+  uint64_t* __restrict__ list = spec + g * p.spl;
+  uint32_t cnt = 0;
+  while (s < c.L) {
+    uint64_t e;
+    const uint32_t kind = cdc_step(c, s, lane, &e);
+    if (kind == kStepStop) break;
+    if (cnt >= p.spl) {  // never: a list holds ceil(seg / min_len) cuts
+      if (lane == 0) atomicOr(&counts[7], 1ull);
+      break;
+    }
+    if (lane == 0) list[cnt] = e | (uint64_t)kind << 62;
+    ++cnt;
+    s = e;
+    if (e >= limit) break;
+  }
+  if (lane == 0) {
+    scnt[g] = cnt;
+    srec[g] = make_uint4(0, 0, 0, 0);
+  }
+}
+
+// what a window's wave leaves behind (lane 0) and the workgroup's sums
+struct CdcWinSums {
+  unsigned long long bytes;
+  uint32_t kind[3], open;  // open: the windows that are not final
+};
+__device__ __forceinline__ void cdc_window_done(const CdcChain& c, uint32_t i, uint64_t s, uint32_t cnt, bool bad,
+                                                uint32_t n_hash, uint32_t n_max, uint32_t n_end,
+                                                uint32_t* __restrict__ fcnt, uint64_t* __restrict__ consumed,
+                                                unsigned long long* __restrict__ counts, CdcWinSums* sums) {
+  const uint64_t used = c.fin ? c.L : s;
+  fcnt[i] = cnt;
+  if (consumed) consumed[i] = used;
+  if (bad || (c.fin && s < c.L)) atomicOr(&counts[7], 1ull);  // never: a window has at most ceil(L / min_len) chunks
+  atomicAdd(&sums->bytes, (unsigned long long)used);
+  if (!c.fin) atomicAdd(&sums->open, 1u);
+  if (n_hash) atomicAdd(&sums->kind[kStepHash], n_hash);
+  if (n_max) atomicAdd(&sums->kind[kStepMax], n_max);
+  if (n_end) atomicAdd(&sums->kind[kStepEnd], n_end);
+}
+__device__ __forceinline__ void cdc_sums_clear(CdcWinSums* sums) {
+  if (threadIdx.x == 0) sums->bytes = 0, sums->open = 0;
+  if (threadIdx.x < 3) sums->kind[threadIdx.x] = 0;
+  __syncthreads();
+}
+__device__ __forceinline__ void cdc_sums_add(const CdcWinSums* sums, unsigned long long* __restrict__ counts) {
+  __syncthreads();
+  if (threadIdx.x == 0 && sums->bytes) atomicAdd(&counts[2], sums->bytes);
+  // (every add here goes to one word of all workgroups: the windows that are not final are counted, which
+  // are none in a call over whole files, so that such a call adds to the words k_cdc_cut adds to and no more)
+  if (threadIdx.x == 0 && sums->open) atomicAdd(&counts[6], (unsigned long long)sums->open);
+  if (threadIdx.x < 3 && sums->kind[threadIdx.x]) atomicAdd(&counts[3 + threadIdx.x], (unsigned long long)sums->kind[threadIdx.x]);
+}
+
+// a window without segments: k_cdc_cut's one-wave chain with the stop rule
+__global__ void __launch_bounds__(kCutTB) k_cdc_cut_win(const uint64_t* __restrict__ lens,
+                                                        const uint8_t* __restrict__ final, uint32_t n,
+                                                        const uint32_t* __restrict__ sb,
+                                                        const uint32_t* __restrict__ mcb,
+                                                        const uint32_t* __restrict__ gb,
+                                                        const uint64_t* __restrict__ bitmap, CdcWinParams p,
+                                                        uint64_t* __restrict__ ends, uint32_t* __restrict__ fcnt,
+                                                        uint64_t* __restrict__ consumed,
+                                                        unsigned long long* __restrict__ counts) {
+  __shared__ CdcWinSums sums;
+  cdc_sums_clear(&sums);
+  const uint32_t i = blockIdx.x * (kCutTB / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i < n && gb[i + 1] == gb[i]) {  // the same for the whole wave
+    const CdcChain c = cdc_chain_of(p, bitmap, sb, lens, final, i);
+    const uint64_t base = mcb[i];
+    uint64_t room = mcb[i + 1] - base;
+    if (base + room > p.max_chunks) room = base < p.max_chunks ? p.max_chunks - base : 0;  // never, with a true plan
+    uint32_t cnt = 0, n_hash = 0, n_max = 0, n_end = 0;
+    uint64_t s = 0;
+    bool bad = false;
+    while (s < c.L) {
+      uint64_t e;
+      const uint32_t kind = cdc_step(c, s, lane, &e);
+      if (kind == kStepStop) break;
+      if (cnt >= room) {
+        bad = true;
+        break;
+      }
+      if (lane == 0) ends[base + cnt] = e;
+      if (kind == kStepHash) ++n_hash; else if (kind == kStepMax) ++n_max; else ++n_end;
+      ++cnt;
+      s = e;
+    }
+    if (lane == 0) cdc_window_done(c, i, s, cnt, bad, n_hash, n_max, n_end, fcnt, consumed, counts, &sums);
+  } else if (i < n && gb[i + 1] > p.max_segs && lane == 0) {
+    // never, with a true plan: segments past the workspace's, which no wave stitches
+    fcnt[i] = 0;
+    if (consumed) consumed[i] = 0;
+    atomicOr(&counts[7], 1ull);
+  }
+  cdc_sums_add(&sums, counts);
+}
+
+// a window with segments: the wave of its first segment's slot stitches it
+__global__ void __launch_bounds__(kCutTB) k_cdc_stitch(const uint64_t* __restrict__ lens,
+                                                       const uint8_t* __restrict__ final, uint32_t n,
+                                                       const uint32_t* __restrict__ sb,
+                                                       const uint32_t* __restrict__ mcb,
+                                                       const uint32_t* __restrict__ gb,
+                                                       const uint64_t* __restrict__ bitmap, CdcWinParams p,
+                                                       const uint64_t* __restrict__ spec,
+                                                       const uint32_t* __restrict__ scnt, uint4* __restrict__ srec,
+                                                       uint64_t* __restrict__ ends, uint32_t* __restrict__ fcnt,
+                                                       uint64_t* __restrict__ consumed,
+                                                       unsigned long long* __restrict__ counts) {
+  __shared__ CdcWinSums sums;
+  cdc_sums_clear(&sums);
+  const uint64_t g0 = (uint64_t)blockIdx.x * (kCutTB / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t segs = gb[n] < p.max_segs ? gb[n] : p.max_segs;
+  const uint32_t i = g0 < segs ? cdc_owner(gb, n, (uint32_t)g0) : 0u;
+  if (g0 < segs && gb[i] == g0 && gb[i + 1] <= p.max_segs) {  // the same for the whole wave
+    const CdcChain c = cdc_chain_of(p, bitmap, sb, lens, final, i);
+    const uint64_t base = mcb[i];
+    uint64_t room = mcb[i + 1] - base;
+    if (base + room > p.max_chunks) room = base < p.max_chunks ? p.max_chunks - base : 0;  // never, with a true plan
+    uint32_t cnt = 0, n_hash = 0, n_max = 0, n_end = 0;
+    uint64_t s = 0;
+    bool bad = false;
+    while (s < c.L && !bad) {
+      const uint64_t j = s / p.seg;
+      const uint64_t g = g0 + j, limit = (j + 1) * p.seg;
+      if (g >= segs) {  // never, with a true plan
+        bad = true;
+        break;
+      }
+      const uint64_t* __restrict__ list = spec + g * p.spl;
+      const uint32_t sc = scnt[g] < p.spl ? scnt[g] : (uint32_t)p.spl;
+      const uint32_t start = cnt;
+      uint32_t walk = 0, merge = 0, take = 0;
+      bool stopped = false;
+      if (s == j * p.seg) {
+        take = sc;  // the segment's wave began where the true chain enters
+      } else {
+        uint32_t k = 0;
+        for (;;) {
+          uint64_t e;
+          const uint32_t kind = cdc_step(c, s, lane, &e);
+          if (kind == kStepStop) {
+            stopped = true;
+            break;
+          }
+          if (cnt >= room) {
+            bad = true;
+            break;
+          }
+          if (lane == 0) ends[base + cnt] = e;
+          if (kind == kStepHash) ++n_hash; else if (kind == kStepMax) ++n_max; else ++n_end;
+          ++cnt, ++walk;
+          s = e;
+          while (k < sc && (list[k] & kCutMask) < e) ++k;
+          if (k < sc && (list[k] & kCutMask) == e) {  // from here on the list is the true chain
+            merge = k + 1, take = sc - merge;
+            break;
+          }
+          if (e >= limit) break;
+        }
+      }
+      if (take > room - cnt) take = (uint32_t)(room - cnt), bad = true;
+      if (take) s = list[merge + take - 1] & kCutMask, cnt += take;
+      if (lane == 0) srec[g] = make_uint4(start, walk, merge, take);
+      if (stopped || s < limit) break;  // the chain stopped, or ended, inside this segment
+    }
+    if (lane == 0) cdc_window_done(c, i, s, cnt, bad, n_hash, n_max, n_end, fcnt, consumed, counts, &sums);
+  }
+  cdc_sums_add(&sums, counts);
+}
+
+__global__ void __launch_bounds__(kCutTB) k_cdc_gather(uint32_t n, const uint32_t* __restrict__ mcb,
+                                                       const uint32_t* __restrict__ gb, CdcWinParams p,
+                                                       const uint64_t* __restrict__ spec,
+                                                       const uint4* __restrict__ srec, uint64_t* __restrict__ ends,
+                                                       unsigned long long* __restrict__ counts) {
+  __shared__ uint32_t s_kind[3];
+  if (threadIdx.x < 3) s_kind[threadIdx.x] = 0;
+  __syncthreads();
+  const uint64_t g = (uint64_t)blockIdx.x * (kCutTB / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t segs = gb[n] < p.max_segs ? gb[n] : p.max_segs;
+  if (g < segs) {  // the same for the whole wave
+    const uint4 rec = srec[g];  // start, walk, merge, take
+    if (rec.w) {
+      const uint32_t i = cdc_owner(gb, n, (uint32_t)g);
+      const uint64_t base = mcb[i];
+      uint64_t room = mcb[i + 1] - base;
+      if (base + room > p.max_chunks) room = base < p.max_chunks ? p.max_chunks - base : 0;
+      const uint64_t first = (uint64_t)rec.x + rec.y;  // the segment's taken cuts follow its walked ones
+      uint32_t kinds[3] = {0, 0, 0};
+      for (uint32_t k0 = 0; k0 < rec.w; k0 += 64) {
+        const uint32_t k = k0 + lane;
+        uint32_t kind = kStepStop;
+        if (k < rec.w && (uint64_t)rec.z + k < p.spl && first + k < room) {
+          const uint64_t v = spec[g * p.spl + rec.z + k];
+          ends[base + first + k] = v & kCutMask;
+          kind = (uint32_t)(v >> 62);
+        }
+#pragma unroll
+        for (uint32_t t = 0; t < 3; ++t) kinds[t] += (uint32_t)__popcll(__ballot(kind == t));
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (uint32_t t = 0; t < 3; ++t)
+          if (kinds[t]) atomicAdd(&s_kind[t], kinds[t]);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && s_kind[threadIdx.x]) atomicAdd(&counts[3 + threadIdx.x], (unsigned long long)s_kind[threadIdx.x]);
+}
+
+// after k_cdc_emit, which counts every entry as a file: `files` counts the final windows
+__global__ void k_cdc_win_finish(uint32_t n, unsigned long long* __restrict__ counts) { counts[0] = n - counts[6]; }
+
+}  // namespace
+
+hipError_t cdc_chunk_windows(const CdcWinLayout& w, const CdcArgs& a, const CdcWinArgs& wa, hipStream_t st) {
+  const CdcLayout& l = w.l;
+  const uint32_t n = a.n;
+  uint32_t* sb = at<uint32_t>(a.ws, l.sb);
+  uint32_t* tb = at<uint32_t>(a.ws, l.tb);
+  uint32_t* mcb = at<uint32_t>(a.ws, l.mcb);
+  uint32_t* fcnt = at<uint32_t>(a.ws, l.fcnt);
+  uint32_t* gb = at<uint32_t>(a.ws, w.gb);
+  uint32_t* scnt = at<uint32_t>(a.ws, w.scnt);
+  uint4* srec = at<uint4>(a.ws, w.srec);
+  uint64_t* spec = at<uint64_t>(a.ws, w.spec);
+  unsigned long long* counts = at<unsigned long long>(a.ws, l.counts);
+  const uint64_t* bitmap = at<const uint64_t>(a.ws, l.bitmap);
+  const uint64_t cap_units = (uint64_t)kUnitsPerSlot * a.file_slots;
+  const CdcWinParams p{a.p.min_len, a.p.avg_bits, a.p.max_len, wa.seg, w.max_segs, w.spl, cap_units, a.max_chunks};
+  hipError_t e;
+  if ((e = hipMemsetAsync(counts, 0, 64, st))) return e;
+  hipLaunchKernelGGL(k_cdc_win_sizes, dim3(blocks_of(n, 256)), dim3(256), 0, st, a.lens, n, a.p.min_len, wa.seg, sb, tb,
+                     mcb, gb);
+  hipLaunchKernelGGL(k_cdc_win_scan, dim3(4), dim3(1024), 0, st, sb, tb, mcb, gb, n);
+  const uint64_t tiles_bound = a.file_slots / (kCdcTile / kCdcSlot) + n;
+  const uint32_t gear_grid = (uint32_t)(tiles_bound < 8192 ? (tiles_bound ? tiles_bound : 1) : 8192);
+  hipLaunchKernelGGL(k_cdc_gear, dim3(gear_grid), dim3(kCdcTB), 0, st, a.blob, a.offs, a.lens, n, (const uint32_t*)tb,
+                     (const uint32_t*)sb, cap_units, 1u << (33 - a.p.avg_bits), 1u << (31 - a.p.avg_bits),
+                     at<uint4>(a.ws, l.bitmap));
+  const dim3 seg_grid(blocks_of(w.max_segs * 64, kCutTB));
+  if (w.max_segs)
+    hipLaunchKernelGGL(k_cdc_cut_seg, seg_grid, dim3(kCutTB), 0, st, a.lens, wa.final, n, (const uint32_t*)sb,
+                       (const uint32_t*)gb, bitmap, p, spec, scnt, srec, counts);
+  hipLaunchKernelGGL(k_cdc_cut_win, dim3(blocks_of((uint64_t)n * 64, kCutTB)), dim3(kCutTB), 0, st, a.lens, wa.final, n,
+                     (const uint32_t*)sb, (const uint32_t*)mcb, (const uint32_t*)gb, bitmap, p,
+                     at<uint64_t>(a.ws, l.ends), fcnt, wa.consumed, counts);
+  if (w.max_segs)
+    hipLaunchKernelGGL(k_cdc_stitch, seg_grid, dim3(kCutTB), 0, st, a.lens, wa.final, n, (const uint32_t*)sb,
+                       (const uint32_t*)mcb, (const uint32_t*)gb, bitmap, p, (const uint64_t*)spec,
+                       (const uint32_t*)scnt, srec, at<uint64_t>(a.ws, l.ends), fcnt, wa.consumed, counts);
+  if (w.max_segs)
+    hipLaunchKernelGGL(k_cdc_gather, seg_grid, dim3(kCutTB), 0, st, n, (const uint32_t*)mcb, (const uint32_t*)gb, p,
+                       (const uint64_t*)spec, (const uint4*)srec, at<uint64_t>(a.ws, l.ends), counts);
+  hipLaunchKernelGGL(k_cdc_scan, dim3(1), dim3(1024), 0, st, fcnt, fcnt, fcnt, n);
+  const uint64_t slots = a.max_chunks > (uint64_t)n + 1 ? a.max_chunks : (uint64_t)n + 1;
+  hipLaunchKernelGGL(k_cdc_emit, dim3(blocks_of(slots, 256)), dim3(256), 0, st, a.offs, n, (const uint32_t*)mcb,
+                     (const uint32_t*)fcnt, at<const uint64_t>(a.ws, l.ends), a.max_chunks, at<uint64_t>(a.ws, l.woff),
+                     at<uint64_t>(a.ws, l.wlen), a.file_chunks, a.chunk_off, a.chunk_len, a.chunk_file, counts);
+  hipLaunchKernelGGL(k_cdc_win_finish, dim3(1), dim3(1), 0, st, n, counts);
   return hipGetLastError();
 }
 

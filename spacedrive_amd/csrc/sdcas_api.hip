@@ -2362,17 +2362,24 @@ static uint64_t chunk_pack_cap() {
 
 // Enqueue the whole of a chunk call on st (device arrays, valid parameters,
 // n != 0); waits for st once when keys or digests are asked for.
+// win: the call is over windows (sdcas_dev_chunk_windows), cut in segments.
 static int chunk_enqueue(sdcas_ctx* c, const char* who, CdcArgs a, uint64_t* d_keys, uint8_t* d_digests32,
-                         uint64_t* d_counts, hipStream_t st) {
-  const CdcLayout l = cdc_layout(a.n, a.max_chunks, a.file_slots);
+                         uint64_t* d_counts, hipStream_t st, const CdcWinArgs* win = nullptr) {
+  CdcWinLayout w{};
+  if (win) {
+    w = cdc_win_layout(a.n, a.max_chunks, a.file_slots, a.p, win->seg);
+    if (w.max_segs > 0xFFFFFFFEull) return c->fail(SDCAS_E_CAPACITY, "%s: more than 2^32 segments", who);
+  }
+  const CdcLayout l = win ? w.l : cdc_layout(a.n, a.max_chunks, a.file_slots);
+  const uint64_t ws_bytes = win ? w.bytes : l.bytes;
   hipError_t e;
-  if (l.bytes > c->cd_ws.cap) {
+  if (ws_bytes > c->cd_ws.cap) {
     // an earlier call's kernels may still use what is about to be freed
-    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->cd_ws.ensure(l.bytes)))
+    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->cd_ws.ensure(ws_bytes)))
       return c->hip_fail(e, "chunk workspace");
   }
   a.ws = c->cd_ws.p;
-  if ((e = cdc_chunk(l, a, st))) return c->hip_fail(e, who);
+  if ((e = win ? cdc_chunk_windows(w, a, *win, st) : cdc_chunk(l, a, st))) return c->hip_fail(e, who);
   if (d_counts &&
       (e = hipMemcpyAsync(d_counts, a.ws + l.counts, kCdcCounts * sizeof(uint64_t), hipMemcpyDeviceToDevice, st)))
     return c->hip_fail(e, who);
@@ -2473,18 +2480,32 @@ int sdcas_dev_chunk(sdcas_ctx* c, const uint8_t* d_blob, const uint64_t* d_offse
                        d_keys, d_digests32, d_counts, call.st);
 }
 
-int sdcas_chunk_messages(sdcas_ctx* c, const uint8_t* blob, const uint64_t* offsets, const uint64_t* lens, size_t n,
-                         const sdcas_chunk_params* params, uint64_t* out_file_chunks, uint64_t* out_chunk_off,
-                         uint64_t* out_chunk_len, uint32_t* out_chunk_file, uint64_t* out_keys, uint8_t* out_digests32,
-                         sdcas_chunk_counts* out_counts) {
+// the segment length of a windows call (SDCAS_CHUNK_SEG_BYTES, read per call)
+static uint64_t chunk_seg(const CdcParams& p) {
+  const char* v = getenv("SDCAS_CHUNK_SEG_BYTES");
+  return cdc_seg_bytes(p, v ? strtoull(v, nullptr, 10) : 0);
+}
+
+uint64_t sdcas_chunk_seg_bytes(const sdcas_chunk_params* params) {
+  const CdcParams p = chunk_params(params);
+  return cdc_params_valid(p) ? chunk_seg(p) : 0;
+}
+
+// sdcas_chunk_messages (windows false: final and out_consumed are null) and
+// sdcas_chunk_windows over host arrays
+static int chunk_host(sdcas_ctx* c, const char* who, bool windows, const uint8_t* blob, const uint64_t* offsets,
+                      const uint64_t* lens, const uint8_t* final, size_t n, const sdcas_chunk_params* params,
+                      uint64_t* out_file_chunks, uint64_t* out_chunk_off, uint64_t* out_chunk_len,
+                      uint32_t* out_chunk_file, uint64_t* out_keys, uint8_t* out_digests32, uint64_t* out_consumed,
+                      sdcas_chunk_counts* out_counts) {
   static_assert(sizeof(sdcas_chunk_counts) == kCdcCounts * sizeof(uint64_t), "six u64 counts");
   if (!c) return SDCAS_E_INVALID;
   const CdcParams p = chunk_params(params);
-  if (!cdc_params_valid(p)) return c->fail(SDCAS_E_INVALID, "chunk_messages: invalid chunk parameters");
-  if (n && (!offsets || !lens)) return c->fail(SDCAS_E_INVALID, "chunk_messages: null offsets or lens");
+  if (!cdc_params_valid(p)) return c->fail(SDCAS_E_INVALID, "%s: invalid chunk parameters", who);
+  if (n && (!offsets || !lens)) return c->fail(SDCAS_E_INVALID, "%s: null offsets or lens", who);
   uint64_t max_chunks = 0, max_slots = 0, slots = 0;
   if (cdc_plan(lens, n, p, &max_chunks, &max_slots) != kCdcOk)
-    return c->fail(SDCAS_E_CAPACITY, "chunk_messages: more than 2^30 chunks");
+    return c->fail(SDCAS_E_CAPACITY, "%s: more than 2^30 chunks", who);
   // every file at a 16-byte aligned place of the device copy, 64 readable bytes behind it
   std::vector<uint64_t> at(n);
   uint64_t bytes = 0, content = 0;
@@ -2493,8 +2514,8 @@ int sdcas_chunk_messages(sdcas_ctx* c, const uint8_t* blob, const uint64_t* offs
     bytes += (lens[i] + kSlack + 15) & ~15ull;
     content += lens[i];
   }
-  if (content && !blob) return c->fail(SDCAS_E_INVALID, "chunk_messages: null blob");
-  if (int rc = chunk_args(c, "chunk_messages", offsets, lens, n, p, max_chunks, max_slots, &slots)) return rc;
+  if (content && !blob) return c->fail(SDCAS_E_INVALID, "%s: null blob", who);
+  if (int rc = chunk_args(c, who, offsets, lens, n, p, max_chunks, max_slots, &slots)) return rc;
   if (out_counts) memset(out_counts, 0, sizeof *out_counts);
   if (n == 0) {
     if (out_file_chunks) out_file_chunks[0] = 0;
@@ -2508,10 +2529,11 @@ int sdcas_chunk_messages(sdcas_ctx* c, const uint8_t* blob, const uint64_t* offs
   const uint64_t mc = max_chunks;
   const uint64_t o_offs = bytes, o_lens = o_offs + 8 * n, o_fc = o_lens + 8 * n, o_off = o_fc + 8 * (n + 1),
                  o_len = o_off + 8 * mc, o_keys = o_len + 8 * mc, o_cts = o_keys + 8 * mc, o_dig = o_cts + 64,
-                 o_file = o_dig + 32 * mc, total = o_file + 4 * mc;
+                 o_file = o_dig + 32 * mc, o_cons = (o_file + 4 * mc + 7) & ~7ull, o_fin = o_cons + 8 * n,
+                 total = windows ? o_fin + n : o_file + 4 * mc;  // windows: | consumed | final
   if (total > c->cd_io.cap) {
     if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->cd_io.ensure(total)))
-      return c->hip_fail(e, "chunk_messages buffers");
+      return c->hip_fail(e, who);
   }
   uint8_t* io = c->cd_io.p;
   {
@@ -2522,9 +2544,12 @@ int sdcas_chunk_messages(sdcas_ctx* c, const uint8_t* blob, const uint64_t* offs
       if (lens[i]) memcpy(img.data() + at[i], blob + offsets[i], lens[i]);
       hoffs[i] = at[i], hoffs[n + i] = lens[i];
     }
-    if ((e = hipMemcpyAsync(io, img.data(), img.size(), hipMemcpyHostToDevice, st)) || (e = hipStreamSynchronize(st)))
-      return c->hip_fail(e, "chunk_messages H2D");
+    if ((e = hipMemcpyAsync(io, img.data(), img.size(), hipMemcpyHostToDevice, st)) ||
+        (final && (e = hipMemcpyAsync(io + o_fin, final, n, hipMemcpyHostToDevice, st))) ||
+        (e = hipStreamSynchronize(st)))
+      return c->hip_fail(e, who);
   }
+  const CdcWinArgs win{final ? io + o_fin : nullptr, reinterpret_cast<uint64_t*>(io + o_cons), windows ? chunk_seg(p) : 0};
   CdcArgs a{nullptr,
             io,
             reinterpret_cast<const uint64_t*>(io + o_offs),
@@ -2537,31 +2562,81 @@ int sdcas_chunk_messages(sdcas_ctx* c, const uint8_t* blob, const uint64_t* offs
             reinterpret_cast<uint64_t*>(io + o_off),
             reinterpret_cast<uint64_t*>(io + o_len),
             reinterpret_cast<uint32_t*>(io + o_file)};
-  if (int rc = chunk_enqueue(c, "chunk_messages", a, out_keys ? reinterpret_cast<uint64_t*>(io + o_keys) : nullptr,
-                             out_digests32 ? io + o_dig : nullptr, reinterpret_cast<uint64_t*>(io + o_cts), st))
+  if (int rc = chunk_enqueue(c, who, a, out_keys ? reinterpret_cast<uint64_t*>(io + o_keys) : nullptr,
+                             out_digests32 ? io + o_dig : nullptr, reinterpret_cast<uint64_t*>(io + o_cts), st,
+                             windows ? &win : nullptr))
     return rc;
   // the counts down first: they say how many entries of each array follow
   sdcas_chunk_counts cts;
   if ((e = hipMemcpyAsync(&cts, io + o_cts, sizeof cts, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
-    return c->hip_fail(e, "chunk_messages counts");
+    return c->hip_fail(e, who);
   const uint64_t m = cts.chunks;
-  if (m > mc) return c->fail(SDCAS_E_HIP, "chunk_messages: counts out of range");
+  if (m > mc) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
   std::vector<uint32_t> file(out_chunk_off ? m : 0);
   if ((out_file_chunks && (e = hipMemcpyAsync(out_file_chunks, io + o_fc, 8 * (n + 1), hipMemcpyDeviceToHost, st))) ||
+      (out_consumed && (e = hipMemcpyAsync(out_consumed, io + o_cons, 8 * n, hipMemcpyDeviceToHost, st))) ||
       (m && out_chunk_off && ((e = hipMemcpyAsync(out_chunk_off, io + o_off, 8 * m, hipMemcpyDeviceToHost, st)) ||
                               (e = hipMemcpyAsync(file.data(), io + o_file, 4 * m, hipMemcpyDeviceToHost, st)))) ||
       (m && out_chunk_len && (e = hipMemcpyAsync(out_chunk_len, io + o_len, 8 * m, hipMemcpyDeviceToHost, st))) ||
       (m && out_chunk_file && (e = hipMemcpyAsync(out_chunk_file, io + o_file, 4 * m, hipMemcpyDeviceToHost, st))) ||
       (m && out_keys && (e = hipMemcpyAsync(out_keys, io + o_keys, 8 * m, hipMemcpyDeviceToHost, st))) ||
       (m && out_digests32 && (e = hipMemcpyAsync(out_digests32, io + o_dig, 32 * m, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, "chunk_messages D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_messages sync");
+    return c->hip_fail(e, who);
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, who);
   // offsets in the caller's blob, not in the device copy
   if (out_chunk_off)
     for (uint64_t k = 0; k < m; ++k)
       if (file[k] < n) out_chunk_off[k] = out_chunk_off[k] - at[file[k]] + offsets[file[k]];
   if (out_counts) *out_counts = cts;
   return SDCAS_OK;
+}
+
+int sdcas_chunk_messages(sdcas_ctx* c, const uint8_t* blob, const uint64_t* offsets, const uint64_t* lens, size_t n,
+                         const sdcas_chunk_params* params, uint64_t* out_file_chunks, uint64_t* out_chunk_off,
+                         uint64_t* out_chunk_len, uint32_t* out_chunk_file, uint64_t* out_keys, uint8_t* out_digests32,
+                         sdcas_chunk_counts* out_counts) {
+  return chunk_host(c, "chunk_messages", false, blob, offsets, lens, nullptr, n, params, out_file_chunks, out_chunk_off,
+                    out_chunk_len, out_chunk_file, out_keys, out_digests32, nullptr, out_counts);
+}
+
+int sdcas_chunk_windows(sdcas_ctx* c, const uint8_t* blob, const uint64_t* offsets, const uint64_t* lens,
+                        const uint8_t* final, size_t n, const sdcas_chunk_params* params, uint64_t* out_file_chunks,
+                        uint64_t* out_chunk_off, uint64_t* out_chunk_len, uint32_t* out_chunk_file, uint64_t* out_keys,
+                        uint8_t* out_digests32, uint64_t* out_consumed, sdcas_chunk_counts* out_counts) {
+  return chunk_host(c, "chunk_windows", true, blob, offsets, lens, final, n, params, out_file_chunks, out_chunk_off,
+                    out_chunk_len, out_chunk_file, out_keys, out_digests32, out_consumed, out_counts);
+}
+
+int sdcas_dev_chunk_windows(sdcas_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, const uint64_t* d_lens,
+                            const uint8_t* d_final, size_t n, const sdcas_chunk_params* params, uint64_t max_chunks,
+                            uint64_t max_slots, uint64_t* d_file_chunks, uint64_t* d_chunk_off, uint64_t* d_chunk_len,
+                            uint32_t* d_chunk_file, uint64_t* d_keys, uint8_t* d_digests32, uint64_t* d_consumed,
+                            uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  const CdcParams p = chunk_params(params);
+  uint64_t slots = 0;
+  if (int rc = chunk_args(c, "dev_chunk_windows", d_offsets, d_lens, n, p, max_chunks, max_slots, &slots)) return rc;
+  if (n && !d_blob) return c->fail(SDCAS_E_INVALID, "dev_chunk_windows: null blob");
+  if (((uintptr_t)d_blob | (uintptr_t)d_digests32) & 15)
+    return c->fail(SDCAS_E_INVALID, "dev_chunk_windows: blob or digests not 16-byte aligned");
+  if ((((uintptr_t)d_offsets | (uintptr_t)d_lens | (uintptr_t)d_file_chunks | (uintptr_t)d_chunk_off |
+        (uintptr_t)d_chunk_len | (uintptr_t)d_keys | (uintptr_t)d_consumed | (uintptr_t)d_counts) & 7) ||
+      ((uintptr_t)d_chunk_file & 3))
+    return c->fail(SDCAS_E_INVALID, "dev_chunk_windows: an array is not 8-byte (chunk_file: 4-byte) aligned");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (n == 0) {
+    hipError_t e;
+    if ((d_counts && (e = hipMemsetAsync(d_counts, 0, kCdcCounts * sizeof(uint64_t), call.st))) ||
+        (d_file_chunks && (e = hipMemsetAsync(d_file_chunks, 0, sizeof(uint64_t), call.st))))
+      return c->hip_fail(e, "dev_chunk_windows");
+    return SDCAS_OK;
+  }
+  const CdcWinArgs win{d_final, d_consumed, chunk_seg(p)};
+  return chunk_enqueue(c, "dev_chunk_windows",
+                       CdcArgs{nullptr, d_blob, d_offsets, d_lens, (uint32_t)n, p, max_chunks, slots, d_file_chunks,
+                               d_chunk_off, d_chunk_len, d_chunk_file},
+                       d_keys, d_digests32, d_counts, call.st, &win);
 }
 
 static int sharing_args(sdcas_ctx* c, const char* who, const void* chunk_file, const void* chunk_len, const void* rep,

@@ -572,7 +572,167 @@ class Engine:
                 "chunk_file": fl, "keys": keys, "digests": dig, "rep": rep, "chunk_counts": ccounts,
                 "sharing_counts": scounts}
 
+    # -- chunk windows: files larger than device memory, piece by piece --------------
+    @staticmethod
+    def chunk_seg_bytes(params=None):
+        """sdcas_chunk_seg_bytes (no GPU): the segment length the cut pass of
+        chunk_windows uses for these parameters (SDCAS_CHUNK_SEG_BYTES, default
+        1 MiB, not below 2 * max_len, a multiple of 64); 0 for invalid ones"""
+        cp = Engine._chunk_params(params)
+        return int(N.load().sdcas_chunk_seg_bytes(ctypes.byref(cp)))
+
+    def chunk_windows(self, blob, offsets, lens, final=None, params=None, hashes=True):
+        """chunk_messages over windows (sdcas_chunk_windows; the definition is
+        in include/sdcas.h): window i is blob[offsets[i] : offsets[i] +
+        lens[i]], bytes of a file from one of its cuts on; final[i] says that
+        it ends where the file ends (None: all do). -> chunk_messages' seven
+        results and consumed uint64[n]: where the next window of that file
+        begins, relative to this one"""
+        blob = _arr(blob, np.uint8)
+        offsets, lens = _arr(offsets, np.uint64), _arr(lens, np.uint64)
+        n = lens.size
+        if offsets.size != n:
+            raise ValueError(f"chunk_windows: {n} lens, {offsets.size} offsets")
+        if final is not None:
+            final = _arr(np.asarray(final).astype(np.uint8), np.uint8)
+            if final.size != n:
+                raise ValueError(f"chunk_windows: {n} lens, {final.size} final flags")
+        if n and int((offsets + lens).max()) > blob.size:
+            raise ValueError("chunk_windows: a window ends past the blob")
+        mc, _ = self.chunk_plan(lens, params)
+        fc = np.zeros(n + 1, np.uint64)
+        off, ln = np.zeros(mc, np.uint64), np.zeros(mc, np.uint64)
+        fl = np.zeros(mc, np.uint32)
+        keys = np.zeros(mc, np.uint64) if hashes else None
+        dig = np.zeros((mc, 32), np.uint8) if hashes else None
+        consumed = np.zeros(n, np.uint64)
+        counts = N.ChunkCounts()
+        cp = self._chunk_params(params)
+        self._check(self.L.sdcas_chunk_windows(self.ctx, _ptr(blob), _ptr(offsets), _ptr(lens),
+                                               None if final is None else _ptr(final), n, ctypes.byref(cp),
+                                               _ptr(fc), _ptr(off), _ptr(ln), _ptr(fl),
+                                               _ptr(keys) if hashes else None, _ptr(dig) if hashes else None,
+                                               _ptr(consumed), ctypes.byref(counts)), "sdcas_chunk_windows")
+        m = int(counts.chunks)
+        return fc, off[:m].copy(), ln[:m].copy(), fl[:m].copy(), keys[:m].copy() if hashes else None, \
+            dig[:m].copy() if hashes else None, counts.as_dict(), consumed
+
+    @staticmethod
+    def plan_windows(lens, window_bytes):
+        """the windows chunk_stream makes of files of these lengths, taken in
+        order (no GPU) -> list of (first_file, n_files, streamed): consecutive
+        whole files while they fit in window_bytes together (streamed False),
+        a file larger than window_bytes alone, over consecutive windows
+        (streamed True, n_files 1)"""
+        window_bytes = int(window_bytes)
+        if window_bytes <= 0:
+            raise ValueError("plan_windows: window_bytes must be positive")
+        plan, first, held = [], 0, 0
+        for i, n in enumerate(int(v) for v in lens):
+            if n > window_bytes:
+                if i > first:
+                    plan.append((first, i - first, False))
+                plan.append((i, 1, True))
+                first, held = i + 1, 0
+            elif held + n > window_bytes:
+                plan.append((first, i - first, False))
+                first, held = i, n
+            else:
+                held += n
+        if len(lens) > first:
+            plan.append((first, len(lens) - first, False))
+        return plan
+
+    def chunk_stream(self, paths, window_bytes=256 << 20, params=None):
+        """the chunks of these files without their contents being resident at
+        once: a generator over windows of at most window_bytes (plan_windows).
+        Whole files share a window, all final; a file larger than window_bytes
+        is streamed alone, each window starting at the `consumed` of the one
+        before and grown when one consumed nothing, so chunks stay numbered
+        file by file. Yields dicts of "chunk_off" (offsets in the file),
+        "chunk_len", "chunk_file" (indices into paths), "keys", "digests",
+        "counts" (sdcas_chunk_counts of this window), "first_file", "n_files",
+        "file_pos" (where a streamed window begins), "final" and "sizes" (the
+        bytes read of each of the window's files)."""
+        paths = [os.fspath(p) for p in paths]
+        lens = [os.path.getsize(p) for p in paths]
+        for first, nf, streamed in self.plan_windows(lens, window_bytes):
+            if not streamed:
+                data = []
+                for p in paths[first:first + nf]:
+                    with open(p, "rb") as f:
+                        data.append(f.read())
+                blob, offs, ln_ = self.pack(data)
+                fc, off, ln, fl, keys, dig, counts, _ = self.chunk_windows(blob, offs, ln_, None, params)
+                yield {"chunk_off": off - offs[fl], "chunk_len": ln, "chunk_file": fl + np.uint32(first), "keys": keys,
+                       "digests": dig, "counts": counts, "first_file": first, "n_files": nf, "file_pos": 0,
+                       "final": True, "sizes": ln_}
+                continue
+            pos, want, size = 0, int(window_bytes), lens[first]
+            with open(paths[first], "rb") as f:
+                while True:
+                    f.seek(pos)
+                    data = f.read(want)
+                    final = pos + len(data) >= size or len(data) < want
+                    blob, offs, ln_ = self.pack([data])
+                    fc, off, ln, fl, keys, dig, counts, consumed = self.chunk_windows(blob, offs, ln_, [final], params)
+                    used = int(consumed[0])
+                    if not final and used == 0:
+                        want *= 2  # shorter than max_len: nothing could be decided
+                        continue
+                    yield {"chunk_off": off - offs[fl] + np.uint64(pos), "chunk_len": ln,
+                           "chunk_file": fl + np.uint32(first), "keys": keys, "digests": dig, "counts": counts,
+                           "first_file": first, "n_files": 1, "file_pos": pos, "final": bool(final),
+                           "sizes": np.array([used], np.uint64)}
+                    if final:
+                        break
+                    pos, want = pos + used, int(window_bytes)
+
+    def similar_files_streamed(self, paths, window_bytes=256 << 20, params=None):
+        """similar_files for files that need not fit in device memory: the
+        chunks come from chunk_stream, window by window; the chunk arrays, keys
+        and digests are kept and one confirm and one sharing pass run over all
+        of them. The same dict as similar_files, equal to it entry for entry"""
+        paths = [os.fspath(p) for p in paths]
+        n = len(paths)
+        parts = {k: [] for k in ("chunk_off", "chunk_len", "chunk_file", "keys", "digests")}
+        sizes = np.zeros(n, np.uint64)
+        ccounts = dict.fromkeys((name for name, _ in N.ChunkCounts._fields_), 0)
+        for w in self.chunk_stream(paths, window_bytes, params):
+            for k in parts:
+                parts[k].append(w[k])
+            sizes[w["first_file"]:w["first_file"] + w["n_files"]] += w["sizes"]
+            for k, v in w["counts"].items():
+                ccounts[k] += v
+        off = np.concatenate(parts["chunk_off"] or [np.zeros(0, np.uint64)]).astype(np.uint64)
+        ln = np.concatenate(parts["chunk_len"] or [np.zeros(0, np.uint64)]).astype(np.uint64)
+        fl = np.concatenate(parts["chunk_file"] or [np.zeros(0, np.uint32)]).astype(np.uint32)
+        keys = np.concatenate(parts["keys"] or [np.zeros(0, np.uint64)]).astype(np.uint64)
+        dig = np.concatenate(parts["digests"] or [np.zeros((0, 32), np.uint8)]).astype(np.uint8)
+        fc = np.zeros(n + 1, np.uint64)
+        fc[1:] = np.cumsum(np.bincount(fl, minlength=n)[:n])
+        rep = self.confirm_duplicates(keys, dig)[0]
+        new, own, other, peer, peer_bytes, scounts = self.chunk_sharing(fl, ln, rep, n)
+        return {"sizes": sizes, "new_bytes": new, "self_bytes": own, "other_bytes": other, "peer": peer,
+                "peer_bytes": peer_bytes, "file_chunks": fc, "chunk_off": off, "chunk_len": ln,
+                "chunk_file": fl, "keys": keys, "digests": dig, "rep": rep, "chunk_counts": ccounts,
+                "sharing_counts": scounts}
+
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
+    def dev_chunk_windows(self, blob, offs, lens, final, n, max_chunks, max_slots, params=None, file_chunks=0,
+                          chunk_off=0, chunk_len=0, chunk_file=0, keys=0, digests=0, consumed=0, counts=0, stream=0):
+        """chunk_windows over device arrays (sdcas_dev_chunk_windows):
+        dev_chunk's contracts; final uint8[n] or 0 (all final), consumed
+        uint64[n] or 0. Waits for the device once when keys or digests are
+        asked for, never otherwise"""
+        cp = self._chunk_params(params)
+        self._check(self.L.sdcas_dev_chunk_windows(self.ctx, blob or None, offs or None, lens or None, final or None,
+                                                   int(n), ctypes.byref(cp), int(max_chunks), int(max_slots),
+                                                   file_chunks or None, chunk_off or None, chunk_len or None,
+                                                   chunk_file or None, keys or None, digests or None,
+                                                   consumed or None, counts or None, stream or None),
+                    "dev_chunk_windows")
+
     def dev_chunk(self, blob, offs, lens, n, max_chunks, max_slots, params=None, file_chunks=0, chunk_off=0,
                   chunk_len=0, chunk_file=0, keys=0, digests=0, counts=0, stream=0):
         """chunk_messages over device arrays (sdcas_dev_chunk): the blob and

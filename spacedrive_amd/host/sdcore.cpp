@@ -1742,4 +1742,173 @@ SimilarityReport similarity_report(Engine& engine, Library& db, const Location& 
   return out;
 }
 
+// ---- the same for files that are not resident at once ----------------------------------
+
+Engine::WindowChunks Engine::chunk_windows(const std::vector<uint8_t>& blob, const std::vector<uint64_t>& offsets,
+                                           const std::vector<uint64_t>& lens, const std::vector<uint8_t>& final,
+                                           const sdcas_chunk_params* params) {
+  const size_t n = lens.size();
+  if (offsets.size() != n || (!final.empty() && final.size() != n))
+    throw std::invalid_argument("chunk_windows: offsets / lens / final lengths differ");
+  for (size_t i = 0; i < n; ++i)
+    if (offsets[i] > blob.size() || lens[i] > blob.size() - offsets[i])
+      throw std::invalid_argument("chunk_windows: window " + std::to_string(i) + " ends past the blob");
+  uint64_t max_chunks = 0;
+  int rc = sdcas_chunk_plan(lens.data(), n, params, &max_chunks, nullptr);
+  if (rc != SDCAS_OK) throw LibraryError(rc, "sdcas_chunk_plan: the parameters or the lengths are refused");
+  WindowChunks r;
+  r.file_chunks.assign(n + 1, 0), r.consumed.assign(n, 0);
+  r.chunk_off.assign(max_chunks, 0), r.chunk_len.assign(max_chunks, 0), r.keys.assign(max_chunks, 0);
+  r.chunk_file.assign(max_chunks, 0);
+  r.digests.assign(32 * max_chunks, 0);
+  rc = sdcas_chunk_windows(ctx_, blob.data(), offsets.data(), lens.data(), final.empty() ? nullptr : final.data(), n,
+                           params, r.file_chunks.data(), r.chunk_off.data(), r.chunk_len.data(), r.chunk_file.data(),
+                           r.keys.data(), r.digests.data(), r.consumed.data(), &r.counts);
+  if (rc != SDCAS_OK) fail(rc, "sdcas_chunk_windows");
+  const size_t m = r.counts.chunks;
+  r.chunk_off.resize(m), r.chunk_len.resize(m), r.keys.resize(m), r.chunk_file.resize(m), r.digests.resize(32 * m);
+  return r;
+}
+
+std::vector<WindowPlan> plan_chunk_windows(const std::vector<uint64_t>& sizes, uint64_t window_bytes) {
+  if (window_bytes == 0) throw std::invalid_argument("plan_chunk_windows: window_bytes must be positive");
+  std::vector<WindowPlan> plan;
+  size_t first = 0;
+  uint64_t held = 0;
+  for (size_t i = 0; i < sizes.size(); ++i) {
+    if (sizes[i] > window_bytes) {
+      if (i > first) plan.push_back(WindowPlan{first, i - first, false});
+      plan.push_back(WindowPlan{i, 1, true});
+      first = i + 1, held = 0;
+    } else if (sizes[i] > window_bytes - held) {
+      plan.push_back(WindowPlan{first, i - first, false});
+      first = i, held = sizes[i];
+    } else {
+      held += sizes[i];
+    }
+  }
+  if (sizes.size() > first) plan.push_back(WindowPlan{first, sizes.size() - first, false});
+  return plan;
+}
+
+Engine::Chunks merge_chunk_windows(const std::vector<ChunkWindow>& windows, size_t n_files, std::vector<uint64_t>* sizes) {
+  Engine::Chunks out;
+  std::vector<uint64_t> per_file(n_files, 0), used(n_files, 0);
+  size_t last_file = 0, last_n = 0;
+  uint64_t last_pos = 0;
+  for (const ChunkWindow& w : windows) {
+    const Engine::WindowChunks& c = w.chunks;
+    const size_t nf = w.offsets.size(), m = c.chunk_off.size();
+    if (c.consumed.size() != nf || c.chunk_len.size() != m || c.chunk_file.size() != m || c.keys.size() != m ||
+        c.digests.size() != 32 * m)
+      throw std::invalid_argument("merge_chunk_windows: a window's arrays do not fit each other");
+    // the next window of a streamed file follows in that file; any other begins behind the files before it
+    const bool follows = nf == 1 && last_n == 1 && w.first_file == last_file && w.file_pos >= last_pos && w.file_pos;
+    if ((!follows && w.first_file < last_file + last_n) || w.first_file > n_files || nf > n_files - w.first_file)
+      throw std::invalid_argument("merge_chunk_windows: a window goes back or names a file past n_files");
+    if (w.file_pos && nf != 1) throw std::invalid_argument("merge_chunk_windows: a window inside a file holds that file alone");
+    uint32_t before = 0;
+    for (size_t k = 0; k < m; ++k) {
+      const uint32_t f = c.chunk_file[k];
+      if (f >= nf || f < before || c.chunk_off[k] < w.offsets[f])
+        throw std::invalid_argument("merge_chunk_windows: a window's chunks are not in its files' order");
+      before = f;
+      out.chunk_file.push_back((uint32_t)(w.first_file + f));
+      out.chunk_off.push_back(c.chunk_off[k] - w.offsets[f] + w.file_pos);
+      out.chunk_len.push_back(c.chunk_len[k]);
+      out.keys.push_back(c.keys[k]);
+      ++per_file[w.first_file + f];
+    }
+    out.digests.insert(out.digests.end(), c.digests.begin(), c.digests.end());
+    for (size_t f = 0; f < nf; ++f) used[w.first_file + f] += c.consumed[f];
+    out.counts.files += c.counts.files, out.counts.chunks += c.counts.chunks;
+    out.counts.total_bytes += c.counts.total_bytes, out.counts.hash_cuts += c.counts.hash_cuts;
+    out.counts.max_cuts += c.counts.max_cuts, out.counts.end_chunks += c.counts.end_chunks;
+    if (nf) last_file = w.first_file, last_n = nf, last_pos = w.file_pos;
+  }
+  out.file_chunks.assign(n_files + 1, 0);
+  for (size_t i = 0; i < n_files; ++i) out.file_chunks[i + 1] = out.file_chunks[i] + per_file[i];
+  if (sizes) *sizes = used;
+  return out;
+}
+
+namespace {
+
+// up to `want` bytes of f from pos on, appended to blob -> the bytes read
+uint64_t read_some(std::FILE* f, uint64_t pos, uint64_t want, std::vector<uint8_t>& blob) {
+  if (!f || fseeko(f, (off_t)pos, SEEK_SET) != 0) return 0;
+  uint8_t buf[1 << 16];
+  uint64_t total = 0;
+  while (total < want) {
+    const size_t ask = (size_t)std::min<uint64_t>(sizeof buf, want - total);
+    const size_t got = std::fread(buf, 1, ask, f);
+    if (!got) break;
+    blob.insert(blob.end(), buf, buf + got);
+    total += got;
+  }
+  return total;
+}
+
+}  // namespace
+
+SimilarityReport similarity_report_streamed(Engine& engine, Library& db, const Location& location, const std::string& sub,
+                                            uint64_t window_bytes) {
+  std::vector<FilePathRow> rows;
+  for (FilePathRow& r : db.file_paths_in_location(location.id, sub))
+    if (!r.is_dir) rows.push_back(std::move(r));
+  const size_t n = rows.size();
+  if (n == 0) return SimilarityReport{};
+  std::vector<uint64_t> sizes(n, 0);  // a file that cannot be read counts as empty
+  for (size_t i = 0; i < n; ++i)
+    if (std::FILE* f = std::fopen(full_path(location, rows[i]).c_str(), "rb")) {
+      if (fseeko(f, 0, SEEK_END) == 0 && ftello(f) > 0) sizes[i] = (uint64_t)ftello(f);
+      std::fclose(f);
+    }
+  std::vector<ChunkWindow> windows;
+  for (const WindowPlan& wp : plan_chunk_windows(sizes, window_bytes)) {
+    if (!wp.streamed) {
+      ChunkWindow w;
+      w.first_file = wp.first_file;
+      std::vector<uint8_t> blob;
+      std::vector<uint64_t> lens(wp.n_files, 0);
+      for (size_t k = 0; k < wp.n_files; ++k) {
+        w.offsets.push_back(blob.size());
+        std::FILE* f = std::fopen(full_path(location, rows[wp.first_file + k]).c_str(), "rb");
+        lens[k] = read_some(f, 0, sizes[wp.first_file + k], blob);
+        if (f) std::fclose(f);
+      }
+      w.chunks = engine.chunk_windows(blob, w.offsets, lens, {});
+      windows.push_back(std::move(w));
+      continue;
+    }
+    std::FILE* f = std::fopen(full_path(location, rows[wp.first_file]).c_str(), "rb");
+    uint64_t pos = 0, want = window_bytes;
+    for (;;) {
+      ChunkWindow w;
+      w.first_file = wp.first_file, w.file_pos = pos, w.offsets = {0};
+      std::vector<uint8_t> blob;
+      const uint64_t got = read_some(f, pos, want, blob);
+      const bool final = got < want || pos + got >= sizes[wp.first_file];
+      w.chunks = engine.chunk_windows(blob, w.offsets, {got}, {(uint8_t)final});
+      const uint64_t used = w.chunks.consumed[0];
+      if (!final && used == 0) {
+        want *= 2;  // shorter than max_len: nothing could be decided
+        continue;
+      }
+      windows.push_back(std::move(w));
+      if (final) break;
+      pos += used, want = window_bytes;
+    }
+    if (f) std::fclose(f);
+  }
+  std::vector<uint64_t> used;
+  const Engine::Chunks ch = merge_chunk_windows(windows, n, &used);
+  const Engine::Confirm c = engine.confirm_duplicates(ch.keys, ch.digests, {});
+  const Engine::Sharing s = engine.chunk_sharing(ch.chunk_file, ch.chunk_len, c.rep, n);
+  SimilarityReport out = similarity_report_from(rows, used, s.peer, s.peer_bytes);
+  out.chunks = ch.counts;
+  out.counts = s.counts;
+  return out;
+}
+
 }  // namespace sdcore
