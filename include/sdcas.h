@@ -796,6 +796,120 @@ int sdcas_dev_chunk_sharing(sdcas_ctx *ctx, const uint32_t *d_chunk_file, const 
                             uint64_t *d_self_bytes, uint64_t *d_other_bytes, int64_t *d_peer, uint64_t *d_peer_bytes,
                             uint64_t *d_counts, void *stream);
 
+/* ---- chunk index: a batch's chunks against the chunks stored before ----------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * The "existing" side of the chunk group-by: what sdcas_dedup's existing_keys
+ * are to the cas keys. An INDEX of n entries with directory width `bits`
+ * (0 <= bits <= 28, n <= 2^30) is four caller-owned arrays:
+ *   keys[n] u64, digests32[n] (32 B each; 16-byte aligned on the device),
+ *   values[n] u64 (opaque here; the upper layers store the owning file's id),
+ *   with the entries STRICTLY ASCENDING in the pair (key as u64, digest as 32
+ *   bytes in memcmp order), so that pairs are distinct. For real chunks the
+ *   key is the digest's bytes 0..8 big-endian and this is digest order; any
+ *   keys are taken, forged ones too, as sdcas_confirm_duplicates takes them.
+ *   dir[2^bits + 1] u32: dir[j] = the number of entries with
+ *   keys[i] >> (64 - bits) < j; for bits == 0 the directory is {0, n}. The
+ *   last slot is always n.
+ * The device calls clamp every directory value to n before use: a directory
+ * that does not belong to its arrays gives wrong answers, never an index past
+ * them. Results are exact and do not depend on scheduling: two calls on one
+ * input give the same bytes. */
+#define SDCAS_INDEX_MAX_ENTRIES (1ull << 30)
+#define SDCAS_INDEX_MAX_BITS 28u
+/* GPU-free. The recommended directory width for n entries: 0 for n < 8, else
+ * min(28, ceil_log2(n) - 2): about 4 entries per bucket. */
+uint32_t sdcas_chunk_index_dir_bits(uint64_t n);
+/* GPU-free, host arrays (used on load from disk): SDCAS_OK when the arrays are
+ * an index as defined above. SDCAS_E_CAPACITY for n > 2^30 or bits > 28, before
+ * any array is touched. SDCAS_E_INVALID for a NULL array that is needed, or
+ * with *out_first_bad (may be NULL) = the first entry i >= 1 that does not
+ * order after entry i - 1 or, when the entries are in order, the first
+ * directory slot that does not hold its count. */
+int sdcas_chunk_index_check(const uint64_t *keys, const uint8_t *digests32, const uint32_t *dir, uint64_t n,
+                            uint32_t bits, uint64_t *out_first_bad);
+
+typedef struct sdcas_index_match_counts {
+  uint64_t queries; /* valid queries */
+  uint64_t hits;
+  uint64_t misses;
+  uint64_t skipped; /* !valid */
+} sdcas_index_match_counts;
+/* Read-only match of m queries (keys, digests32, valid: sdcas_confirm_duplicates'
+ * inputs; valid NULL: all are valid) against the index; its cost follows m, not n:
+ *   out_pos[c]    the entry i with idx_keys[i] == keys[c] and all 32 digest
+ *                 bytes equal; -1 when there is none or !valid[c]
+ *   out_value[c]  idx_values[i], or 0
+ * Any output may be NULL; m == 0 and n == 0 are SDCAS_OK. Host arrays: one
+ * upload of the index and the batch, the device call, one download (a caller
+ * that keeps an index should keep it on the device and use the call below). */
+int sdcas_chunk_index_match(sdcas_ctx *ctx, const uint64_t *idx_keys, const uint8_t *idx_digests32,
+                            const uint64_t *idx_values, const uint32_t *idx_dir, uint64_t n, uint32_t bits,
+                            const uint64_t *keys, const uint8_t *digests32, const uint8_t *valid, size_t m,
+                            int64_t *out_pos, uint64_t *out_value, sdcas_index_match_counts *out_counts);
+/* Device arrays, asynchronous on `stream` with sdcas_dev_hash_messages's
+ * stream rules. Both digest arrays 16-byte aligned, the u64 arrays and the
+ * outputs 8-byte, d_idx_dir 4-byte (SDCAS_E_INVALID otherwise, as for a NULL
+ * array that is needed); n > 2^30, m > 2^30 or bits > 28 is SDCAS_E_CAPACITY;
+ * both are reported before anything is enqueued. d_counts: four u64 in
+ * sdcas_index_match_counts' order, overwritten. The call never waits for the
+ * device and uses no workspace. */
+int sdcas_dev_chunk_index_match(sdcas_ctx *ctx, const uint64_t *d_idx_keys, const uint8_t *d_idx_digests32,
+                                const uint64_t *d_idx_values, const uint32_t *d_idx_dir, uint64_t n, uint32_t bits,
+                                const uint64_t *d_keys, const uint8_t *d_digests32, const uint8_t *d_valid, size_t m,
+                                int64_t *d_out_pos, uint64_t *d_out_value, uint64_t *d_counts, void *stream);
+
+/* Add: the NEW index is the sorted distinct union of the old entries and the
+ * valid pairs of the batch, with its directory at bits_new (the widths may
+ * differ: growing re-buckets). A pair the old index holds keeps the old
+ * value; a new pair takes values[c] of the LOWEST batch position c that holds
+ * it. The new keys / digests32 / values arrays hold n_old + m entries, of
+ * which the first entries_new are written and the rest left as they were;
+ * new_dir holds 2^bits_new + 1.
+ *   out_pos[c]    the pair's entry in the new index; -1 when !valid[c]
+ *   out_flags[c]  SDCAS_INDEX_HIT: the pair was in the old index;
+ *                 SDCAS_INDEX_ADDED: the pair is new and values[c] was stored;
+ *                 SDCAS_INDEX_SKIPPED: !valid[c];
+ *                 0: a later copy, within the batch, of an added pair
+ * queries == hits + added + batch_duplicates. Old and new arrays must not
+ * overlap (checked from pointers and sizes: SDCAS_E_INVALID); n_old + m <=
+ * 2^30 (SDCAS_E_CAPACITY). values NULL: every stored value is 0. out_pos,
+ * out_flags and the counts may be NULL. */
+#define SDCAS_INDEX_HIT     1u
+#define SDCAS_INDEX_ADDED   2u
+#define SDCAS_INDEX_SKIPPED 4u
+typedef struct sdcas_index_add_counts {
+  uint64_t queries; /* valid batch entries */
+  uint64_t hits;
+  uint64_t added;
+  uint64_t batch_duplicates;
+  uint64_t entries_old;
+  uint64_t entries_new; /* entries_old + added */
+} sdcas_index_add_counts;
+/* Host arrays: one upload, the device call, the counts down, then exactly
+ * entries_new entries of the new arrays and the new directory. */
+int sdcas_chunk_index_add(sdcas_ctx *ctx, const uint64_t *old_keys, const uint8_t *old_digests32,
+                          const uint64_t *old_values, const uint32_t *old_dir, uint64_t n_old, uint32_t bits_old,
+                          const uint64_t *keys, const uint8_t *digests32, const uint64_t *values,
+                          const uint8_t *valid, size_t m, uint64_t *new_keys, uint8_t *new_digests32,
+                          uint64_t *new_values, uint32_t *new_dir, uint32_t bits_new, int64_t *out_pos,
+                          uint8_t *out_flags, sdcas_index_add_counts *out_counts);
+/* Device arrays, asynchronous on `stream`, alignments as for the match
+ * (d_out_flags any). d_counts: six u64 in sdcas_index_add_counts' order,
+ * overwritten: entries_new stays on the device, and every grid is sized from
+ * the bounds m and n_old. The context's workspace for a batch of m (about 100
+ * bytes per batch entry with the group-by's tables; nothing that grows with
+ * n_old) is allocated by the first call that needs it, which waits for the
+ * stream: warm up outside timed regions. After that the call never waits. */
+int sdcas_dev_chunk_index_add(sdcas_ctx *ctx, const uint64_t *d_old_keys, const uint8_t *d_old_digests32,
+                              const uint64_t *d_old_values, const uint32_t *d_old_dir, uint64_t n_old,
+                              uint32_t bits_old, const uint64_t *d_keys, const uint8_t *d_digests32,
+                              const uint64_t *d_values, const uint8_t *d_valid, size_t m, uint64_t *d_new_keys,
+                              uint8_t *d_new_digests32, uint64_t *d_new_values, uint32_t *d_new_dir,
+                              uint32_t bits_new, int64_t *d_out_pos, uint8_t *d_out_flags, uint64_t *d_counts,
+                              void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

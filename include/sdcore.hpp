@@ -74,6 +74,18 @@ class LibraryError : public std::runtime_error {
   int code;
 };
 
+// A chunk index on the host (include/sdcas.h "chunk index"): the entries
+// strictly ascending in (key, digest as 32 bytes), digests 32 bytes per entry,
+// values the file_path id of the row that held the chunk first, and the
+// directory of 2^bits + 1 slots.
+struct ChunkIndexData {
+  std::vector<uint64_t> keys, values;
+  std::vector<uint8_t> digests;
+  std::vector<uint32_t> dir{0, 0};
+  uint32_t bits = 0;
+  size_t size() const { return keys.size(); }
+};
+
 class Engine {
  public:
   struct Options {
@@ -203,6 +215,27 @@ class Engine {
   WindowChunks chunk_windows(const std::vector<uint8_t>& blob, const std::vector<uint64_t>& offsets,
                              const std::vector<uint64_t>& lens, const std::vector<uint8_t>& final,
                              const sdcas_chunk_params* params = nullptr);
+
+  // a batch's (key, digest) pairs against a chunk index
+  // (sdcas_chunk_index_match); valid may be empty (every query takes part)
+  struct IndexMatch {
+    std::vector<int64_t> pos;     // the entry with the query's key and digest, -1: none
+    std::vector<uint64_t> value;  // its value, or 0
+    sdcas_index_match_counts counts{};
+  };
+  IndexMatch chunk_index_match(const ChunkIndexData& index, const std::vector<uint64_t>& keys,
+                               const std::vector<uint8_t>& digests, const std::vector<uint8_t>& valid);
+  // the index with the batch's unseen pairs merged in (sdcas_chunk_index_add),
+  // its directory at the recommended width for the old entries plus the batch
+  struct IndexAdd {
+    ChunkIndexData index;
+    std::vector<int64_t> pos;    // each pair's entry in the new index
+    std::vector<uint8_t> flags;  // SDCAS_INDEX_*
+    sdcas_index_add_counts counts{};
+  };
+  IndexAdd chunk_index_add(const ChunkIndexData& index, const std::vector<uint64_t>& keys,
+                           const std::vector<uint8_t>& digests, const std::vector<uint64_t>& values,
+                           const std::vector<uint8_t>& valid);
 
   sdcas_ctx* raw() { return ctx_; }
 
@@ -515,6 +548,25 @@ class SqliteLibrary : public Library {
   bool concurrent_orphan_reads() override;
   std::vector<FilePathRow> get_orphan_file_paths_concurrent(int32_t location_id, int32_t cursor,
                                                             const std::string& sub, size_t take) override;
+
+  // The chunk index's tables (similarity_report_indexed): chunk_index(digest
+  // BLOB PRIMARY KEY, file_path_id INTEGER), one row per distinct chunk with
+  // the row that held it first — the key is the digest's first 8 bytes and
+  // ORDER BY digest is index order, since SQLite orders BLOBs as memcmp does —
+  // and chunk_indexed_file(file_path_id INTEGER PRIMARY KEY, size INTEGER), the
+  // rows whose chunks are in it. Both are created by the first call below.
+  // The stored index, its directory at the recommended width; checked
+  // (sdcas_chunk_index_check, and every digest 32 bytes): LibraryError with
+  // SDCAS_E_INVALID for a table that is no index.
+  ChunkIndexData load_chunk_index();
+  // (file_path id, bytes read) of the rows indexed so far, ascending by id
+  std::vector<std::pair<int32_t, uint64_t>> chunk_indexed_files();
+  // one transaction, and the only writes to the two tables: the added chunks
+  // (32 bytes each) with their owners, and the rows now indexed. A digest
+  // already stored or a row already indexed is std::runtime_error, and then
+  // nothing of the call is kept.
+  void append_chunk_index(const std::vector<uint8_t>& digests, const std::vector<int32_t>& owners,
+                          const std::vector<std::pair<int32_t, uint64_t>>& files);
 
  private:
   struct Impl;
@@ -860,5 +912,30 @@ Engine::Chunks merge_chunk_windows(const std::vector<ChunkWindow>& windows, size
 // them. The same report as similarity_report whenever that one can run.
 SimilarityReport similarity_report_streamed(Engine& engine, Library& db, const Location& location,
                                             const std::string& sub = "", uint64_t window_bytes = 256ull << 20);
+
+// ---- the same against the chunks stored before ------------------------------------------
+// The per-file sharing of a batch against a chunk index (no device work of its
+// own: Engine::chunk_sharing over the batch's chunks with one pseudo-chunk per
+// matched pair in front). rep / hit_value: Engine::confirm_duplicates' rep over
+// the batch's chunks and Engine::chunk_index_match's pos / value. The origin of
+// a chunk is the stored value when the index holds it, else file_ids[the file of
+// its lowest copy in the batch]; peer is a FILE ID (ties to the lowest), -1 none.
+struct IndexedSharing {
+  std::vector<uint64_t> new_bytes, self_bytes, other_bytes, indexed_bytes, peer_bytes;
+  std::vector<int64_t> peer;
+};
+IndexedSharing indexed_sharing(Engine& engine, const Engine::Chunks& chunks, const std::vector<int64_t>& rep,
+                               const Engine::IndexMatch& match, const std::vector<uint64_t>& file_ids);
+// similarity_report_streamed for the rows that came since the last call: the
+// location's file rows that chunk_indexed_file does not hold yet go through
+// the windows, their chunks are confirmed, matched against the stored index
+// (SqliteLibrary::load_chunk_index) and added to it with their row's id, and
+// the added chunks and the rows are recorded (append_chunk_index, the only
+// writes). Reports a Pair for each of those rows that has a peer; a peer may
+// be a row indexed by an earlier call. Called after each of several batches
+// of files is created, the union of its reports is similarity_report_streamed's
+// over all of them. With no new row it reports nothing and writes nothing.
+SimilarityReport similarity_report_indexed(Engine& engine, SqliteLibrary& db, const Location& location,
+                                           const std::string& sub = "", uint64_t window_bytes = 256ull << 20);
 
 }  // namespace sdcore

@@ -48,6 +48,11 @@ SDCAS_CHUNK_PARAMS_DEFAULT = (2048, 13, 65536)
 SDCAS_CHUNK_MAX_CHUNKS = 1 << 30
 SDCAS_CHUNK_GEAR_TILE = 32768
 SDCAS_CHUNK_GEAR_STRIP = 128
+SDCAS_INDEX_MAX_ENTRIES = 1 << 30
+SDCAS_INDEX_MAX_BITS = 28
+SDCAS_INDEX_HIT = 1
+SDCAS_INDEX_ADDED = 2
+SDCAS_INDEX_SKIPPED = 4
 
 # every entry point include/sdcas.h and include/sdcas_bench.h declare
 ABI_SYMBOLS = [
@@ -62,6 +67,8 @@ ABI_SYMBOLS = [
     "sdcas_chunk_plan", "sdcas_chunk_messages", "sdcas_dev_chunk", "sdcas_chunk_sharing",
     "sdcas_dev_chunk_sharing",  # added after ABI 7
     "sdcas_chunk_seg_bytes", "sdcas_chunk_windows", "sdcas_dev_chunk_windows",  # added after ABI 7
+    "sdcas_chunk_index_dir_bits", "sdcas_chunk_index_check", "sdcas_chunk_index_match",
+    "sdcas_dev_chunk_index_match", "sdcas_chunk_index_add", "sdcas_dev_chunk_index_add",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -178,6 +185,25 @@ class SharingCounts(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class IndexMatchCounts(ctypes.Structure):
+    """sdcas_index_match_counts"""
+    _fields_ = [("queries", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("misses", ctypes.c_uint64),
+                ("skipped", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class IndexAddCounts(ctypes.Structure):
+    """sdcas_index_add_counts"""
+    _fields_ = [("queries", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("added", ctypes.c_uint64),
+                ("batch_duplicates", ctypes.c_uint64), ("entries_old", ctypes.c_uint64),
+                ("entries_new", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _lib_path = LIB_PATH
 
@@ -261,6 +287,18 @@ def load():
     L.sdcas_chunk_sharing.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
                                       ctypes.POINTER(SharingCounts)]
     L.sdcas_dev_chunk_sharing.argtypes = [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    _u32 = ctypes.c_uint32
+    L.sdcas_chunk_index_dir_bits.argtypes = [_u64]
+    L.sdcas_chunk_index_dir_bits.restype = _u32
+    L.sdcas_chunk_index_check.argtypes = [_vp, _vp, _vp, _u64, _u32, _vp]
+    L.sdcas_chunk_index_match.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _sz, _vp, _vp,
+                                          ctypes.POINTER(IndexMatchCounts)]
+    L.sdcas_dev_chunk_index_match.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _sz, _vp, _vp, _vp,
+                                              _vp]
+    L.sdcas_chunk_index_add.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp,
+                                        _vp, _u32, _vp, _vp, ctypes.POINTER(IndexAddCounts)]
+    L.sdcas_dev_chunk_index_add.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _sz, _vp, _vp,
+                                            _vp, _vp, _u32, _vp, _vp, _vp, _vp]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

@@ -34,6 +34,7 @@
 #include "dupsets.h"
 #include "dirtree.h"
 #include "cdc.h"
+#include "chunk_index.h"
 #include "dist_dedup.h"
 #include "synth.h"
 
@@ -225,6 +226,10 @@ struct sdcas_ctx {
   // calls' device copies of their arrays
   DevBuf<uint8_t> cd_ws, cd_pack, cd_io, cs_ws, cs_io;
   HostStage cd_stage;
+
+  // the chunk index (chunk_index.hip): the add's workspace, and the host
+  // calls' device copies of their arrays
+  DevBuf<uint8_t> ci_ws, ci_io;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -859,6 +864,8 @@ void sdcas_destroy(sdcas_ctx* c) {
   c->tt_io.release();
   for (auto* b : {&c->cd_ws, &c->cd_pack, &c->cd_io, &c->cs_ws, &c->cs_io}) b->release();
   c->cd_stage.release();
+  c->ci_ws.release();
+  c->ci_io.release();
   c->dist.release();
   c->sm_d_files.release();
   c->sm_nodes.release();
@@ -2717,6 +2724,257 @@ int sdcas_chunk_sharing(sdcas_ctx* c, const uint32_t* chunk_file, const uint64_t
       (out_counts && (e = hipMemcpyAsync(out_counts, io + o_cts, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
     return c->hip_fail(e, "chunk_sharing D2H");
   if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_sharing sync");
+  return SDCAS_OK;
+}
+
+// ---- the chunk index (chunk_index.hip) ----------------------------------------------
+
+uint32_t sdcas_chunk_index_dir_bits(uint64_t n) { return index_dir_bits(n); }
+
+int sdcas_chunk_index_check(const uint64_t* keys, const uint8_t* digests32, const uint32_t* dir, uint64_t n,
+                            uint32_t bits, uint64_t* out_first_bad) {
+  static_assert(SDCAS_INDEX_MAX_ENTRIES == kIndexMaxEntries && SDCAS_INDEX_MAX_BITS == kIndexMaxBits, "index limits");
+  if (n > kIndexMaxEntries || bits > kIndexMaxBits) return SDCAS_E_CAPACITY;
+  if (!dir || (n && (!keys || !digests32))) return SDCAS_E_INVALID;
+  uint64_t bad = 0;
+  if (index_check(keys, digests32, dir, n, bits, &bad)) {
+    if (out_first_bad) *out_first_bad = bad;
+    return SDCAS_E_INVALID;
+  }
+  return SDCAS_OK;
+}
+
+// an index argument (host or device): its limits, and the arrays a lookup reads
+static int index_view_args(sdcas_ctx* c, const char* who, const void* keys, const void* digests, const void* dir,
+                           uint64_t n, uint32_t bits) {
+  if (n > kIndexMaxEntries) return c->fail(SDCAS_E_CAPACITY, "%s: an index of %llu entries exceeds 2^30", who, (unsigned long long)n);
+  if (bits > kIndexMaxBits) return c->fail(SDCAS_E_CAPACITY, "%s: a directory of %u bits exceeds 28", who, bits);
+  if (n && (!keys || !digests || !dir)) return c->fail(SDCAS_E_INVALID, "%s: null index keys, digests or directory", who);
+  return SDCAS_OK;
+}
+static int index_batch_args(sdcas_ctx* c, const char* who, const void* keys, const void* digests, size_t m) {
+  if (m > kIndexMaxEntries) return c->fail(SDCAS_E_CAPACITY, "%s: a batch of %zu exceeds 2^30", who, m);
+  if (m && (!keys || !digests)) return c->fail(SDCAS_E_INVALID, "%s: null keys or digests", who);
+  return SDCAS_OK;
+}
+static bool index_ranges_meet(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+  if (!a || !b || !a_bytes || !b_bytes) return false;
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + b_bytes && y < x + a_bytes;
+}
+// the add's arguments: limits, the arrays it needs, old against new
+static int index_add_args(sdcas_ctx* c, const char* who, const void* old_keys, const void* old_digests,
+                          const void* old_values, const void* old_dir, uint64_t n_old, uint32_t bits_old,
+                          const void* keys, const void* digests, size_t m, const void* new_keys,
+                          const void* new_digests, const void* new_values, const void* new_dir, uint32_t bits_new) {
+  if (int rc = index_view_args(c, who, old_keys, old_digests, old_dir, n_old, bits_old)) return rc;
+  if (int rc = index_batch_args(c, who, keys, digests, m)) return rc;
+  if (bits_new > kIndexMaxBits) return c->fail(SDCAS_E_CAPACITY, "%s: a directory of %u bits exceeds 28", who, bits_new);
+  const uint64_t cap = n_old + m;
+  if (cap > kIndexMaxEntries) return c->fail(SDCAS_E_CAPACITY, "%s: %llu old entries and a batch of %zu exceed 2^30", who, (unsigned long long)n_old, m);
+  if (!new_dir || (cap && (!new_keys || !new_digests || !new_values)))
+    return c->fail(SDCAS_E_INVALID, "%s: null array of the new index", who);
+  const void* o[4] = {old_keys, old_digests, old_values, old_dir};
+  const uint64_t ob[4] = {8 * n_old, 32 * n_old, 8 * n_old, n_old ? 4 * index_dir_slots(bits_old) : 0};
+  const void* w[4] = {new_keys, new_digests, new_values, new_dir};
+  const uint64_t wb[4] = {8 * cap, 32 * cap, 8 * cap, 4 * index_dir_slots(bits_new)};
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j)
+      if (index_ranges_meet(o[i], ob[i], w[j], wb[j]))
+        return c->fail(SDCAS_E_INVALID, "%s: the old and the new index overlap", who);
+  return SDCAS_OK;
+}
+
+// the add's workspace (and the group-by's) grown to a batch of m; the stream
+// waits first, as an earlier call's kernels may still use what is freed
+static int index_add_ws(sdcas_ctx* c, size_t m, hipStream_t st) {
+  const size_t need = (size_t)index_add_layout(m).bytes;
+  if (need > c->ci_ws.cap) {
+    hipError_t e = c->scratch_sync();
+    if (!e) e = hipStreamSynchronize(st);
+    if (!e) e = c->ci_ws.ensure(need);
+    if (e) return c->hip_fail(e, "chunk index workspace");
+  }
+  return m ? confirm_ws(c, m, st) : SDCAS_OK;
+}
+static int index_io(sdcas_ctx* c, size_t bytes, hipStream_t st) {
+  if (bytes <= c->ci_io.cap) return SDCAS_OK;
+  hipError_t e = c->scratch_sync();
+  if (!e) e = hipStreamSynchronize(st);
+  if (!e) e = c->ci_io.ensure(bytes);
+  return e ? c->hip_fail(e, "chunk index buffers") : SDCAS_OK;
+}
+
+int sdcas_dev_chunk_index_match(sdcas_ctx* c, const uint64_t* d_idx_keys, const uint8_t* d_idx_digests32,
+                                const uint64_t* d_idx_values, const uint32_t* d_idx_dir, uint64_t n, uint32_t bits,
+                                const uint64_t* d_keys, const uint8_t* d_digests32, const uint8_t* d_valid, size_t m,
+                                int64_t* d_out_pos, uint64_t* d_out_value, uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_view_args(c, "dev_chunk_index_match", d_idx_keys, d_idx_digests32, d_idx_dir, n, bits)) return rc;
+  if (int rc = index_batch_args(c, "dev_chunk_index_match", d_keys, d_digests32, m)) return rc;
+  if ((((uintptr_t)d_idx_digests32 | (uintptr_t)d_digests32) & 15) ||
+      (((uintptr_t)d_idx_keys | (uintptr_t)d_idx_values | (uintptr_t)d_keys | (uintptr_t)d_out_pos |
+        (uintptr_t)d_out_value | (uintptr_t)d_counts) & 7) ||
+      ((uintptr_t)d_idx_dir & 3))
+    return c->fail(SDCAS_E_INVALID, "dev_chunk_index_match: an array is misaligned (digests 16 B, directory 4 B, others 8 B)");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  if (m == 0) {
+    if (d_counts && (e = hipMemsetAsync(d_counts, 0, kIndexMatchCounts * sizeof(uint64_t), call.st)))
+      return c->hip_fail(e, "counts");
+    return SDCAS_OK;
+  }
+  const IndexView v{d_idx_keys, d_idx_digests32, d_idx_values, d_idx_dir, (uint32_t)n, bits};
+  e = index_match(v, d_keys, d_digests32, d_valid, (uint32_t)m, d_out_pos, d_out_value, (unsigned long long*)d_counts,
+                  call.st);
+  return e ? c->hip_fail(e, "dev_chunk_index_match") : SDCAS_OK;
+}
+
+namespace {
+// byte offsets of consecutive 16-byte aligned parts of one buffer
+struct Parts {
+  size_t o = 0;
+  size_t take(size_t bytes) {
+    const size_t at = o;
+    o += (bytes + 15) & ~(size_t)15;
+    return at;
+  }
+};
+}  // namespace
+
+int sdcas_chunk_index_match(sdcas_ctx* c, const uint64_t* idx_keys, const uint8_t* idx_digests32,
+                            const uint64_t* idx_values, const uint32_t* idx_dir, uint64_t n, uint32_t bits,
+                            const uint64_t* keys, const uint8_t* digests32, const uint8_t* valid, size_t m,
+                            int64_t* out_pos, uint64_t* out_value, sdcas_index_match_counts* out_counts) {
+  static_assert(sizeof(sdcas_index_match_counts) == kIndexMatchCounts * sizeof(uint64_t), "four u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_view_args(c, "chunk_index_match", idx_keys, idx_digests32, idx_dir, n, bits)) return rc;
+  if (int rc = index_batch_args(c, "chunk_index_match", keys, digests32, m)) return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  if (m == 0) return SDCAS_OK;
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = call.st;
+  const size_t dir_bytes = n ? 4 * (size_t)index_dir_slots(bits) : 0;
+  Parts p;
+  const size_t o_ik = p.take(8 * n), o_id = p.take(32 * n), o_iv = p.take(8 * n), o_dir = p.take(dir_bytes),
+               o_k = p.take(8 * m), o_d = p.take(32 * m), o_v = p.take(m), o_pos = p.take(8 * m),
+               o_val = p.take(8 * m), o_cts = p.take(8 * kIndexMatchCounts);
+  if (int rc = index_io(c, p.o, st)) return rc;
+  uint8_t* io = c->ci_io.p;
+  if ((n && ((e = hipMemcpyAsync(io + o_ik, idx_keys, 8 * n, hipMemcpyHostToDevice, st)) ||
+             (e = hipMemcpyAsync(io + o_id, idx_digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
+             (idx_values && (e = hipMemcpyAsync(io + o_iv, idx_values, 8 * n, hipMemcpyHostToDevice, st))) ||
+             (e = hipMemcpyAsync(io + o_dir, idx_dir, dir_bytes, hipMemcpyHostToDevice, st)))) ||
+      (e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
+      (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
+      (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))
+    return c->hip_fail(e, "chunk_index_match H2D");
+  const IndexView v{reinterpret_cast<const uint64_t*>(io + o_ik), io + o_id,
+                    idx_values ? reinterpret_cast<const uint64_t*>(io + o_iv) : nullptr,
+                    reinterpret_cast<const uint32_t*>(io + o_dir), (uint32_t)n, bits};
+  if ((e = index_match(v, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d, valid ? io + o_v : nullptr,
+                       (uint32_t)m, out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr,
+                       out_value ? reinterpret_cast<uint64_t*>(io + o_val) : nullptr,
+                       out_counts ? reinterpret_cast<unsigned long long*>(io + o_cts) : nullptr, st)))
+    return c->hip_fail(e, "chunk_index_match");
+  if ((out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
+      (out_value && (e = hipMemcpyAsync(out_value, io + o_val, 8 * m, hipMemcpyDeviceToHost, st))) ||
+      (out_counts && (e = hipMemcpyAsync(out_counts, io + o_cts, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
+    return c->hip_fail(e, "chunk_index_match D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_index_match sync");
+  return SDCAS_OK;
+}
+
+int sdcas_dev_chunk_index_add(sdcas_ctx* c, const uint64_t* d_old_keys, const uint8_t* d_old_digests32,
+                              const uint64_t* d_old_values, const uint32_t* d_old_dir, uint64_t n_old,
+                              uint32_t bits_old, const uint64_t* d_keys, const uint8_t* d_digests32,
+                              const uint64_t* d_values, const uint8_t* d_valid, size_t m, uint64_t* d_new_keys,
+                              uint8_t* d_new_digests32, uint64_t* d_new_values, uint32_t* d_new_dir,
+                              uint32_t bits_new, int64_t* d_out_pos, uint8_t* d_out_flags, uint64_t* d_counts,
+                              void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_add_args(c, "dev_chunk_index_add", d_old_keys, d_old_digests32, d_old_values, d_old_dir, n_old,
+                              bits_old, d_keys, d_digests32, m, d_new_keys, d_new_digests32, d_new_values, d_new_dir,
+                              bits_new))
+    return rc;
+  if ((((uintptr_t)d_old_digests32 | (uintptr_t)d_digests32 | (uintptr_t)d_new_digests32) & 15) ||
+      (((uintptr_t)d_old_keys | (uintptr_t)d_old_values | (uintptr_t)d_keys | (uintptr_t)d_values |
+        (uintptr_t)d_new_keys | (uintptr_t)d_new_values | (uintptr_t)d_out_pos | (uintptr_t)d_counts) & 7) ||
+      (((uintptr_t)d_old_dir | (uintptr_t)d_new_dir) & 3))
+    return c->fail(SDCAS_E_INVALID, "dev_chunk_index_add: an array is misaligned (digests 16 B, directories 4 B, others 8 B)");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = index_add_ws(c, m, call.st)) return rc;
+  const IndexView old{d_old_keys, d_old_digests32, d_old_values, d_old_dir, (uint32_t)n_old, bits_old};
+  const IndexOut out{d_new_keys, d_new_digests32, d_new_values, d_new_dir, bits_new};
+  hipError_t e = index_add(c->ci_ws.p, c->cf_ws.p, old, d_keys, d_digests32, d_values, d_valid, (uint32_t)m, out,
+                           d_out_pos, d_out_flags, (unsigned long long*)d_counts, call.st);
+  return e ? c->hip_fail(e, "dev_chunk_index_add") : SDCAS_OK;
+}
+
+int sdcas_chunk_index_add(sdcas_ctx* c, const uint64_t* old_keys, const uint8_t* old_digests32,
+                          const uint64_t* old_values, const uint32_t* old_dir, uint64_t n_old, uint32_t bits_old,
+                          const uint64_t* keys, const uint8_t* digests32, const uint64_t* values,
+                          const uint8_t* valid, size_t m, uint64_t* new_keys, uint8_t* new_digests32,
+                          uint64_t* new_values, uint32_t* new_dir, uint32_t bits_new, int64_t* out_pos,
+                          uint8_t* out_flags, sdcas_index_add_counts* out_counts) {
+  static_assert(sizeof(sdcas_index_add_counts) == kIndexAddCounts * sizeof(uint64_t), "six u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_add_args(c, "chunk_index_add", old_keys, old_digests32, old_values, old_dir, n_old, bits_old, keys,
+                              digests32, m, new_keys, new_digests32, new_values, new_dir, bits_new))
+    return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = call.st;
+  const size_t n = n_old, cap = n_old + m;
+  const size_t odir_bytes = n ? 4 * (size_t)index_dir_slots(bits_old) : 0, ndir_bytes = 4 * (size_t)index_dir_slots(bits_new);
+  Parts p;
+  const size_t o_ok = p.take(8 * n), o_od = p.take(32 * n), o_ov = p.take(8 * n), o_odir = p.take(odir_bytes),
+               o_k = p.take(8 * m), o_d = p.take(32 * m), o_val = p.take(8 * m), o_v = p.take(m),
+               o_nk = p.take(8 * cap), o_nd = p.take(32 * cap), o_nv = p.take(8 * cap), o_ndir = p.take(ndir_bytes),
+               o_pos = p.take(8 * m), o_fl = p.take(m), o_cts = p.take(8 * kIndexAddCounts);
+  if (int rc = index_io(c, p.o, st)) return rc;
+  if (int rc = index_add_ws(c, m, st)) return rc;
+  uint8_t* io = c->ci_io.p;
+  if ((n && ((e = hipMemcpyAsync(io + o_ok, old_keys, 8 * n, hipMemcpyHostToDevice, st)) ||
+             (e = hipMemcpyAsync(io + o_od, old_digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
+             (old_values && (e = hipMemcpyAsync(io + o_ov, old_values, 8 * n, hipMemcpyHostToDevice, st))) ||
+             (e = hipMemcpyAsync(io + o_odir, old_dir, odir_bytes, hipMemcpyHostToDevice, st)))) ||
+      (m && ((e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
+             (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
+             (values && (e = hipMemcpyAsync(io + o_val, values, 8 * m, hipMemcpyHostToDevice, st))) ||
+             (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))))
+    return c->hip_fail(e, "chunk_index_add H2D");
+  const IndexView old{reinterpret_cast<const uint64_t*>(io + o_ok), io + o_od,
+                      old_values ? reinterpret_cast<const uint64_t*>(io + o_ov) : nullptr,
+                      reinterpret_cast<const uint32_t*>(io + o_odir), (uint32_t)n, bits_old};
+  const IndexOut out{reinterpret_cast<uint64_t*>(io + o_nk), io + o_nd, reinterpret_cast<uint64_t*>(io + o_nv),
+                     reinterpret_cast<uint32_t*>(io + o_ndir), bits_new};
+  if ((e = index_add(c->ci_ws.p, c->cf_ws.p, old, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d,
+                     values ? reinterpret_cast<const uint64_t*>(io + o_val) : nullptr, valid ? io + o_v : nullptr,
+                     (uint32_t)m, out, out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr,
+                     out_flags ? io + o_fl : nullptr, reinterpret_cast<unsigned long long*>(io + o_cts), st)))
+    return c->hip_fail(e, "chunk_index_add");
+  // the counts down first: they say how many entries of the new arrays follow
+  sdcas_index_add_counts cts;
+  if ((e = hipMemcpyAsync(&cts, io + o_cts, sizeof cts, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
+    return c->hip_fail(e, "chunk_index_add counts");
+  const size_t nn = (size_t)cts.entries_new;
+  if (nn > cap) return c->fail(SDCAS_E_HIP, "chunk_index_add: counts out of range");
+  if ((nn && ((e = hipMemcpyAsync(new_keys, io + o_nk, 8 * nn, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(new_digests32, io + o_nd, 32 * nn, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(new_values, io + o_nv, 8 * nn, hipMemcpyDeviceToHost, st)))) ||
+      (e = hipMemcpyAsync(new_dir, io + o_ndir, ndir_bytes, hipMemcpyDeviceToHost, st)) ||
+      (m && out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
+      (m && out_flags && (e = hipMemcpyAsync(out_flags, io + o_fl, m, hipMemcpyDeviceToHost, st))))
+    return c->hip_fail(e, "chunk_index_add D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_index_add sync");
+  if (out_counts) *out_counts = cts;
   return SDCAS_OK;
 }
 

@@ -95,6 +95,7 @@ class Engine:
     def __init__(self, device: int = 0, io_threads: int = 0, staging_bytes: int = 0, progress=None, cancel=None,
                  direct_io=False):
         self.L = N.load()
+        self.device_ordinal = int(device)
         self._cb = self._progress_fn(progress)
         self._cancel = cancel
         opts = N.Options(device, io_threads, N.SDCAS_OPT_DIRECT_IO if direct_io else 0, staging_bytes, self._cb,
@@ -718,7 +719,198 @@ class Engine:
                 "chunk_file": fl, "keys": keys, "digests": dig, "rep": rep, "chunk_counts": ccounts,
                 "sharing_counts": scounts}
 
+    # -- the chunk index: a batch's chunks against the chunks stored before ------------
+    @staticmethod
+    def chunk_index_dir_bits(n):
+        """sdcas_chunk_index_dir_bits (no GPU): the recommended directory width
+        for an index of n entries"""
+        return int(N.load().sdcas_chunk_index_dir_bits(int(n)))
+
+    @staticmethod
+    def chunk_index_check(keys, digests, dir, bits):
+        """sdcas_chunk_index_check (no GPU) over host arrays -> (rc, first_bad):
+        (SDCAS_OK, None) for an index as include/sdcas.h defines it,
+        (SDCAS_E_INVALID, the first entry or directory slot that is wrong),
+        (SDCAS_E_CAPACITY, None) beyond the limits"""
+        keys, digests, dir = _arr(keys, np.uint64), _arr(digests, np.uint8), _arr(dir, np.uint32)
+        n = keys.size
+        if digests.size != 32 * n:
+            raise ValueError(f"chunk_index_check: {n} keys, {digests.size} digest bytes")
+        if int(bits) <= N.SDCAS_INDEX_MAX_BITS and dir.size != (1 << int(bits)) + 1:
+            raise ValueError(f"chunk_index_check: {dir.size} directory slots for {int(bits)} bits")
+        bad = ctypes.c_uint64(0)
+        rc = N.load().sdcas_chunk_index_check(_ptr(keys), _ptr(digests), _ptr(dir), n, int(bits), ctypes.byref(bad))
+        return rc, int(bad.value) if rc == N.SDCAS_E_INVALID else None
+
+    @staticmethod
+    def _index_arrays(index, who):
+        keys, digests, values, dir, bits = index
+        keys, digests, dir = _arr(keys, np.uint64), _arr(digests, np.uint8), _arr(dir, np.uint32)
+        values = None if values is None else _arr(values, np.uint64)
+        n = keys.size
+        if digests.size != 32 * n or (values is not None and values.size != n):
+            raise ValueError(f"{who}: {n} index keys, {digests.size} digest bytes")
+        if n and dir.size != (1 << int(bits)) + 1:
+            raise ValueError(f"{who}: {dir.size} directory slots for {int(bits)} bits")
+        return keys, digests, values, dir, int(bits)
+
+    @staticmethod
+    def _index_batch(keys, digests, valid, who):
+        keys, digests = _arr(keys, np.uint64), _arr(digests, np.uint8)
+        m = keys.size
+        if digests.size != 32 * m:
+            raise ValueError(f"{who}: {m} keys, {digests.size} digest bytes")
+        va = None if valid is None else _arr(valid, np.uint8)
+        if va is not None and va.size != m:
+            raise ValueError(f"{who}: {m} keys, {va.size} valid flags")
+        return keys, digests, va
+
+    def chunk_index_match(self, index, keys, digests, valid=None):
+        """sdcas_chunk_index_match over host arrays. index: (keys uint64[n],
+        digests uint8[n, 32], values uint64[n] or None, dir uint32[2^bits + 1],
+        bits) -> (pos int64[m]: the entry with the query's key and digest or
+        -1, value uint64[m]: its value or 0, counts: dict of
+        sdcas_index_match_counts' four fields)"""
+        ik, idg, iv, idir, bits = self._index_arrays(index, "chunk_index_match")
+        keys, digests, va = self._index_batch(keys, digests, valid, "chunk_index_match")
+        m = keys.size
+        pos, value = np.zeros(m, np.int64), np.zeros(m, np.uint64)
+        counts = N.IndexMatchCounts()
+        self._check(self.L.sdcas_chunk_index_match(self.ctx, _ptr(ik), _ptr(idg), _ptr(iv), _ptr(idir), ik.size, bits,
+                                                   _ptr(keys), _ptr(digests), _ptr(va), m, _ptr(pos), _ptr(value),
+                                                   ctypes.byref(counts)), "sdcas_chunk_index_match")
+        return pos, value, counts.as_dict()
+
+    def chunk_index_add(self, index, keys, digests, values, valid=None, bits_new=None):
+        """sdcas_chunk_index_add over host arrays: the sorted distinct union
+        of the index (chunk_index_match's tuple) and the batch's valid pairs,
+        with its directory at bits_new (None: the recommended width for n + m)
+        -> (new index tuple, trimmed to entries_new, pos int64[m], flags
+        uint8[m]: SDCAS_INDEX_HIT / ADDED / SKIPPED or 0, counts: dict of
+        sdcas_index_add_counts' six fields)"""
+        ik, idg, iv, idir, bits = self._index_arrays(index, "chunk_index_add")
+        keys, digests, va = self._index_batch(keys, digests, valid, "chunk_index_add")
+        m, n = keys.size, ik.size
+        values = None if values is None else _arr(values, np.uint64)
+        if values is not None and values.size != m:
+            raise ValueError(f"chunk_index_add: {m} keys, {values.size} values")
+        if bits_new is None:
+            bits_new = self.chunk_index_dir_bits(n + m)
+        bits_new = int(bits_new)
+        if not 0 <= bits_new <= N.SDCAS_INDEX_MAX_BITS:
+            raise N.SdcasError(N.SDCAS_E_CAPACITY, f"chunk_index_add: a directory of {bits_new} bits")
+        nk, nd, nv = np.zeros(n + m, np.uint64), np.zeros((n + m, 32), np.uint8), np.zeros(n + m, np.uint64)
+        ndir = np.zeros((1 << bits_new) + 1, np.uint32)
+        pos, flags = np.zeros(m, np.int64), np.zeros(m, np.uint8)
+        counts = N.IndexAddCounts()
+        self._check(self.L.sdcas_chunk_index_add(self.ctx, _ptr(ik), _ptr(idg), _ptr(iv), _ptr(idir), n, bits,
+                                                 _ptr(keys), _ptr(digests), _ptr(values), _ptr(va), m,
+                                                 nk.ctypes.data, nd.ctypes.data, nv.ctypes.data, ndir.ctypes.data,
+                                                 bits_new, _ptr(pos), _ptr(flags), ctypes.byref(counts)),
+                    "sdcas_chunk_index_add")
+        e = int(counts.entries_new)
+        return (nk[:e].copy(), nd[:e].copy(), nv[:e].copy(), ndir, bits_new), pos, flags, counts.as_dict()
+
+    def similar_files_indexed(self, paths, file_ids, index, params=None, window_bytes=256 << 20):
+        """similar_files_streamed against what earlier calls stored: the files
+        are chunked through chunk_stream, their chunks confirmed within the
+        batch, matched against `index` (a ChunkIndex) and then added to it
+        with the value file_ids[chunk_file]. The origin of a chunk is the
+        stored value when the index holds it, else the id of the file of its
+        lowest copy in the batch; `peer` is a FILE ID (from file_ids or a
+        stored value; ties go to the lowest id), -1 for none. Every listed
+        file has its own id, also a path listed twice. -> dict with the per-file
+        arrays "sizes", "new_bytes", "self_bytes", "other_bytes",
+        "indexed_bytes" (the bytes of chunks the index held before the call),
+        "peer", "peer_bytes", and "chunk_counts", "match_counts", "add_counts".
+        For ids ascending in scan order and any split of the files into
+        consecutive calls on one index that started empty, the per-file
+        results are similar_files_streamed's over all the files at once, with
+        its peer mapped through the ids."""
+        import torch
+
+        paths = [os.fspath(p) for p in paths]
+        n = len(paths)
+        ids = _arr(file_ids, np.uint64)
+        if ids.size != n:
+            raise ValueError(f"similar_files_indexed: {n} paths, {ids.size} file ids")
+        if np.unique(ids).size != n:
+            raise ValueError("similar_files_indexed: file ids must be distinct")
+        parts = {k: [] for k in ("chunk_len", "chunk_file", "keys", "digests")}
+        sizes = np.zeros(n, np.uint64)
+        ccounts = dict.fromkeys((name for name, _ in N.ChunkCounts._fields_), 0)
+        for w in self.chunk_stream(paths, window_bytes, params):
+            for k in parts:
+                parts[k].append(w[k])
+            sizes[w["first_file"]:w["first_file"] + w["n_files"]] += w["sizes"]
+            for k, v in w["counts"].items():
+                ccounts[k] += v
+        ln = np.concatenate(parts["chunk_len"] or [np.zeros(0, np.uint64)]).astype(np.uint64)
+        fl = np.concatenate(parts["chunk_file"] or [np.zeros(0, np.uint32)]).astype(np.uint32)
+        keys = np.concatenate(parts["keys"] or [np.zeros(0, np.uint64)]).astype(np.uint64)
+        dig = np.concatenate(parts["digests"] or [np.zeros((0, 32), np.uint8)]).astype(np.uint8)
+        m = keys.size
+        if index.engine is not self:
+            raise ValueError("similar_files_indexed: the index belongs to another engine")
+        with torch.cuda.stream(index.stream):  # the batch goes up once; confirm, match and add run on the index's stream
+            d_keys, d_dig = index._upload(keys, np.int64), index._upload(dig, np.uint8)
+            d_rep = torch.empty(m, dtype=torch.int64, device=index.device)
+            self.dev_confirm_duplicates(d_keys.data_ptr(), d_dig.data_ptr(), 0, m, rep=d_rep.data_ptr(),
+                                        stream=index.stream.cuda_stream)
+            d_pos, d_val, mcounts = index._match_dev(d_keys, d_dig, None)
+            rep, hit, val = d_rep.cpu().numpy(), d_pos.cpu().numpy() >= 0, d_val.cpu().numpy().view(np.uint64)
+            acounts = index._add_dev(d_keys, d_dig, index._upload(ids[fl], np.int64), None)[2]
+        # One pseudo-chunk of length 0 per chunk that is its pair's lowest in
+        # the batch and hits the index, in front of the batch's chunks, owned
+        # by a pseudo file that stands for the stored owner: a batch chunk with
+        # a hit then has its lowest copy there. Files get ordinals by the rank
+        # of their id over the stored owners and the batch's ids, so that the
+        # sharing pass's tie rule (the lowest ordinal) is the lowest id.
+        heads = np.flatnonzero(hit & (rep == np.arange(m)))
+        all_ids = np.union1d(val[heads], ids)
+        ordinal = np.searchsorted(all_ids, ids).astype(np.uint32)
+        nh = heads.size
+        s_file = np.concatenate([np.searchsorted(all_ids, val[heads]).astype(np.uint32), ordinal[fl]])
+        s_len = np.concatenate([np.zeros(nh, np.uint64), ln])
+        slot = np.full(m, -1, np.int64)
+        slot[heads] = np.arange(nh)
+        s_rep = np.concatenate([np.arange(nh, dtype=np.int64), np.where(hit, slot[rep], rep + nh)])
+        new, own, other, peer, peer_bytes, _ = self.chunk_sharing(s_file, s_len, s_rep, all_ids.size)
+        indexed = np.zeros(n, np.uint64)
+        np.add.at(indexed, fl[hit], ln[hit])
+        peer = peer[ordinal]
+        return {"sizes": sizes, "new_bytes": new[ordinal], "self_bytes": own[ordinal], "other_bytes": other[ordinal],
+                "indexed_bytes": indexed, "peer": np.where(peer >= 0, all_ids[np.maximum(peer, 0)].astype(np.int64), -1),
+                "peer_bytes": peer_bytes[ordinal], "chunk_counts": ccounts, "match_counts": mcounts,
+                "add_counts": acounts}
+
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
+    def dev_chunk_index_match(self, idx_keys, idx_digests, idx_values, idx_dir, n, bits, keys, digests, valid, m,
+                              pos=0, value=0, counts=0, stream=0):
+        """chunk_index_match over device arrays (sdcas_dev_chunk_index_match);
+        idx_values, valid and any output may be 0; counts four uint64; nothing
+        waits for the device and no workspace is used"""
+        self._check(self.L.sdcas_dev_chunk_index_match(self.ctx, idx_keys or None, idx_digests or None,
+                                                       idx_values or None, idx_dir or None, int(n), int(bits),
+                                                       keys or None, digests or None, valid or None, int(m),
+                                                       pos or None, value or None, counts or None, stream or None),
+                    "dev_chunk_index_match")
+
+    def dev_chunk_index_add(self, old_keys, old_digests, old_values, old_dir, n_old, bits_old, keys, digests, values,
+                            valid, m, new_keys, new_digests, new_values, new_dir, bits_new, pos=0, flags=0, counts=0,
+                            stream=0):
+        """chunk_index_add over device arrays (sdcas_dev_chunk_index_add): the
+        new arrays hold n_old + m entries (the directory 2^bits_new + 1) and
+        must not overlap the old ones; counts six uint64, entries_new among
+        them; nothing waits for the device once the workspace for m exists"""
+        self._check(self.L.sdcas_dev_chunk_index_add(self.ctx, old_keys or None, old_digests or None,
+                                                     old_values or None, old_dir or None, int(n_old), int(bits_old),
+                                                     keys or None, digests or None, values or None, valid or None,
+                                                     int(m), new_keys or None, new_digests or None,
+                                                     new_values or None, new_dir or None, int(bits_new), pos or None,
+                                                     flags or None, counts or None, stream or None),
+                    "dev_chunk_index_add")
+
     def dev_chunk_windows(self, blob, offs, lens, final, n, max_chunks, max_slots, params=None, file_chunks=0,
                           chunk_off=0, chunk_len=0, chunk_file=0, keys=0, digests=0, consumed=0, counts=0, stream=0):
         """chunk_windows over device arrays (sdcas_dev_chunk_windows):
@@ -881,6 +1073,158 @@ class Engine:
 
 
 _default = None
+
+
+class ChunkIndex:
+    """A chunk index (include/sdcas.h) kept on the device: the (key, digest)
+    pairs of the chunks stored so far, sorted, each with the id of the file
+    that held it first. `match` costs what the batch costs, not what the index
+    holds; `add` merges the batch's unseen pairs in one pass over the index.
+
+    The four arrays are torch tensors on the engine's GPU (keys and values as
+    int64 bit patterns of the uint64 words, the directory as int32); every
+    device call runs on the index's own stream, and a tensor handed to the
+    `_dev` forms must have been made under ``torch.cuda.stream(index.stream)``.
+    """
+
+    def __init__(self, engine, device=None):
+        import torch
+        self.engine = engine
+        self.device = torch.device(device if device is not None else f"cuda:{engine.device_ordinal}")
+        self.stream = torch.cuda.Stream(self.device)
+        self.n, self.bits = 0, 0
+        with torch.cuda.stream(self.stream):
+            self.keys = torch.zeros(0, dtype=torch.int64, device=self.device)
+            self.digests = torch.zeros(0, dtype=torch.uint8, device=self.device)
+            self.values = torch.zeros(0, dtype=torch.int64, device=self.device)
+            self.dir = torch.zeros(2, dtype=torch.int32, device=self.device)
+
+    def _upload(self, a, dtype):
+        """a host array's bytes as a device tensor of `dtype` (a numpy dtype of
+        the same width: uint64 words travel as int64)"""
+        import torch
+        a = np.ascontiguousarray(a).reshape(-1)
+        return torch.from_numpy(a.view(dtype).copy()).to(self.device)
+
+    def _batch(self, keys, digests, valid, who):
+        keys, digests, va = Engine._index_batch(keys, digests, valid, who)
+        return (self._upload(keys, np.int64), self._upload(digests, np.uint8),
+                None if va is None else self._upload(va, np.uint8))
+
+    # -- match ----------------------------------------------------------------------
+    def _match_dev(self, d_keys, d_digests, d_valid):
+        """device tensors in, device tensors out: (pos int64[m], value
+        int64[m]: the uint64's bits, counts dict — reading them is the wait)"""
+        import torch
+        m = d_keys.numel()
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else 0
+        with torch.cuda.stream(self.stream):
+            pos = torch.empty(m, dtype=torch.int64, device=self.device)
+            value = torch.empty(m, dtype=torch.int64, device=self.device)
+            counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+            self.engine.dev_chunk_index_match(p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n,
+                                              self.bits, p(d_keys), p(d_digests), p(d_valid), m, p(pos), p(value),
+                                              counts.data_ptr(), stream=self.stream.cuda_stream)
+            c = [int(v) for v in counts.cpu()]
+        return pos, value, dict(zip((name for name, _ in N.IndexMatchCounts._fields_), c))
+
+    def match(self, keys, digests, valid=None):
+        """only the batch goes up -> (pos int64[m], value uint64[m], counts),
+        as Engine.chunk_index_match"""
+        import torch
+        with torch.cuda.stream(self.stream):
+            d_keys, d_dig, d_valid = self._batch(keys, digests, valid, "ChunkIndex.match")
+            pos, value, counts = self._match_dev(d_keys, d_dig, d_valid)
+            return pos.cpu().numpy(), value.cpu().numpy().view(np.uint64), counts
+
+    # -- add ------------------------------------------------------------------------
+    def _add_dev(self, d_keys, d_digests, d_values, d_valid):
+        """the batch merged in: new arrays of n + m entries, the device add at
+        the recommended width for n + m, entries_new read (the one wait), the
+        arrays swapped -> (pos int64[m], flags uint8[m] device tensors, counts)"""
+        import torch
+        m = d_keys.numel()
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else 0
+        bits_new = self.engine.chunk_index_dir_bits(self.n + m)
+        with torch.cuda.stream(self.stream):
+            if m == 0:  # nothing to merge: the index stays as it is
+                return (torch.empty(0, dtype=torch.int64, device=self.device),
+                        torch.empty(0, dtype=torch.uint8, device=self.device),
+                        dict(zip((name for name, _ in N.IndexAddCounts._fields_), (0, 0, 0, 0, self.n, self.n))))
+            cap = self.n + m
+            keys = torch.empty(cap, dtype=torch.int64, device=self.device)
+            digests = torch.empty(32 * cap, dtype=torch.uint8, device=self.device)
+            values = torch.empty(cap, dtype=torch.int64, device=self.device)
+            dir = torch.empty((1 << bits_new) + 1, dtype=torch.int32, device=self.device)
+            pos = torch.empty(m, dtype=torch.int64, device=self.device)
+            flags = torch.empty(m, dtype=torch.uint8, device=self.device)
+            counts = torch.zeros(6, dtype=torch.int64, device=self.device)
+            self.engine.dev_chunk_index_add(p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n,
+                                            self.bits, p(d_keys), p(d_digests), p(d_values), p(d_valid), m, p(keys),
+                                            p(digests), p(values), dir.data_ptr(), bits_new, p(pos), p(flags),
+                                            counts.data_ptr(), stream=self.stream.cuda_stream)
+            c = [int(v) for v in counts.cpu()]
+            n_new = c[5]
+            if not self.n <= n_new <= cap:
+                raise N.SdcasError(N.SDCAS_E_HIP, f"ChunkIndex.add: {n_new} entries from {self.n} and a batch of {m}")
+            self.keys, self.digests, self.values, self.dir = keys[:n_new], digests[:32 * n_new], values[:n_new], dir
+            self.n, self.bits = n_new, bits_new
+        return pos, flags, dict(zip((name for name, _ in N.IndexAddCounts._fields_), c))
+
+    def add(self, keys, digests, values, valid=None):
+        """-> (pos int64[m]: the pair's entry in the index as it is now, flags
+        uint8[m], counts), as Engine.chunk_index_add"""
+        import torch
+        with torch.cuda.stream(self.stream):
+            d_keys, d_dig, d_valid = self._batch(keys, digests, valid, "ChunkIndex.add")
+            values = _arr(values, np.uint64)
+            if values.size != d_keys.numel():
+                raise ValueError(f"ChunkIndex.add: {d_keys.numel()} keys, {values.size} values")
+            pos, flags, counts = self._add_dev(d_keys, d_dig, self._upload(values, np.int64), d_valid)
+            return pos.cpu().numpy(), flags.cpu().numpy(), counts
+
+    # -- host copies ----------------------------------------------------------------
+    def arrays(self):
+        """-> (keys uint64[n], digests uint8[n, 32], values uint64[n], dir
+        uint32[2^bits + 1], bits) on the host: Engine.chunk_index_match's tuple"""
+        import torch
+        with torch.cuda.stream(self.stream):
+            return (self.keys.cpu().numpy().view(np.uint64), self.digests.cpu().numpy().reshape(-1, 32),
+                    self.values.cpu().numpy().view(np.uint64), self.dir.cpu().numpy().view(np.uint32), self.bits)
+
+    def save(self, path):
+        """the index as one .npz"""
+        keys, digests, values, dir, bits = self.arrays()
+        with open(path, "wb") as f:
+            np.savez(f, keys=keys, digests=digests, values=values, dir=dir, bits=np.uint32(bits))
+
+    @classmethod
+    def load(cls, engine, path, device=None):
+        """an index saved by `save`: checked (sdcas_chunk_index_check) before
+        anything goes to the device; ValueError when it is not an index"""
+        import torch
+        import zipfile
+        try:  # the archive's own checksums catch a byte that changed on disk
+            with np.load(path) as z:
+                keys, digests, values, dir, bits = (z["keys"].astype(np.uint64), z["digests"].astype(np.uint8),
+                                                    z["values"].astype(np.uint64), z["dir"].astype(np.uint32),
+                                                    int(z["bits"]))
+        except (zipfile.BadZipFile, KeyError, EOFError, OSError, ValueError) as e:
+            raise ValueError(f"{path}: not a saved chunk index ({e})") from e
+        n = keys.size
+        if digests.size != 32 * n or values.size != n or not 0 <= bits <= N.SDCAS_INDEX_MAX_BITS or \
+                dir.size != (1 << bits) + 1:
+            raise ValueError(f"{path}: the arrays' sizes do not make an index")
+        rc, bad = Engine.chunk_index_check(keys, digests, dir, bits)
+        if rc != N.SDCAS_OK:
+            raise ValueError(f"{path}: not a chunk index (sdcas error {rc}" +
+                             (f", first at entry or slot {bad})" if bad is not None else ")"))
+        ix = cls(engine, device)
+        with torch.cuda.stream(ix.stream):
+            ix.keys, ix.digests = ix._upload(keys, np.int64), ix._upload(digests, np.uint8)
+            ix.values, ix.dir = ix._upload(values, np.int64), ix._upload(dir, np.int32)
+        ix.n, ix.bits = n, bits
+        return ix
 
 
 def default_engine() -> Engine:

@@ -1849,15 +1849,12 @@ uint64_t read_some(std::FILE* f, uint64_t pos, uint64_t want, std::vector<uint8_
   return total;
 }
 
-}  // namespace
-
-SimilarityReport similarity_report_streamed(Engine& engine, Library& db, const Location& location, const std::string& sub,
-                                            uint64_t window_bytes) {
-  std::vector<FilePathRow> rows;
-  for (FilePathRow& r : db.file_paths_in_location(location.id, sub))
-    if (!r.is_dir) rows.push_back(std::move(r));
+// the chunks of the rows' files, read through windows of at most window_bytes,
+// as one call over the whole files would give them; used[i]: the bytes read of
+// row i's file
+Engine::Chunks chunk_rows_windowed(Engine& engine, const Location& location, const std::vector<FilePathRow>& rows,
+                                   uint64_t window_bytes, std::vector<uint64_t>& used) {
   const size_t n = rows.size();
-  if (n == 0) return SimilarityReport{};
   std::vector<uint64_t> sizes(n, 0);  // a file that cannot be read counts as empty
   for (size_t i = 0; i < n; ++i)
     if (std::FILE* f = std::fopen(full_path(location, rows[i]).c_str(), "rb")) {
@@ -1901,13 +1898,170 @@ SimilarityReport similarity_report_streamed(Engine& engine, Library& db, const L
     }
     if (f) std::fclose(f);
   }
+  return merge_chunk_windows(windows, n, &used);
+}
+
+}  // namespace
+
+SimilarityReport similarity_report_streamed(Engine& engine, Library& db, const Location& location, const std::string& sub,
+                                            uint64_t window_bytes) {
+  std::vector<FilePathRow> rows;
+  for (FilePathRow& r : db.file_paths_in_location(location.id, sub))
+    if (!r.is_dir) rows.push_back(std::move(r));
+  const size_t n = rows.size();
+  if (n == 0) return SimilarityReport{};
   std::vector<uint64_t> used;
-  const Engine::Chunks ch = merge_chunk_windows(windows, n, &used);
+  const Engine::Chunks ch = chunk_rows_windowed(engine, location, rows, window_bytes, used);
   const Engine::Confirm c = engine.confirm_duplicates(ch.keys, ch.digests, {});
   const Engine::Sharing s = engine.chunk_sharing(ch.chunk_file, ch.chunk_len, c.rep, n);
   SimilarityReport out = similarity_report_from(rows, used, s.peer, s.peer_bytes);
   out.chunks = ch.counts;
   out.counts = s.counts;
+  return out;
+}
+
+// ---- the same against the chunks stored before ------------------------------------------
+
+Engine::IndexMatch Engine::chunk_index_match(const ChunkIndexData& index, const std::vector<uint64_t>& keys,
+                                             const std::vector<uint8_t>& digests, const std::vector<uint8_t>& valid) {
+  const size_t n = index.size(), m = keys.size();
+  if (index.digests.size() != 32 * n || index.values.size() != n || index.bits > SDCAS_INDEX_MAX_BITS ||
+      index.dir.size() != (size_t(1) << index.bits) + 1)
+    throw std::invalid_argument("chunk_index_match: the index's arrays do not fit each other");
+  if (digests.size() != 32 * m || (!valid.empty() && valid.size() != m))
+    throw std::invalid_argument("chunk_index_match: keys / digests / valid lengths differ");
+  IndexMatch r;
+  r.pos.assign(m, -1), r.value.assign(m, 0);
+  const int rc = sdcas_chunk_index_match(ctx_, index.keys.data(), index.digests.data(), index.values.data(),
+                                         index.dir.data(), n, index.bits, keys.data(), digests.data(),
+                                         valid.empty() ? nullptr : valid.data(), m, r.pos.data(), r.value.data(),
+                                         &r.counts);
+  if (rc != SDCAS_OK) fail(rc, "sdcas_chunk_index_match");
+  return r;
+}
+
+Engine::IndexAdd Engine::chunk_index_add(const ChunkIndexData& index, const std::vector<uint64_t>& keys,
+                                         const std::vector<uint8_t>& digests, const std::vector<uint64_t>& values,
+                                         const std::vector<uint8_t>& valid) {
+  const size_t n = index.size(), m = keys.size();
+  if (index.digests.size() != 32 * n || index.values.size() != n || index.bits > SDCAS_INDEX_MAX_BITS ||
+      index.dir.size() != (size_t(1) << index.bits) + 1)
+    throw std::invalid_argument("chunk_index_add: the index's arrays do not fit each other");
+  if (digests.size() != 32 * m || values.size() != m || (!valid.empty() && valid.size() != m))
+    throw std::invalid_argument("chunk_index_add: keys / digests / values / valid lengths differ");
+  IndexAdd r;
+  ChunkIndexData& out = r.index;
+  out.bits = sdcas_chunk_index_dir_bits(n + m);
+  out.keys.assign(n + m, 0), out.values.assign(n + m, 0), out.digests.assign(32 * (n + m), 0);
+  out.dir.assign((size_t(1) << out.bits) + 1, 0);
+  r.pos.assign(m, -1), r.flags.assign(m, 0);
+  const int rc = sdcas_chunk_index_add(ctx_, index.keys.data(), index.digests.data(), index.values.data(),
+                                       index.dir.data(), n, index.bits, keys.data(), digests.data(), values.data(),
+                                       valid.empty() ? nullptr : valid.data(), m, out.keys.data(), out.digests.data(),
+                                       out.values.data(), out.dir.data(), out.bits, r.pos.data(), r.flags.data(),
+                                       &r.counts);
+  if (rc != SDCAS_OK) fail(rc, "sdcas_chunk_index_add");
+  const size_t e = r.counts.entries_new;
+  out.keys.resize(e), out.values.resize(e), out.digests.resize(32 * e);
+  return r;
+}
+
+IndexedSharing indexed_sharing(Engine& engine, const Engine::Chunks& chunks, const std::vector<int64_t>& rep,
+                               const Engine::IndexMatch& match, const std::vector<uint64_t>& file_ids) {
+  const size_t m = chunks.chunk_file.size(), n = file_ids.size();
+  if (chunks.chunk_len.size() != m || rep.size() != m || match.pos.size() != m || match.value.size() != m)
+    throw std::invalid_argument("indexed_sharing: the chunk arrays do not fit each other");
+  for (size_t c = 0; c < m; ++c)
+    if (chunks.chunk_file[c] >= n || rep[c] < 0 || (size_t)rep[c] > c)
+      throw std::invalid_argument("indexed_sharing: chunk " + std::to_string(c) + " names no file or no earlier chunk");
+  // Files get ordinals by the rank of their id over the stored owners and the
+  // batch's ids, so that the sharing pass's tie rule (the lowest ordinal) is
+  // the lowest id. One pseudo-chunk of no bytes per chunk that is its pair's
+  // lowest in the batch and is in the index stands in front of the batch's
+  // chunks, owned by the stored owner: a batch chunk the index holds then has
+  // its lowest copy there.
+  std::vector<size_t> heads;
+  std::vector<uint64_t> all_ids(file_ids);
+  for (size_t c = 0; c < m; ++c)
+    if (match.pos[c] >= 0 && (size_t)rep[c] == c) {
+      heads.push_back(c);
+      all_ids.push_back(match.value[c]);
+    }
+  std::sort(all_ids.begin(), all_ids.end());
+  all_ids.erase(std::unique(all_ids.begin(), all_ids.end()), all_ids.end());
+  auto ordinal_of = [&](uint64_t id) { return (uint32_t)(std::lower_bound(all_ids.begin(), all_ids.end(), id) - all_ids.begin()); };
+  std::vector<uint32_t> ordinal(n);
+  for (size_t i = 0; i < n; ++i) ordinal[i] = ordinal_of(file_ids[i]);
+  const size_t nh = heads.size();
+  std::vector<uint32_t> s_file(nh + m);
+  std::vector<uint64_t> s_len(nh + m, 0);
+  std::vector<int64_t> s_rep(nh + m), slot(m, -1);
+  for (size_t h = 0; h < nh; ++h) {
+    s_file[h] = ordinal_of(match.value[heads[h]]);
+    s_rep[h] = (int64_t)h;
+    slot[heads[h]] = (int64_t)h;
+  }
+  for (size_t c = 0; c < m; ++c) {
+    s_file[nh + c] = ordinal[chunks.chunk_file[c]];
+    s_len[nh + c] = chunks.chunk_len[c];
+    s_rep[nh + c] = match.pos[c] >= 0 ? slot[(size_t)rep[c]] : rep[c] + (int64_t)nh;
+  }
+  const Engine::Sharing s = engine.chunk_sharing(s_file, s_len, s_rep, all_ids.size());
+  IndexedSharing out;
+  out.indexed_bytes.assign(n, 0);
+  for (size_t c = 0; c < m; ++c)
+    if (match.pos[c] >= 0) out.indexed_bytes[chunks.chunk_file[c]] += chunks.chunk_len[c];
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t o = ordinal[i];
+    out.new_bytes.push_back(s.new_bytes[o]), out.self_bytes.push_back(s.self_bytes[o]);
+    out.other_bytes.push_back(s.other_bytes[o]), out.peer_bytes.push_back(s.peer_bytes[o]);
+    out.peer.push_back(s.peer[o] < 0 ? -1 : (int64_t)all_ids[(size_t)s.peer[o]]);
+  }
+  return out;
+}
+
+SimilarityReport similarity_report_indexed(Engine& engine, SqliteLibrary& db, const Location& location,
+                                           const std::string& sub, uint64_t window_bytes) {
+  std::set<int32_t> done;
+  for (const auto& f : db.chunk_indexed_files()) done.insert(f.first);
+  std::vector<FilePathRow> rows;  // ascending by id: the order of the scan
+  for (FilePathRow& r : db.file_paths_in_location(location.id, sub))
+    if (!r.is_dir && !done.count(r.id)) rows.push_back(std::move(r));
+  const size_t n = rows.size();
+  if (n == 0) return SimilarityReport{};
+  std::vector<uint64_t> used;
+  const Engine::Chunks ch = chunk_rows_windowed(engine, location, rows, window_bytes, used);
+  const size_t m = ch.keys.size();
+  const Engine::Confirm c = engine.confirm_duplicates(ch.keys, ch.digests, {});
+  const ChunkIndexData index = db.load_chunk_index();
+  const Engine::IndexMatch match = engine.chunk_index_match(index, ch.keys, ch.digests, {});
+  std::vector<uint64_t> file_ids(n), values(m);
+  for (size_t i = 0; i < n; ++i) file_ids[i] = (uint64_t)rows[i].id;
+  for (size_t k = 0; k < m; ++k) values[k] = file_ids[ch.chunk_file[k]];
+  const IndexedSharing s = indexed_sharing(engine, ch, c.rep, match, file_ids);
+  const Engine::IndexAdd add = engine.chunk_index_add(index, ch.keys, ch.digests, values, {});
+  // what the add stored: the pairs whose value it took, with their rows
+  std::vector<uint8_t> digests;
+  std::vector<int32_t> owners;
+  for (size_t k = 0; k < m; ++k)
+    if (add.flags[k] & SDCAS_INDEX_ADDED) {
+      digests.insert(digests.end(), ch.digests.begin() + 32 * k, ch.digests.begin() + 32 * (k + 1));
+      owners.push_back((int32_t)values[k]);
+    }
+  std::vector<std::pair<int32_t, uint64_t>> files;
+  for (size_t i = 0; i < n; ++i) files.emplace_back(rows[i].id, used[i]);
+  db.append_chunk_index(digests, owners, files);
+  SimilarityReport out;
+  for (size_t i = 0; i < n; ++i)
+    if (s.peer[i] >= 0) out.pairs.push_back(SimilarityReport::Pair{rows[i].id, (int32_t)s.peer[i], s.peer_bytes[i], used[i]});
+  std::sort(out.pairs.begin(), out.pairs.end(), [](const SimilarityReport::Pair& a, const SimilarityReport::Pair& b) {
+    return a.shared_bytes != b.shared_bytes ? a.shared_bytes > b.shared_bytes : a.file_path_id < b.file_path_id;
+  });
+  out.chunks = ch.counts;
+  out.counts.files = n, out.counts.chunks = m, out.counts.files_with_peer = out.pairs.size();
+  out.counts.distinct_chunks = add.counts.added, out.counts.total_bytes = ch.counts.total_bytes;
+  for (size_t k = 0; k < m; ++k)
+    if (add.flags[k] & SDCAS_INDEX_ADDED) out.counts.stored_bytes += ch.chunk_len[k];
   return out;
 }
 

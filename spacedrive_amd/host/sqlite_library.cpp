@@ -762,4 +762,87 @@ void SqliteLibrary::set_integrity_checksum(int32_t id, const std::string& checks
   x.done(x.set_checksum);
 }
 
+// ---- the chunk index's tables --------------------------------------------------------
+
+namespace {
+// WITHOUT ROWID: the primary key is the table's own b-tree, so ORDER BY digest
+// reads it in place
+const char* const kChunkTables =
+    "CREATE TABLE IF NOT EXISTS chunk_index (digest BLOB PRIMARY KEY, file_path_id INTEGER NOT NULL) WITHOUT ROWID;"
+    "CREATE TABLE IF NOT EXISTS chunk_indexed_file (file_path_id INTEGER PRIMARY KEY, size INTEGER NOT NULL)";
+}  // namespace
+
+ChunkIndexData SqliteLibrary::load_chunk_index() {
+  Impl& x = *d_;
+  x.exec(kChunkTables);
+  ChunkIndexData out;
+  Stmt st;
+  x.prepare(st, "SELECT digest, file_path_id FROM chunk_index ORDER BY digest");
+  int rc;
+  while ((rc = sqlite3_step(st.s)) == SQLITE_ROW) {
+    const void* blob = sqlite3_column_blob(st.s, 0);
+    if (!blob || sqlite3_column_bytes(st.s, 0) != 32)
+      throw LibraryError(SDCAS_E_INVALID, "chunk_index: entry " + std::to_string(out.size()) + " holds no 32-byte digest");
+    const uint8_t* d = (const uint8_t*)blob;
+    out.keys.push_back(from_be64(d, 8));
+    out.digests.insert(out.digests.end(), d, d + 32);
+    out.values.push_back((uint64_t)sqlite3_column_int64(st.s, 1));
+  }
+  if (rc != SQLITE_DONE) x.fail("chunk_index");
+  // the directory at the recommended width, by one pass over the sorted keys
+  const uint64_t n = out.size();
+  out.bits = sdcas_chunk_index_dir_bits(n);
+  out.dir.assign((size_t(1) << out.bits) + 1, 0);
+  for (uint64_t i = 0; i < n && out.bits; ++i) ++out.dir[(size_t)(out.keys[i] >> (64 - out.bits)) + 1];
+  for (size_t j = 1; j < out.dir.size(); ++j) out.dir[j] += out.dir[j - 1];
+  out.dir.back() = (uint32_t)n;
+  uint64_t bad = 0;
+  if (int e = sdcas_chunk_index_check(out.keys.data(), out.digests.data(), out.dir.data(), n, out.bits, &bad))
+    throw LibraryError(e, "chunk_index: not an index at entry or slot " + std::to_string(bad));
+  return out;
+}
+
+std::vector<std::pair<int32_t, uint64_t>> SqliteLibrary::chunk_indexed_files() {
+  Impl& x = *d_;
+  x.exec(kChunkTables);
+  std::vector<std::pair<int32_t, uint64_t>> out;
+  Stmt st;
+  x.prepare(st, "SELECT file_path_id, size FROM chunk_indexed_file ORDER BY file_path_id");
+  int rc;
+  while ((rc = sqlite3_step(st.s)) == SQLITE_ROW)
+    out.emplace_back((int32_t)sqlite3_column_int64(st.s, 0), (uint64_t)sqlite3_column_int64(st.s, 1));
+  if (rc != SQLITE_DONE) x.fail("chunk_indexed_file");
+  return out;
+}
+
+void SqliteLibrary::append_chunk_index(const std::vector<uint8_t>& digests, const std::vector<int32_t>& owners,
+                                       const std::vector<std::pair<int32_t, uint64_t>>& files) {
+  if (digests.size() != 32 * owners.size())
+    throw std::invalid_argument("append_chunk_index: 32 digest bytes per owner");
+  Impl& x = *d_;
+  x.exec(kChunkTables);
+  if (owners.empty() && files.empty()) return;
+  Stmt chunk, file;
+  x.prepare(chunk, "INSERT INTO chunk_index (digest, file_path_id) VALUES (?1, ?2)");
+  x.prepare(file, "INSERT INTO chunk_indexed_file (file_path_id, size) VALUES (?1, ?2)");
+  x.exec("SAVEPOINT chunk_append");
+  try {
+    for (size_t k = 0; k < owners.size(); ++k) {
+      sqlite3_bind_blob(chunk.s, 1, digests.data() + 32 * k, 32, SQLITE_TRANSIENT);
+      sqlite3_bind_int64(chunk.s, 2, owners[k]);
+      x.done(chunk);
+    }
+    for (const auto& f : files) {
+      sqlite3_bind_int64(file.s, 1, f.first);
+      sqlite3_bind_int64(file.s, 2, (int64_t)f.second);
+      x.done(file);
+    }
+  } catch (...) {
+    sqlite3_reset(chunk.s), sqlite3_reset(file.s);
+    x.exec("ROLLBACK TO chunk_append; RELEASE chunk_append");
+    throw;
+  }
+  x.exec("RELEASE chunk_append");
+}
+
 }  // namespace sdcore
