@@ -1945,6 +1945,25 @@ static const LeafVariant kLeafVariants[] = {
     // from it (hash_chunk_quad_lds, compress_quad_w: no per-round word
     // selects, 453 -> 141 v_cndmask in the kernel)
     PRODS(4 * kSmallTile, k_leaf_tree<4 * kSmallTile, 79, 1, 0, 2, 0, 0, kSmallTile, 3>),
+    // 85-92: 67 with several G steps per asm block (b3_device.h, compress<GA>
+    // with GA % 10 = 3 or 4): 85-88 two G's per block, 89-92 four; within
+    // each four: no nop, s_nop 0 after each group of add3 and of rotates,
+    // after each group of rotates, after each single rotate
+    ABL1(512, k_leaf_tree<512, 379, 1, 1, 2, 2>),
+    ABL1(512, k_leaf_tree<512, 1379, 1, 1, 2, 2>),
+    ABL1(512, k_leaf_tree<512, 2379, 1, 1, 2, 2>),
+    ABL1(512, k_leaf_tree<512, 3379, 1, 1, 2, 2>),
+    ABL1(512, k_leaf_tree<512, 479, 1, 1, 2, 2>),
+    ABL1(512, k_leaf_tree<512, 1479, 1, 1, 2, 2>),
+    ABL1(512, k_leaf_tree<512, 2479, 1, 1, 2, 2>),
+    ABL1(512, k_leaf_tree<512, 3479, 1, 1, 2, 2>),
+    // 93, 94: two / four G's per block, s_nop 0 after every half-rate
+    // instruction (each v_add3_u32 and each v_alignbit_b32)
+    ABL1(512, k_leaf_tree<512, 4379, 1, 1, 2, 2>),
+    ABL1(512, k_leaf_tree<512, 4479, 1, 1, 2, 2>),
+    // 95: 67 with the G block of rounds 2-6 (B3_G_ASM_R: a nop after each
+    // rotate only), what 67 was before B3_G_ASM parked after v_add3_u32 too
+    ABL1(512, k_leaf_tree<512, 679, 1, 1, 2, 2>),
 };
 #undef PROD
 #undef PROD1
@@ -2160,7 +2179,7 @@ constexpr int kDefaultPieceVariant = 19;
 bool piece_variant_available(int v) {
   if (v == 17 || v == 19) return true;
 #ifdef SDCAS_ABLATIONS
-  if (v >= 0 && v <= 20) return true;
+  if (v >= 0 && v <= 31) return true;
 #endif
   return false;
 }
@@ -2195,8 +2214,33 @@ static hipError_t launch_piece_dyn(const uint8_t* blob, const PieceDesc* pieces,
   return hipGetLastError();
 }
 
+// 19 with several G steps per asm block (the leaf variants 85-92's G)
+template <int PF>
+static hipError_t launch_piece_l4(const uint8_t* blob, const PieceDesc* pieces, uint32_t npieces, uint32_t* file_nodes,
+                                  uint32_t* l4, hipStream_t st) {
+  if (!l4) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_piece_l4<PF, 6>), dim3(npieces), dim3(kWG), 0, st, blob, pieces, npieces, file_nodes, l4);
+  hipLaunchKernelGGL((k_piece_top<PF>), dim3((npieces + kTopPieces - 1) / kTopPieces), dim3(kWG), 0, st, pieces,
+                     npieces, l4, file_nodes);
+  return hipGetLastError();
+}
+
 static hipError_t piece_hash_ablation(int v, const uint8_t* blob, const PieceDesc* pieces, uint32_t npieces,
                                       uint32_t* file_nodes, uint32_t* ctr, uint32_t* l4, hipStream_t st) {
+  // 21-28: two G's per block (21-24) or four (25-28), nop placement as 85-92
+  if (v == 21) return launch_piece_l4<359>(blob, pieces, npieces, file_nodes, l4, st);
+  if (v == 22) return launch_piece_l4<1359>(blob, pieces, npieces, file_nodes, l4, st);
+  if (v == 23) return launch_piece_l4<2359>(blob, pieces, npieces, file_nodes, l4, st);
+  if (v == 24) return launch_piece_l4<3359>(blob, pieces, npieces, file_nodes, l4, st);
+  if (v == 25) return launch_piece_l4<459>(blob, pieces, npieces, file_nodes, l4, st);
+  if (v == 26) return launch_piece_l4<1459>(blob, pieces, npieces, file_nodes, l4, st);
+  if (v == 27) return launch_piece_l4<2459>(blob, pieces, npieces, file_nodes, l4, st);
+  if (v == 28) return launch_piece_l4<3459>(blob, pieces, npieces, file_nodes, l4, st);
+  // 29, 30: two / four G's per block, a nop after every half-rate instruction (leaf 93, 94)
+  if (v == 29) return launch_piece_l4<4359>(blob, pieces, npieces, file_nodes, l4, st);
+  if (v == 30) return launch_piece_l4<4459>(blob, pieces, npieces, file_nodes, l4, st);
+  // 31: 19 with the G block of rounds 2-6 (B3_G_ASM_R, leaf 95)
+  if (v == 31) return launch_piece_l4<659>(blob, pieces, npieces, file_nodes, l4, st);
   if (v == 20) {  // 19 at 8 waves/SIMD (64 VGPRs; the spills are outside the full-chunk loop)
     if (!l4) return hipErrorInvalidValue;
     hipLaunchKernelGGL((k_piece_l4<259, 8>), dim3(npieces), dim3(kWG), 0, st, blob, pieces, npieces, file_nodes, l4);

@@ -53,7 +53,9 @@ def main():
     vl = [int(v) for v in a.variants.split(",")] if a.variants else [v for v in range(64) if eng.dev_set_leaf_variant(v)]
     for v in vl:
         assert eng.dev_set_leaf_variant(v), f"variant {v} is not in {N.ABLATION_LIB_PATH if not a.product else N.LIB_PATH}"
-    vs = [(v, int(so)) for v in vl for so in a.sorts.split(",")]
+    # an arm is (variant, sort, position): a variant named twice gives two
+    # arms of identical code (A/A), whose spread is the noise of the A/B
+    vs = [(v, int(so), i) for i, v in enumerate(vl) for so in a.sorts.split(",")]
     outs = {}
     res = {v: [] for v in vs}
     for r in range(a.rounds):
@@ -77,7 +79,7 @@ def main():
         leafs = sorted(x[0] for x in res[v])
         seqs = sorted(x[1] for x in res[v])
         same = np.array_equal(outs[v], ref)
-        print(f"variant {v[0]} sort {v[1]}: leaf med {leafs[len(leafs)//2]:.3f} min {leafs[0]:.3f} ms "
+        print(f"variant {v[0]} sort {v[1]}: leaf med {leafs[len(leafs)//2]:.3f} min {leafs[0]:.3f} max {leafs[-1]:.3f} ms "
               f"({msg / leafs[0] / 1e6:.0f} GB/s), seq med {seqs[len(seqs)//2]:.3f} ms, agree={same}",
               flush=True)
     eng.close()

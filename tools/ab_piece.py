@@ -50,12 +50,14 @@ def main():
     out = torch.zeros((sizes.size, 32), dtype=torch.uint8, device=dev)
     files = np.arange(sizes.size, dtype=np.uint64)
     addrs = np.uint64(blob.data_ptr()) + offs
-    vl = [int(v) for v in a.variants.split(",")]
+    # an arm is (position, variant): a variant named twice gives two arms of
+    # identical code (A/A), whose spread is the noise of the A/B
+    vl = list(enumerate(int(v) for v in a.variants.split(",")))
     res = {v: [] for v in vl}
     digests = {}
     for r in range(a.rounds):
         for v in vl:
-            assert eng.dev_set_piece_variant(v), v
+            assert eng.dev_set_piece_variant(v[1]), v[1]
             eng.dev_profile(True)
             for _ in range(a.reps):
                 eng.dev_stream_begin(sizes)
@@ -71,7 +73,7 @@ def main():
     nbytes = int(sizes.sum())
     for v in vl:
         x = sorted(res[v])
-        print(f"piece variant {v}: med {x[len(x) // 2]:.2f} ms min {x[0]:.2f} ms "
+        print(f"piece variant {v[1]}: med {x[len(x) // 2]:.3f} ms min {x[0]:.3f} max {x[-1]:.3f} ms "
               f"({nbytes / x[0] / 1e6:.0f} GB/s best), agree={np.array_equal(digests[v], ref)}", flush=True)
     eng.close()
 

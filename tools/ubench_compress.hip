@@ -3,10 +3,13 @@
 // Register-only: each lane runs dependent compressions (2 independent streams
 // per lane), 8 waves per SIMD; prints G compressions/s per variant and checks
 // every variant against the reference G (b3_device.h) bit-exactly.
+// "ubench_compress ITERS gsched" runs the schedules with several G's per asm
+// block and every nop placement against variant 11 (profiles/gsched_compress.txt).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 
@@ -95,6 +98,12 @@ __device__ __forceinline__ void g_nop(uint32_t& a, uint32_t& b, uint32_t& c, uin
   if (K == 5) asm volatile(G_NOP_TEXT("", "", NOP1) : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(x), "v"(y));
   if (K == 6) asm volatile(G_ROT_TEXT("", NOP, "", NOP) : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(x), "v"(y));
   if (K == 7) asm volatile(G_ROT_TEXT(NOP, "", NOP, "") : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(x), "v"(y));
+  if (K == 9)  // after v_add3_u32 and v_alignbit_b32 (every half-rate instruction), not after v_add_u32
+    asm volatile("v_add3_u32 %0, %0, %1, %4\n" NOP "v_xor_b32 %3, %3, %0\n v_alignbit_b32 %3, %3, %3, 16\n" NOP
+                 "v_add_u32 %2, %2, %3\n v_xor_b32 %1, %1, %2\n v_alignbit_b32 %1, %1, %1, 12\n" NOP
+                 "v_add3_u32 %0, %0, %1, %5\n" NOP "v_xor_b32 %3, %3, %0\n v_alignbit_b32 %3, %3, %3, 8\n" NOP
+                 "v_add_u32 %2, %2, %3\n v_xor_b32 %1, %1, %2\n v_alignbit_b32 %1, %1, %1, 7\n" NOP
+                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(x), "v"(y));
   if (K == 8) asm volatile(G_NOP_TEXT(NOP, NOP, "") : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(x), "v"(y));
 }
 
@@ -119,7 +128,8 @@ __device__ __forceinline__ void g2_asm(uint32_t& a, uint32_t& b, uint32_t& c, ui
 }
 
 // 9..13 one asm block per G with s_nop 0 after: 9 every instruction, 10
-// xor + alignbit, 11 alignbit, 12 xor, 13 add3/add
+// xor + alignbit, 11 alignbit, 12 xor, 13 add3/add; 18 alignbit + add3 (every
+// half-rate instruction: the product's B3_G_ASM)
 // VAR: 0 reference (add3 + alignbit); 1 add3 -> 2 adds; 2 rot12/rot7 by shifts;
 // 3 all rotations by shifts; 4 = 1 + 2; 5 the four xors as v_bitop3_b32;
 // 6 = 0 with every xor / alignbit as inline asm (same instructions as 5 but
@@ -130,7 +140,7 @@ __device__ __forceinline__ void G(uint32_t& a, uint32_t& b, uint32_t& c, uint32_
     g_asm(a, b, c, d, x, y);
     return;
   }
-  if (VAR >= 9 && VAR <= 17) {
+  if (VAR >= 9 && VAR <= 18) {
     g_nop<VAR - 9>(a, b, c, d, x, y);
     return;
   }
@@ -180,8 +190,123 @@ __device__ __forceinline__ void G(uint32_t& a, uint32_t& b, uint32_t& c, uint32_
     RND(V, __VA_ARGS__) \
   }
 
+// ---- candidate schedules with several G's per asm block (b3_device.h:
+// B3_G2_TEXT, B3_G4_TEXT and their first-column forms) -----------------------
+// MODE 0: no nop; 1: s_nop 0 after each pair (group) of half-rate ops, add3
+// and rotate; 2: after each pair (group) of rotates only; 3: after each single
+// rotate; 4: after each single rotate and each single add3 (every half-rate
+// instruction).
+#define MODE_ASM(TEXT, OPS)                                            \
+  if (MODE == 0) asm volatile(TEXT("", "", "", "") OPS);               \
+  if (MODE == 1) asm volatile(TEXT(B3_NOP, B3_NOP, "", "") OPS);       \
+  if (MODE == 2) asm volatile(TEXT("", B3_NOP, "", "") OPS);           \
+  if (MODE == 3) asm volatile(TEXT("", "", B3_NOP, "") OPS);           \
+  if (MODE == 4) asm volatile(TEXT("", "", B3_NOP, B3_NOP) OPS);
+template <int MODE>
+__device__ __forceinline__ void gp2(uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1, uint32_t& c0, uint32_t& c1,
+                                    uint32_t& d0, uint32_t& d1, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
+  MODE_ASM(B3_G2_TEXT, B3_G2_OPS(a0, a1, b0, b1, c0, c1, d0, d1, x0, y0, x1, y1))
+}
+template <int MODE>
+__device__ __forceinline__ void gp2f(uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1, uint32_t& c0, uint32_t& c1,
+                                     uint32_t& d0, uint32_t& d1, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                                     uint32_t ci0, uint32_t ci1, uint32_t di0, uint32_t di1) {
+  MODE_ASM(B3_G2F_TEXT, B3_G2F_OPS(a0, a1, b0, b1, c0, c1, d0, d1, x0, y0, x1, y1, ci0, ci1, di0, di1))
+}
+// G B three instructions behind G A: B's add3 beside A's add, B's lone xor
+// (after its add3) beside A's second xor, the rotates in pairs. NH follows a
+// lone add3, NR a rotate pair (or the lone rotate at either end).
+#define SA(S) B3_CALL(S, B3_G2_0)
+#define SB(S) B3_CALL(S, B3_G2_1)
+#define G2S_TEXT(NH, NR, NRI, NHI)                                                                \
+  SA(B3_ST0) NH NHI SA(B3_ST1) SA(B3_ST2) NRI NR                                                 \
+  SB(B3_ST0) NH NHI SA(B3_ST3) SB(B3_ST1) SA(B3_ST4) SA(B3_ST5) NRI SB(B3_ST2) NRI NR            \
+  SA(B3_ST6) NH NHI SB(B3_ST3) SA(B3_ST7) SB(B3_ST4) SA(B3_ST8) NRI SB(B3_ST5) NRI NR            \
+  SB(B3_ST6) NH NHI SA(B3_ST9) SB(B3_ST7) SA(B3_ST10) SA(B3_ST11) NRI SB(B3_ST8) NRI NR          \
+  SB(B3_ST9) SB(B3_ST10) SB(B3_ST11) NRI NR
+template <int MODE>
+__device__ __forceinline__ void gs2(uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1, uint32_t& c0, uint32_t& c1,
+                                    uint32_t& d0, uint32_t& d1, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
+  MODE_ASM(G2S_TEXT, B3_G2_OPS(a0, a1, b0, b1, c0, c1, d0, d1, x0, y0, x1, y1))
+}
+template <int MODE>
+__device__ __forceinline__ void gp4(uint32_t& a0, uint32_t& a1, uint32_t& a2, uint32_t& a3, uint32_t& b0, uint32_t& b1,
+                                    uint32_t& b2, uint32_t& b3, uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3,
+                                    uint32_t& d0, uint32_t& d1, uint32_t& d2, uint32_t& d3, uint32_t x0, uint32_t y0,
+                                    uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2, uint32_t x3, uint32_t y3) {
+  MODE_ASM(B3_G4_TEXT,
+           B3_G4_OPS(a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3, d0, d1, d2, d3, x0, y0, x1, y1, x2, y2, x3, y3))
+}
+template <int MODE>
+__device__ __forceinline__ void gp4f(uint32_t& a0, uint32_t& a1, uint32_t& a2, uint32_t& a3, uint32_t& b0, uint32_t& b1,
+                                     uint32_t& b2, uint32_t& b3, uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3,
+                                     uint32_t& d0, uint32_t& d1, uint32_t& d2, uint32_t& d3, uint32_t x0, uint32_t y0,
+                                     uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2, uint32_t x3, uint32_t y3,
+                                     uint32_t di0, uint32_t di1, uint32_t di2, uint32_t di3) {
+  MODE_ASM(B3_G4F_TEXT, B3_G4F_OPS(a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3, d0, d1, d2, d3, x0, y0, x1, y1, x2,
+                                   y2, x3, y3, di0, di1, di2, di3))
+}
+
+// Variants 100 + 10 * SHAPE + MODE (+ 50: the first round's column steps in
+// their copy-free form): SHAPE 0 = g2 paired (two blocks per half-round), 1 =
+// g4 (one block per half-round), 2 = g2 staggered.
+#define RNDS(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15)                               \
+  if (SHAPE == 0) {                                                                                             \
+    gp2<MODE>(v0, v1, v4, v5, v8, v9, v12, v13, m[s0], m[s1], m[s2], m[s3]);                                      \
+    gp2<MODE>(v2, v3, v6, v7, v10, v11, v14, v15, m[s4], m[s5], m[s6], m[s7]);                                    \
+    gp2<MODE>(v0, v1, v5, v6, v10, v11, v15, v12, m[s8], m[s9], m[s10], m[s11]);                                  \
+    gp2<MODE>(v2, v3, v7, v4, v8, v9, v13, v14, m[s12], m[s13], m[s14], m[s15]);                                  \
+  } else if (SHAPE == 2) {                                                                                      \
+    gs2<MODE>(v0, v1, v4, v5, v8, v9, v12, v13, m[s0], m[s1], m[s2], m[s3]);                                      \
+    gs2<MODE>(v2, v3, v6, v7, v10, v11, v14, v15, m[s4], m[s5], m[s6], m[s7]);                                    \
+    gs2<MODE>(v0, v1, v5, v6, v10, v11, v15, v12, m[s8], m[s9], m[s10], m[s11]);                                  \
+    gs2<MODE>(v2, v3, v7, v4, v8, v9, v13, v14, m[s12], m[s13], m[s14], m[s15]);                                  \
+  } else {                                                                                                      \
+    gp4<MODE>(v0, v1, v2, v3, v4, v5, v6, v7, v8, v9, v10, v11, v12, v13, v14, v15, m[s0], m[s1], m[s2], m[s3],  \
+              m[s4], m[s5], m[s6], m[s7]);                                                                      \
+    gp4<MODE>(v0, v1, v2, v3, v5, v6, v7, v4, v10, v11, v8, v9, v15, v12, v13, v14, m[s8], m[s9], m[s10],       \
+              m[s11], m[s12], m[s13], m[s14], m[s15]);                                                          \
+  }
+
+template <int V>
+__device__ __forceinline__ void comp_sched(uint32_t (&cv)[8], const uint32_t (&m)[16], uint32_t ctr) {
+  constexpr bool FIRST = V >= 150;
+  constexpr int SHAPE = ((V - 100) % 50) / 10, MODE = V % 10;
+  uint32_t v0 = cv[0], v1 = cv[1], v2 = cv[2], v3 = cv[3], v4 = cv[4], v5 = cv[5], v6 = cv[6], v7 = cv[7];
+  uint32_t v8, v9, v10, v11, v12, v13, v14, v15;
+  if (FIRST) {
+    const uint32_t z = 0, l = 64;  // comp()'s v13, v14, v15
+    if (SHAPE == 0) {
+      gp2f<MODE>(v0, v1, v4, v5, v8, v9, v12, v13, m[0], m[1], m[2], m[3], IV0, IV1, ctr, z);
+      gp2f<MODE>(v2, v3, v6, v7, v10, v11, v14, v15, m[4], m[5], m[6], m[7], IV2, IV3, l, z);
+      gp2<MODE>(v0, v1, v5, v6, v10, v11, v15, v12, m[8], m[9], m[10], m[11]);
+      gp2<MODE>(v2, v3, v7, v4, v8, v9, v13, v14, m[12], m[13], m[14], m[15]);
+    } else {
+      gp4f<MODE>(v0, v1, v2, v3, v4, v5, v6, v7, v8, v9, v10, v11, v12, v13, v14, v15, m[0], m[1], m[2], m[3], m[4],
+                 m[5], m[6], m[7], ctr, z, l, z);
+      gp4<MODE>(v0, v1, v2, v3, v5, v6, v7, v4, v10, v11, v8, v9, v15, v12, v13, v14, m[8], m[9], m[10], m[11], m[12],
+                m[13], m[14], m[15]);
+    }
+  } else {
+    v8 = IV0; v9 = IV1; v10 = IV2; v11 = IV3; v12 = ctr; v13 = 0; v14 = 64; v15 = 0;
+    RNDS(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
+  }
+  RNDS(2, 6, 3, 10, 7, 0, 4, 13, 1, 11, 12, 5, 9, 14, 15, 8)
+  RNDS(3, 4, 10, 12, 13, 2, 7, 14, 6, 5, 9, 0, 11, 15, 8, 1)
+  RNDS(10, 7, 12, 9, 14, 3, 13, 15, 4, 0, 11, 2, 5, 8, 1, 6)
+  RNDS(12, 13, 9, 11, 15, 10, 14, 8, 7, 2, 5, 3, 0, 1, 6, 4)
+  RNDS(9, 14, 11, 5, 8, 12, 15, 1, 13, 3, 0, 10, 2, 6, 4, 7)
+  RNDS(11, 15, 5, 0, 1, 9, 8, 6, 14, 10, 2, 12, 3, 4, 7, 13)
+  cv[0] = v0 ^ v8; cv[1] = v1 ^ v9; cv[2] = v2 ^ v10; cv[3] = v3 ^ v11;
+  cv[4] = v4 ^ v12; cv[5] = v5 ^ v13; cv[6] = v6 ^ v14; cv[7] = v7 ^ v15;
+}
+
 template <int V>
 __device__ __forceinline__ void comp(uint32_t (&cv)[8], const uint32_t (&m)[16], uint32_t ctr) {
+  if constexpr (V >= 100) {
+    comp_sched<V>(cv, m, ctr);
+    return;
+  }
   uint32_t v0 = cv[0], v1 = cv[1], v2 = cv[2], v3 = cv[3], v4 = cv[4], v5 = cv[5], v6 = cv[6], v7 = cv[7];
   uint32_t v8 = IV0, v9 = IV1, v10 = IV2, v11 = IV3, v12 = ctr, v13 = 0, v14 = 64, v15 = 0;
   RNDX(V, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
@@ -268,10 +393,13 @@ void run(int cus, int wps, int iters, uint32_t* out, uint32_t* ref) {
   const double ghz = med(clk), wave_cycles = med(cyc);
   // a wave runs iters * S * 64 compressions; wps waves share a SIMD
   const double cyc_per_64 = wave_cycles / ((double)iters * S) / wps;
+  // the same from the whole kernel's time: SIMDs x clock / (wave-compressions per second)
+  const double gcs = (double)blocks * 256 * iters * S / ms / 1e6;
+  const double issue = ghz * 4.0 * cus * 64.0 / gcs;
   printf("variant %d streams %d waves/SIMD %d: %.1f G comp/s, clock %.3f GHz, %.0f SIMD cycles per 64 compressions "
-         "(%.2f per wave-instruction at 680) %s\n", V, S, wps,
-         (double)blocks * 256 * iters * S / ms / 1e6, ghz, cyc_per_64, cyc_per_64 / 680.0,
-         ref ? (bad ? "MISMATCH" : "ok") : "(ref)");
+         "(%.2f per wave-instruction at 680), %.0f by rate and clock %s\n", V, S, wps, gcs, ghz, cyc_per_64,
+         cyc_per_64 / 680.0, issue, ref ? (bad ? "MISMATCH" : "ok") : "(ref)");
+  fflush(stdout);
 }
 
 int main(int argc, char** argv) {
@@ -281,6 +409,44 @@ int main(int argc, char** argv) {
   uint32_t *out, *ref;
   hipMalloc(&out, 4 << 20);
   hipMalloc(&ref, 4 << 20);
+  if (argc > 2 && !strcmp(argv[2], "gsched")) {
+    // the schedules with several G's per block, against variant 11 (the
+    // product's block), which runs five times per occupancy for its spread
+    for (int w : {6, 8}) {
+      run<0, 2>(cus, w, iters, ref, nullptr);
+      for (int i = 0; i < 5; ++i) run<11, 2>(cus, w, iters, out, ref);
+      run<7, 2>(cus, w, iters, out, ref);
+      run<18, 2>(cus, w, iters, out, ref);
+      run<8, 2>(cus, w, iters, out, ref);
+      run<100, 2>(cus, w, iters, out, ref);
+      run<101, 2>(cus, w, iters, out, ref);
+      run<102, 2>(cus, w, iters, out, ref);
+      run<103, 2>(cus, w, iters, out, ref);
+      run<104, 2>(cus, w, iters, out, ref);
+      run<110, 2>(cus, w, iters, out, ref);
+      run<111, 2>(cus, w, iters, out, ref);
+      run<112, 2>(cus, w, iters, out, ref);
+      run<113, 2>(cus, w, iters, out, ref);
+      run<114, 2>(cus, w, iters, out, ref);
+      run<120, 2>(cus, w, iters, out, ref);
+      run<121, 2>(cus, w, iters, out, ref);
+      run<122, 2>(cus, w, iters, out, ref);
+      run<123, 2>(cus, w, iters, out, ref);
+      run<124, 2>(cus, w, iters, out, ref);
+      run<150, 2>(cus, w, iters, out, ref);
+      run<151, 2>(cus, w, iters, out, ref);
+      run<152, 2>(cus, w, iters, out, ref);
+      run<153, 2>(cus, w, iters, out, ref);
+      run<154, 2>(cus, w, iters, out, ref);
+      run<160, 2>(cus, w, iters, out, ref);
+      run<161, 2>(cus, w, iters, out, ref);
+      run<162, 2>(cus, w, iters, out, ref);
+      run<163, 2>(cus, w, iters, out, ref);
+      run<164, 2>(cus, w, iters, out, ref);
+      run<11, 2>(cus, w, iters, out, ref);
+    }
+    return 0;
+  }
   for (int w : {4, 6, 8}) {
     run<0, 2>(cus, w, iters, ref, nullptr);
     run<0, 1>(cus, w, iters, out, nullptr);

@@ -11,6 +11,9 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
 
 #define R8(I0, I1, I2, I3, I4, I5, I6, I7) I0 "\n" I1 "\n" I2 "\n" I3 "\n" I4 "\n" I5 "\n" I6 "\n" I7 "\n"
 #define CLOB                                                                                                  \
@@ -141,6 +144,123 @@ __global__ void __launch_bounds__(256) k_probe(uint32_t* out, int iters) {
   if (threadIdx.x == 0 && iters < 0) out[blockIdx.x] = 1;
 }
 
+// ---- half-rate (H) next to full-rate (F) instructions ------------------------
+// Does a full-rate op cost a whole 4-cycle issue slot unless another
+// full-rate op is issued right next to it? H = v_alignbit_b32 x,x; F = one of
+// v_xor_b32 (VOP2, the G step's own), v_bitop3_b32 (two-input xor) or
+// v_add_u32_e64; NOP = "s_nop 0" after every H. Eight instructions per asm
+// statement (two groups of four), 16 statements per loop iteration. Prints
+// lane-ops/s, the in-kernel clock and the SIMD cycles per wave-instruction.
+#define PH(D, S, N) "v_alignbit_b32 " D ", " S ", " S ", 7\n" N
+#define F_XOR(D, A, B) "v_xor_b32 " D ", " A ", " B "\n"
+#define F_BITOP(D, A, B) "v_bitop3_b32 " D ", " A ", " B ", " A " bitop3:0x3c\n"
+#define F_ADD64(D, A, B) "v_add_u32_e64 " D ", " A ", " B "\n"
+// 0: H F H F, each F reads the H before it
+#define C0(F, N) PH("v8", "v16", N) F("v9", "v8", "v20") PH("v10", "v17", N) F("v11", "v10", "v21") \
+                 PH("v12", "v18", N) F("v13", "v12", "v22") PH("v14", "v19", N) F("v15", "v14", "v23")
+// 1: H F F H, the two F independent
+#define C1(F, N) PH("v8", "v16", N) F("v9", "v20", "v21") F("v10", "v24", "v25") PH("v11", "v17", N) \
+                 PH("v12", "v18", N) F("v13", "v28", "v29") F("v14", "v32", "v33") PH("v15", "v19", N)
+// 2: H F F H, the second F reads the first
+#define C2(F, N) PH("v8", "v16", N) F("v9", "v20", "v21") F("v10", "v9", "v25") PH("v11", "v17", N) \
+                 PH("v12", "v18", N) F("v13", "v28", "v29") F("v14", "v13", "v33") PH("v15", "v19", N)
+// 3: H H F F on four independent registers
+#define C3(F, N) PH("v8", "v16", N) PH("v9", "v17", N) F("v10", "v20", "v21") F("v11", "v24", "v25") \
+                 PH("v12", "v18", N) PH("v13", "v19", N) F("v14", "v28", "v29") F("v15", "v32", "v33")
+// 4: H F H F, all independent (a lone F between two H)
+#define C4(F, N) PH("v8", "v16", N) F("v9", "v20", "v21") PH("v10", "v17", N) F("v11", "v24", "v25") \
+                 PH("v12", "v18", N) F("v13", "v28", "v29") PH("v14", "v19", N) F("v15", "v32", "v33")
+// 5: F only; 6: H only (N after each)
+#define C5(F, N) F("v8", "v16", "v17") F("v9", "v20", "v21") F("v10", "v24", "v25") F("v11", "v28", "v29") \
+                 F("v12", "v32", "v33") F("v13", "v36", "v37") F("v14", "v40", "v41") F("v15", "v44", "v45")
+#define C6(F, N) PH("v8", "v16", N) PH("v9", "v17", N) PH("v10", "v18", N) PH("v11", "v19", N) \
+                 PH("v12", "v20", N) PH("v13", "v21", N) PH("v14", "v22", N) PH("v15", "v23", N)
+// 7: H F F F H H (the staggered G's stream), the F independent
+#define C7(F, N) PH("v8", "v16", N) F("v9", "v20", "v21") F("v10", "v24", "v25") F("v11", "v28", "v29") \
+                 PH("v12", "v18", N) PH("v13", "v19", N) F("v14", "v32", "v33") F("v15", "v36", "v37")
+#define PCASE(C)                                                          \
+  if (FK == 0 && !NOP) asm volatile(C(F_XOR, "") ::: CLOB);               \
+  if (FK == 0 && NOP) asm volatile(C(F_XOR, "s_nop 0\n") ::: CLOB);       \
+  if (FK == 1 && !NOP) asm volatile(C(F_BITOP, "") ::: CLOB);             \
+  if (FK == 1 && NOP) asm volatile(C(F_BITOP, "s_nop 0\n") ::: CLOB);     \
+  if (FK == 2 && !NOP) asm volatile(C(F_ADD64, "") ::: CLOB);             \
+  if (FK == 2 && NOP) asm volatile(C(F_ADD64, "s_nop 0\n") ::: CLOB);
+
+template <int CASE, int FK, int NOP>
+__global__ void __launch_bounds__(256) k_pair(uint32_t* out, int iters, uint64_t* stamps) {
+  const uint64_t t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+  for (int it = 0; it < iters; ++it) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (CASE == 0) { PCASE(C0) }
+      if (CASE == 1) { PCASE(C1) }
+      if (CASE == 2) { PCASE(C2) }
+      if (CASE == 3) { PCASE(C3) }
+      if (CASE == 4) { PCASE(C4) }
+      if (CASE == 5) { PCASE(C5) }
+      if (CASE == 6) { PCASE(C6) }
+      if (CASE == 7) { PCASE(C7) }
+    }
+  }
+  if (threadIdx.x == 0 && iters < 0) out[blockIdx.x] = 1;
+  const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+  if (stamps && (threadIdx.x & 63) == 0) {  // vector stores, one lane per wave
+    const uint32_t w = (blockIdx.x * 256 + threadIdx.x) / 64;
+    stamps[2 * w] = t1 - t0;
+    stamps[2 * w + 1] = r1 - r0;
+  }
+}
+
+static const char* kCaseNames[] = {"H F H F, F reads the H before", "H F F H, F independent",  "H F F H, 2nd F reads 1st",
+                                   "H H F F, independent",          "H F H F, independent",    "F only",
+                                   "H only",                        "H F F F H H, independent"};
+static const char* kFNames[] = {"v_xor_b32", "v_bitop3_b32", "v_add_u32_e64"};
+constexpr int kMaxWaves = 256 * 8 * 4;  // 256 CUs at most, 8 waves/SIMD
+
+template <int CASE, int FK, int NOP>
+void pair_report(int cus, int iters, uint32_t* out, uint64_t* stamps) {
+  if (cus > 256) cus = 256;  // the stamp buffer's size
+  printf("%-30s %-14s %s:", kCaseNames[CASE], kFNames[FK], NOP ? "nop " : "bare");
+  for (int w : {1, 2, 4, 6, 8}) {
+    const int blocks = cus * w;
+    hipEvent_t a, b;
+    hipEventCreate(&a);
+    hipEventCreate(&b);
+    hipLaunchKernelGGL((k_pair<CASE, FK, NOP>), dim3(blocks), dim3(256), 0, 0, out, 8, (uint64_t*)nullptr);
+    hipEventRecord(a);
+    hipLaunchKernelGGL((k_pair<CASE, FK, NOP>), dim3(blocks), dim3(256), 0, 0, out, iters, stamps);
+    hipEventRecord(b);
+    hipEventSynchronize(b);
+    float ms;
+    hipEventElapsedTime(&ms, a, b);
+    static uint64_t hs[2 * kMaxWaves];
+    static double clk[kMaxWaves];
+    const int waves = blocks * 4;
+    hipMemcpy(hs, stamps, 16 * waves, hipMemcpyDeviceToHost);
+    for (int i = 0; i < waves; ++i) clk[i] = hs[2 * i + 1] ? (double)hs[2 * i] / (double)hs[2 * i + 1] * 0.1 : 0;
+    std::sort(clk, clk + waves);
+    const double ghz = clk[waves / 2];
+    const double tops = (double)blocks * 256 * iters * 128 / ms / 1e9;  // T lane-ops/s
+    // SIMD cycles per wave-instruction: SIMDs x clock / (wave-instructions per second)
+    const double cyc = ghz * 1e9 * cus * 4 / (tops * 1e12 / 64);
+    printf("  %dw %5.1f T %.3f GHz %.2f cyc", w, tops, ghz, cyc);
+    hipEventDestroy(a);
+    hipEventDestroy(b);
+  }
+  printf("\n");
+  fflush(stdout);
+}
+
+template <int CASE>
+void pair_case(int cus, int iters, uint32_t* out, uint64_t* stamps) {
+  pair_report<CASE, 0, 0>(cus, iters, out, stamps);
+  pair_report<CASE, 0, 1>(cus, iters, out, stamps);
+  pair_report<CASE, 1, 0>(cus, iters, out, stamps);
+  pair_report<CASE, 1, 1>(cus, iters, out, stamps);
+  pair_report<CASE, 2, 0>(cus, iters, out, stamps);
+  pair_report<CASE, 2, 1>(cus, iters, out, stamps);
+}
+
 static const char* kNames[] = {"v_add_u32 (VOP2)",           "v_alignbit x,x (rotate)",   "v_alignbit diff banks",
                                "v_alignbit same bank",       "v_add3_u32 3 banks",        "v_bitop3_b32 3 banks",
                                "v_pk_add_u16 opsel (rot16)", "v_perm_b32",                "v_add3_u32 2 same bank",
@@ -177,6 +297,19 @@ int main(int argc, char** argv) {
   const int iters = argc > 1 ? atoi(argv[1]) : 4000;
   uint32_t* out;
   hipMalloc(&out, 1 << 20);
+  if (argc > 2 && !strcmp(argv[2], "pairs")) {  // the H / F pairing cases alone
+    uint64_t* stamps;
+    hipMalloc(&stamps, 16 * kMaxWaves);
+    pair_case<0>(cus, iters, out, stamps);
+    pair_case<1>(cus, iters, out, stamps);
+    pair_case<2>(cus, iters, out, stamps);
+    pair_case<3>(cus, iters, out, stamps);
+    pair_case<4>(cus, iters, out, stamps);
+    pair_case<5>(cus, iters, out, stamps);
+    pair_case<6>(cus, iters, out, stamps);
+    pair_case<7>(cus, iters, out, stamps);
+    return 0;
+  }
   const int blocks = cus * 8;  // 8 waves per SIMD
   report<0>(blocks, iters, out);
   report<1>(blocks, iters, out);
