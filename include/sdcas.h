@@ -910,6 +910,123 @@ int sdcas_dev_chunk_index_add(sdcas_ctx *ctx, const uint64_t *d_old_keys, const 
                               uint32_t bits_new, int64_t *d_out_pos, uint8_t *d_out_flags, uint64_t *d_counts,
                               void *stream);
 
+/* ---- holders index: a chunk index that can forget files ----------------------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * The chunk index above keeps, per pair, the value that came first and so can
+ * only grow. A HOLDERS INDEX keeps every holder: the same four caller-owned
+ * arrays (keys[n], digests32[n], values[n], dir[2^bits + 1]; the directory
+ * rule, the limits n <= 2^30 and bits <= 28 and the alignments are the chunk
+ * index's), with the entries STRICTLY ASCENDING in the TRIPLE (key as u64,
+ * digest as 32 bytes in memcmp order, value as unsigned 64-bit). A pair may
+ * repeat, once per distinct value; the upper layers store file ids, so the
+ * first entry of a pair's run is its lowest holder and the run's length is the
+ * number of files that hold the pair. Every valid chunk index is a valid
+ * holders index (strict in the pair implies strict in the triple); values
+ * NULL stands for all 0, which allows each pair once.
+ * A run is not bounded by anything (every sparse file holds the all-zero
+ * chunk): no call's cost per thread follows a run's length, and forged keys
+ * (one key, many digests) are taken as before. Directory values are clamped
+ * to n; results are exact and do not depend on scheduling.
+ * sdcas_chunk_index_dir_bits serves both kinds. */
+/* GPU-free, host arrays: as sdcas_chunk_index_check, in the triple order.
+ * *out_first_bad (may be NULL) = the first entry i >= 1 whose triple does not
+ * order after entry i - 1's or, when the entries are in order, the first
+ * directory slot that does not hold its count. */
+int sdcas_chunk_holders_check(const uint64_t *keys, const uint8_t *digests32, const uint64_t *values,
+                              const uint32_t *dir, uint64_t n, uint32_t bits, uint64_t *out_first_bad);
+
+/* Read-only match; the inputs and the counts are sdcas_chunk_index_match's:
+ *   out_pos[c]      the FIRST entry with c's pair; -1 when there is none or !valid[c]
+ *   out_value[c]    that entry's value: the lowest holder; or 0
+ *   out_holders[c]  the number of entries with the pair, or 0
+ * Both ends of the run are found by halving inside the key's bucket: the cost
+ * follows m, not n and not the run. Any output may be NULL. */
+int sdcas_chunk_holders_match(sdcas_ctx *ctx, const uint64_t *idx_keys, const uint8_t *idx_digests32,
+                              const uint64_t *idx_values, const uint32_t *idx_dir, uint64_t n, uint32_t bits,
+                              const uint64_t *keys, const uint8_t *digests32, const uint8_t *valid, size_t m,
+                              int64_t *out_pos, uint64_t *out_value, uint32_t *out_holders,
+                              sdcas_index_match_counts *out_counts);
+/* Device arrays: sdcas_dev_chunk_index_match's rules (d_out_holders 4-byte
+ * aligned). Never waits for the device and uses no workspace. */
+int sdcas_dev_chunk_holders_match(sdcas_ctx *ctx, const uint64_t *d_idx_keys, const uint8_t *d_idx_digests32,
+                                  const uint64_t *d_idx_values, const uint32_t *d_idx_dir, uint64_t n, uint32_t bits,
+                                  const uint64_t *d_keys, const uint8_t *d_digests32, const uint8_t *d_valid,
+                                  size_t m, int64_t *d_out_pos, uint64_t *d_out_value, uint32_t *d_out_holders,
+                                  uint64_t *d_counts, void *stream);
+
+/* Add: the NEW index is the sorted distinct union of the old triples and the
+ * batch's valid triples (keys[c], digests32[c], values[c]; values NULL: 0),
+ * in arrays of n_old + m entries with the directory at bits_new, as
+ * sdcas_chunk_index_add. Read per TRIPLE:
+ *   out_pos[c]    the triple's entry in the new index; -1 when !valid[c]
+ *   out_flags[c]  SDCAS_INDEX_HIT: the old index held the triple (this file
+ *                 already held this chunk); SDCAS_INDEX_ADDED: the triple is
+ *                 new and c is the lowest batch position with it;
+ *                 SDCAS_INDEX_SKIPPED: !valid[c]; 0: a later batch position
+ *                 with the same new triple
+ * queries == hits + added + batch_duplicates. The overlap and capacity rules
+ * are sdcas_chunk_index_add's. */
+int sdcas_chunk_holders_add(sdcas_ctx *ctx, const uint64_t *old_keys, const uint8_t *old_digests32,
+                            const uint64_t *old_values, const uint32_t *old_dir, uint64_t n_old, uint32_t bits_old,
+                            const uint64_t *keys, const uint8_t *digests32, const uint64_t *values,
+                            const uint8_t *valid, size_t m, uint64_t *new_keys, uint8_t *new_digests32,
+                            uint64_t *new_values, uint32_t *new_dir, uint32_t bits_new, int64_t *out_pos,
+                            uint8_t *out_flags, sdcas_index_add_counts *out_counts);
+/* Device arrays, as sdcas_dev_chunk_index_add. The context's workspace for a
+ * batch of m is 16 bytes per batch entry (two orders of the batch positions,
+ * the lower bounds and their compaction) and 1/64 word of counts; nothing
+ * grows with n_old. The batch is ordered by ceil_log2(m) merge passes. The
+ * first call that needs the workspace allocates it and waits for the stream;
+ * after that the call never waits. */
+int sdcas_dev_chunk_holders_add(sdcas_ctx *ctx, const uint64_t *d_old_keys, const uint8_t *d_old_digests32,
+                                const uint64_t *d_old_values, const uint32_t *d_old_dir, uint64_t n_old,
+                                uint32_t bits_old, const uint64_t *d_keys, const uint8_t *d_digests32,
+                                const uint64_t *d_values, const uint8_t *d_valid, size_t m, uint64_t *d_new_keys,
+                                uint8_t *d_new_digests32, uint64_t *d_new_values, uint32_t *d_new_dir,
+                                uint32_t bits_new, int64_t *d_out_pos, uint8_t *d_out_flags, uint64_t *d_counts,
+                                void *stream);
+
+/* Remove: the NEW index is the old entries whose value is not in removed[r]
+ * (u64, STRICTLY ASCENDING, r <= 2^30), in their old order: byte for byte the
+ * index built from the holders that remain. The new keys / digests32 / values
+ * arrays hold n_old entries, of which the first entries_new are written and
+ * the rest left as they were; new_dir holds 2^bits_new + 1 and is rebuilt, so
+ * the widths may differ. The old index streams through once (48 bytes in per
+ * entry, at most 48 out), `removed` is the only thing searched, by halving.
+ * Old and new arrays must not overlap, nor `removed` and the new arrays
+ * (checked from pointers and sizes: SDCAS_E_INVALID). r == 0 copies the old
+ * entries and re-buckets; n_old == 0 is SDCAS_OK. */
+typedef struct sdcas_holders_remove_counts {
+  uint64_t entries_old;
+  uint64_t removed;     /* entries taken out */
+  uint64_t entries_new; /* entries_old - removed */
+  uint64_t values;      /* r */
+} sdcas_holders_remove_counts;
+/* Host arrays: also SDCAS_E_INVALID, before the device is touched, for a
+ * `removed` that is not strictly ascending. One upload, the device call, the
+ * counts down, then exactly entries_new entries and the new directory. */
+int sdcas_chunk_holders_remove(sdcas_ctx *ctx, const uint64_t *old_keys, const uint8_t *old_digests32,
+                               const uint64_t *old_values, const uint32_t *old_dir, uint64_t n_old,
+                               uint32_t bits_old, const uint64_t *removed, size_t r, uint64_t *new_keys,
+                               uint8_t *new_digests32, uint64_t *new_values, uint32_t *new_dir, uint32_t bits_new,
+                               sdcas_holders_remove_counts *out_counts);
+/* Device arrays, asynchronous on `stream`, alignments as for the match
+ * (d_removed 8-byte). d_counts: four u64 in sdcas_holders_remove_counts'
+ * order, overwritten: entries_new stays on the device. `removed` cannot be
+ * checked without reading it: one that is not ascending gives a wrong
+ * selection of entries, never a store outside the arrays (every place is a
+ * rank among at most n_old kept entries, checked against n_old). The
+ * workspace is the keep masks and the kept counts, 36 bytes and a little per
+ * 256 entries, allocated by the first call that needs it (which waits for the
+ * stream); after that the call never waits. */
+int sdcas_dev_chunk_holders_remove(sdcas_ctx *ctx, const uint64_t *d_old_keys, const uint8_t *d_old_digests32,
+                                   const uint64_t *d_old_values, const uint32_t *d_old_dir, uint64_t n_old,
+                                   uint32_t bits_old, const uint64_t *d_removed, size_t r, uint64_t *d_new_keys,
+                                   uint8_t *d_new_digests32, uint64_t *d_new_values, uint32_t *d_new_dir,
+                                   uint32_t bits_new, uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

@@ -69,6 +69,9 @@ ABI_SYMBOLS = [
     "sdcas_chunk_seg_bytes", "sdcas_chunk_windows", "sdcas_dev_chunk_windows",  # added after ABI 7
     "sdcas_chunk_index_dir_bits", "sdcas_chunk_index_check", "sdcas_chunk_index_match",
     "sdcas_dev_chunk_index_match", "sdcas_chunk_index_add", "sdcas_dev_chunk_index_add",  # added after ABI 7
+    "sdcas_chunk_holders_check", "sdcas_chunk_holders_match", "sdcas_dev_chunk_holders_match",
+    "sdcas_chunk_holders_add", "sdcas_dev_chunk_holders_add", "sdcas_chunk_holders_remove",
+    "sdcas_dev_chunk_holders_remove",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -204,6 +207,15 @@ class IndexAddCounts(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class HoldersRemoveCounts(ctypes.Structure):
+    """sdcas_holders_remove_counts"""
+    _fields_ = [("entries_old", ctypes.c_uint64), ("removed", ctypes.c_uint64), ("entries_new", ctypes.c_uint64),
+                ("values", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _lib_path = LIB_PATH
 
@@ -299,6 +311,17 @@ def load():
                                         _vp, _u32, _vp, _vp, ctypes.POINTER(IndexAddCounts)]
     L.sdcas_dev_chunk_index_add.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _sz, _vp, _vp,
                                             _vp, _vp, _u32, _vp, _vp, _vp, _vp]
+    L.sdcas_chunk_holders_check.argtypes = [_vp, _vp, _vp, _vp, _u64, _u32, _vp]
+    L.sdcas_chunk_holders_match.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _sz, _vp, _vp, _vp,
+                                            ctypes.POINTER(IndexMatchCounts)]
+    L.sdcas_dev_chunk_holders_match.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _sz, _vp, _vp,
+                                                _vp, _vp, _vp]
+    L.sdcas_chunk_holders_add.argtypes = L.sdcas_chunk_index_add.argtypes
+    L.sdcas_dev_chunk_holders_add.argtypes = L.sdcas_dev_chunk_index_add.argtypes
+    L.sdcas_chunk_holders_remove.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _sz, _vp, _vp, _vp, _vp, _u32,
+                                             ctypes.POINTER(HoldersRemoveCounts)]
+    L.sdcas_dev_chunk_holders_remove.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _sz, _vp, _vp, _vp, _vp,
+                                                 _u32, _vp, _vp]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

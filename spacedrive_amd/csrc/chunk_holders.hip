@@ -1,0 +1,634 @@
+// chunk_holders.hip — the holders index: the chunk index (chunk_index.hip) with
+// every holder of a pair kept, so that a file's entries can be removed again.
+//
+// The entries are sorted by the triple (key, digest as 32 bytes in memcmp
+// order, value), with the chunk index's directory over the keys' top bits. A
+// pair's entries are a run, lowest value first; a run is not bounded by
+// anything (every sparse file holds the all-zero chunk), so no thread here
+// ever walks one: run ends are found by halving, orders by merging.
+//   k_ch_match     one query per thread: its bucket, the lower bound of the
+//                  pair, then the upper bound from there to the bucket's end
+// The add, for a batch of m against n_old entries, every grid sized from m or
+// n_old and the number of added triples left on the device:
+//   k_ch_iota, k_ch_merge  the batch positions ordered by (valid first, triple,
+//                  position): a merge sort by halving, one launch per doubling,
+//                  so that equal triples are neighbours with the lowest
+//                  position first
+//   k_ch_head      per place in that order: the triple's lower bound in the
+//                  old index, whether it is there, and whether the place is
+//                  the first of a triple that is not; the new firsts counted
+//                  per workgroup
+//   k_ch_scan      the counts scanned, three levels of 256 (chunk_holders.h)
+//   k_ch_place     a new first goes to its rank among the new firsts plus its
+//                  lower bound; that rank also places every later copy and
+//                  every hit, so pos and flags are written here, and the
+//                  counts
+//   k_ch_place_old an old entry goes to its index plus the number of new
+//                  lower bounds that are <= it (as k_ci_place_old)
+//   k_ch_dir       one lower bound in the new keys per directory slot
+// The remove, one thread per old entry:
+//   k_ch_rm_mark   membership of the entry's value in `removed` by halving;
+//                  the waves' keep masks and the kept per workgroup
+//   k_ch_scan      as above
+//   k_ch_rm_scatter a kept entry goes to the kept before its workgroup plus
+//                  its rank in it: the order is preserved
+//   k_ch_dir       the directory of what is left
+// Every directory value is clamped to n, every computed place is checked
+// against the arrays' bound before a store.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include "chunk_holders.h"
+
+namespace sdcas {
+
+namespace {
+
+constexpr uint32_t kChTB = kHoldersTB;
+constexpr uint32_t kChHitBit = 0x80000000u, kChNewBit = 0x40000000u, kChLbMask = 0x3FFFFFFFu;
+constexpr uint8_t kChHit = 1, kChAdded = 2, kChSkipped = 4;  // SDCAS_INDEX_*
+
+struct ChDigest {
+  uint4 a, b;
+};
+__device__ __forceinline__ ChDigest ch_digest(const uint8_t* __restrict__ digests, uint32_t i) {
+  const uint4* p = reinterpret_cast<const uint4*>(digests) + 2 * (size_t)i;
+  return ChDigest{p[0], p[1]};
+}
+__device__ __forceinline__ void ch_store(uint8_t* __restrict__ digests, uint32_t i, const ChDigest& d) {
+  uint4* p = reinterpret_cast<uint4*>(digests) + 2 * (size_t)i;
+  p[0] = d.a;
+  p[1] = d.b;
+}
+// memcmp of the 32 bytes: < 0, 0, > 0 (little-endian word loads, byte-swapped to compare)
+__device__ __forceinline__ int ch_cmp(const ChDigest& x, const ChDigest& y) {
+  const uint32_t xs[8] = {x.a.x, x.a.y, x.a.z, x.a.w, x.b.x, x.b.y, x.b.z, x.b.w};
+  const uint32_t ys[8] = {y.a.x, y.a.y, y.a.z, y.a.w, y.b.x, y.b.y, y.b.z, y.b.w};
+#pragma unroll
+  for (uint32_t w = 0; w < 8; ++w) {
+    if (xs[w] != ys[w]) return __builtin_bswap32(xs[w]) < __builtin_bswap32(ys[w]) ? -1 : 1;
+  }
+  return 0;
+}
+
+__device__ __forceinline__ uint32_t ch_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
+
+struct ChTriple {
+  uint64_t key;
+  ChDigest dig;
+  uint64_t val;
+};
+__device__ __forceinline__ ChTriple ch_triple(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ digests,
+                                              const uint64_t* __restrict__ values, uint32_t i) {
+  return ChTriple{keys[i], ch_digest(digests, i), values ? values[i] : 0ull};
+}
+// entry i of (keys, digests, values) against t: < 0, 0, > 0. The digest is read
+// only where the keys are equal, the value only where the digests are.
+__device__ __forceinline__ int ch_cmp3(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ digests,
+                                       const uint64_t* __restrict__ values, uint32_t i, const ChTriple& t) {
+  const uint64_t k = keys[i];
+  if (k != t.key) return k < t.key ? -1 : 1;
+  const int c = ch_cmp(ch_digest(digests, i), t.dig);
+  if (c) return c;
+  const uint64_t v = values ? values[i] : 0ull;
+  return v == t.val ? 0 : (v < t.val ? -1 : 1);
+}
+
+// the bucket of `key`: [lo, hi), both clamped to n
+__device__ __forceinline__ void ch_bucket(const IndexView& ix, uint64_t key, uint32_t& lo, uint32_t& hi) {
+  const uint32_t b = ix.bits ? (uint32_t)(key >> (64 - ix.bits)) : 0u;
+  lo = ch_min(ix.dir[b], ix.n);
+  hi = ch_min(ix.dir[b + 1], ix.n);
+  if (hi < lo) hi = lo;
+}
+
+// the first entry of [lo, hi) whose pair is not below (key, dig) — or, with
+// `after`, the first whose pair is above it
+__device__ __forceinline__ uint32_t ch_pair_bound(const IndexView& ix, uint32_t lo, uint32_t hi, uint64_t key,
+                                                  const ChDigest& dig, bool after) {
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    const uint64_t k = ix.keys[mid];
+    bool below;
+    if (k != key) {
+      below = k < key;
+    } else {
+      const int c = ch_cmp(ch_digest(ix.digests, mid), dig);
+      below = after ? c <= 0 : c < 0;
+    }
+    if (below) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// the first entry of t's bucket that is not below t; found: it is equal
+__device__ __forceinline__ uint32_t ch_lower_bound3(const IndexView& ix, const ChTriple& t, bool& found) {
+  found = false;
+  if (!ix.n) return 0;
+  uint32_t lo, hi;
+  ch_bucket(ix, t.key, lo, hi);
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    const int c = ch_cmp3(ix.keys, ix.digests, ix.values, mid, t);
+    if (c == 0) {
+      found = true;
+      return mid;
+    }
+    if (c < 0) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// the number of a[0 .. len) that are <= v, looked for in [lo, hi] (a ascending)
+__device__ __forceinline__ uint32_t ch_upper(const uint32_t* __restrict__ a, uint32_t lo, uint32_t hi, uint32_t v) {
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] <= v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// Called by every thread of a workgroup of 256: the number of lower threads
+// whose flag is set; *total <- the workgroup's. s: 4 words of LDS.
+__device__ __forceinline__ uint32_t ch_rank(bool flag, uint32_t* s, uint32_t* total) {
+  const uint64_t bal = __ballot(flag);
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) s[wave] = (uint32_t)__popcll(bal);
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kChTB / 64; ++w) {
+    const uint32_t v = s[w];
+    before += w < wave ? v : 0u;
+    all += v;
+  }
+  *total = all;
+  return before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+}
+
+// the counts of the workgroups before b, from the three scanned levels
+__device__ __forceinline__ uint32_t ch_base(const uint32_t* __restrict__ l1, const uint32_t* __restrict__ l2,
+                                            const uint32_t* __restrict__ l3, uint32_t b) {
+  return l1[b] + l2[b >> 8] + l3[b >> 16];
+}
+
+// One level of the scan: every workgroup turns its 256 counts of a[0 .. n) into
+// their exclusive scan and leaves their sum in up[blockIdx.x].
+__global__ void __launch_bounds__(kChTB) k_ch_scan(uint32_t* __restrict__ a, uint32_t n, uint32_t* __restrict__ up) {
+  __shared__ uint32_t s_w[kChTB / 64];
+  const uint32_t i = blockIdx.x * kChTB + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t v = i < n ? a[i] : 0u;
+  uint32_t inc = v;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t t = __shfl_up(inc, d);
+    if (lane >= d) inc += t;
+  }
+  if (lane == 63) s_w[wave] = inc;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kChTB / 64; ++w) {
+    const uint32_t t = s_w[w];
+    before += w < wave ? t : 0u;
+    all += t;
+  }
+  if (i < n) a[i] = before + inc - v;
+  if (threadIdx.x == 0) up[blockIdx.x] = all;
+}
+
+__global__ void __launch_bounds__(kChTB) k_ch_match(IndexView ix, const uint64_t* __restrict__ keys,
+                                                    const uint8_t* __restrict__ digests,
+                                                    const uint8_t* __restrict__ valid, uint32_t m,
+                                                    int64_t* __restrict__ pos, uint64_t* __restrict__ value,
+                                                    uint32_t* __restrict__ holders,
+                                                    unsigned long long* __restrict__ counts) {
+  __shared__ uint32_t s_cnt[kIndexMatchCounts];
+  if (threadIdx.x < kIndexMatchCounts) s_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t c = blockIdx.x * kChTB + threadIdx.x;
+  bool add[kIndexMatchCounts] = {false, false, false, false};  // queries, hits, misses, skipped
+  if (c < m) {
+    const bool take = !valid || valid[c];
+    uint32_t first = 0, end = 0;
+    if (take && ix.n) {
+      const uint64_t key = keys[c];
+      const ChDigest dig = ch_digest(digests, c);
+      uint32_t lo, hi;
+      ch_bucket(ix, key, lo, hi);
+      first = ch_pair_bound(ix, lo, hi, key, dig, false);
+      // the run's end lies in the same bucket: its entries share the key
+      end = ch_pair_bound(ix, first, hi, key, dig, true);
+    }
+    const bool found = end > first;
+    if (pos) pos[c] = found ? (int64_t)first : -1;
+    if (value) value[c] = found && ix.values ? ix.values[first] : 0ull;
+    if (holders) holders[c] = end - first;
+    add[0] = take, add[1] = found, add[2] = take && !found, add[3] = !take;
+  }
+  if (!counts) return;  // the same for every thread of the grid
+#pragma unroll
+  for (uint32_t w = 0; w < kIndexMatchCounts; ++w) {
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(add[w]));
+    if (cnt && (threadIdx.x & 63) == 0) atomicAdd(&s_cnt[w], cnt);
+  }
+  __syncthreads();
+  if (threadIdx.x < kIndexMatchCounts && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(kChTB) k_ch_iota(uint32_t* __restrict__ ord, uint32_t m) {
+  const uint32_t p = blockIdx.x * kChTB + threadIdx.x;
+  if (p < m) ord[p] = p;
+}
+
+// One pass of the merge sort over all m batch positions by (valid first,
+// triple, position): a total order, so no two compare equal. `in` holds the
+// positions in runs of w places, each run in order; every pair of neighbouring
+// runs is merged into `out`. A position goes to its rank in its own run plus
+// the number of the sibling run's positions before it, found by halving: at
+// most 30 steps per thread and pass, whatever the data.
+__global__ void __launch_bounds__(kChTB) k_ch_merge(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                    const uint64_t* __restrict__ keys,
+                                                    const uint8_t* __restrict__ digests,
+                                                    const uint64_t* __restrict__ values,
+                                                    const uint8_t* __restrict__ valid, uint32_t w, uint32_t m) {
+  const uint32_t p = blockIdx.x * kChTB + threadIdx.x;
+  if (p >= m) return;
+  const uint32_t c = in[p];
+  if (c >= m) return;  // never: `in` holds batch positions
+  const uint32_t first = p / (2 * w) * (2 * w);  // w <= 2^29: 2 w fits
+  const uint32_t mid = ch_min(first + w, m), end = ch_min(first + 2 * w, m);
+  const bool left = p < mid;
+  uint32_t lo = left ? mid : first, hi = left ? end : mid;
+  const uint32_t sib = lo;
+  const bool vc = !valid || valid[c];
+  const ChTriple t = ch_triple(keys, digests, values, c);
+  while (lo < hi) {  // the sibling run's positions before c
+    const uint32_t q = lo + ((hi - lo) >> 1);
+    const uint32_t e = in[q];
+    bool before = false;
+    if (e < m) {  // always
+      const bool ve = !valid || valid[e];
+      if (ve != vc) {
+        before = ve;
+      } else if (!ve) {
+        before = e < c;
+      } else {
+        const int r = ch_cmp3(keys, digests, values, e, t);
+        before = r ? r < 0 : e < c;
+      }
+    }
+    if (before) lo = q + 1;
+    else hi = q;
+  }
+  const uint32_t at = first + (p - (left ? first : mid)) + (lo - sib);
+  if (at < m) out[at] = c;  // always: a rank among the pair's end - first places
+}
+
+// lbf[p] for every place p of the order, the new firsts per workgroup into l1
+__global__ void __launch_bounds__(kChTB) k_ch_head(IndexView old, const uint32_t* __restrict__ ord,
+                                                   const uint64_t* __restrict__ keys,
+                                                   const uint8_t* __restrict__ digests,
+                                                   const uint64_t* __restrict__ values,
+                                                   const uint8_t* __restrict__ valid, uint32_t m,
+                                                   uint32_t* __restrict__ lbf, uint32_t* __restrict__ l1) {
+  __shared__ uint32_t s_w[kChTB / 64];
+  const uint32_t p = blockIdx.x * kChTB + threadIdx.x;
+  bool fresh = false;
+  if (p < m) {
+    const uint32_t c = ord[p];
+    uint32_t w = 0;
+    if (c < m && (!valid || valid[c])) {
+      const ChTriple t = ch_triple(keys, digests, values, c);
+      bool found;
+      const uint32_t lb = ch_lower_bound3(old, t, found);
+      bool head = p == 0;
+      if (!head) {  // the place before holds a valid position: those come first
+        const uint32_t e = ord[p - 1];
+        head = e >= m || ch_cmp3(keys, digests, values, e, t) != 0;
+      }
+      fresh = head && !found;
+      w = (lb & kChLbMask) | (found ? kChHitBit : 0u) | (fresh ? kChNewBit : 0u);
+    }
+    lbf[p] = w;
+  }
+  uint32_t total;
+  (void)ch_rank(fresh, s_w, &total);
+  if (threadIdx.x == 0) l1[blockIdx.x] = total;
+}
+
+// The new firsts into the new index, their lower bounds compacted into lbs,
+// pos and flags of every batch position, the four batch counts.
+__global__ void __launch_bounds__(kChTB) k_ch_place(const uint32_t* __restrict__ ord, const uint32_t* __restrict__ lbf,
+                                                    const uint32_t* __restrict__ l1, const uint32_t* __restrict__ l2,
+                                                    const uint32_t* __restrict__ l3,
+                                                    const uint64_t* __restrict__ keys,
+                                                    const uint8_t* __restrict__ digests,
+                                                    const uint64_t* __restrict__ values,
+                                                    const uint8_t* __restrict__ valid, uint32_t m, IndexOut out,
+                                                    uint32_t cap, uint32_t* __restrict__ lbs,
+                                                    int64_t* __restrict__ pos, uint8_t* __restrict__ flags,
+                                                    unsigned long long* __restrict__ counts) {
+  __shared__ uint32_t s_w[kChTB / 64];
+  __shared__ uint32_t s_cnt[4];
+  if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+  const uint32_t p = blockIdx.x * kChTB + threadIdx.x;
+  const uint32_t w = p < m ? lbf[p] : 0u;
+  const bool fresh = (w & kChNewBit) != 0;
+  uint32_t total;
+  // the new firsts at places <= p
+  const uint32_t upto = ch_base(l1, l2, l3, blockIdx.x) + ch_rank(fresh, s_w, &total) + (fresh ? 1u : 0u);
+  bool add[4] = {false, false, false, false};  // queries, hits, added, batch_duplicates
+  if (p < m) {
+    const uint32_t c = ord[p];
+    if (c < m) {  // always
+      int64_t at = -1;
+      uint8_t fl = kChSkipped;
+      if (!valid || valid[c]) {
+        const uint32_t lb = w & kChLbMask;
+        add[0] = true;
+        if (w & kChHitBit) {  // the new firsts before p stand before the old entry, no other does
+          at = (int64_t)lb + upto;
+          fl = kChHit, add[1] = true;
+        } else if (upto) {  // always: the triple's first is a new first at or before p
+          const uint32_t rank = upto - 1;
+          at = (int64_t)lb + rank;
+          fl = fresh ? kChAdded : 0, add[fresh ? 2 : 3] = true;
+          if (fresh) {
+            if (rank < m) lbs[rank] = lb;
+            if (at < (int64_t)cap) {  // always with an index that is one: lb <= n_old, rank < m
+              out.keys[at] = keys[c];
+              ch_store(out.digests, (uint32_t)at, ch_digest(digests, c));
+              out.values[at] = values ? values[c] : 0ull;
+            }
+          }
+        }
+      }
+      if (pos) pos[c] = at;
+      if (flags) flags[c] = fl;
+    }
+  }
+#pragma unroll
+  for (uint32_t q = 0; q < 4; ++q) {
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(add[q]));
+    if (cnt && (threadIdx.x & 63) == 0) atomicAdd(&s_cnt[q], cnt);
+  }
+  __syncthreads();
+  if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(kChTB) k_ch_place_old(IndexView old, const uint32_t* __restrict__ lbs,
+                                                        const uint32_t* __restrict__ na_p, uint32_t m, IndexOut out,
+                                                        uint32_t cap) {
+  __shared__ uint32_t s_span[2];
+  const uint32_t na = ch_min(*na_p, m);
+  const uint32_t first = blockIdx.x * kChTB;
+  if (threadIdx.x < 2) {
+    const uint32_t v = threadIdx.x == 0 ? first : ch_min(first + kChTB - 1, old.n - 1);
+    s_span[threadIdx.x] = ch_upper(lbs, 0, na, v);
+  }
+  __syncthreads();
+  const uint32_t i = first + threadIdx.x;
+  if (i >= old.n) return;
+  const uint32_t at = i + ch_upper(lbs, s_span[0], s_span[1], i);
+  if (at >= cap) return;  // never: at most na <= m added triples stand before an old entry
+  out.keys[at] = old.keys[i];
+  ch_store(out.digests, at, ch_digest(old.digests, i));
+  out.values[at] = old.values ? old.values[i] : 0ull;
+}
+
+// entries_old, entries_new
+__global__ void k_ch_add_totals(const uint32_t* __restrict__ na_p, uint32_t m, uint32_t n_old,
+                                unsigned long long* __restrict__ counts) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    counts[4] = n_old;
+    counts[5] = (unsigned long long)n_old + ch_min(*na_p, m);
+  }
+}
+
+// dir[j] <- the number of the n = base + min(*extra_p, extra_max) entries
+// whose key's top `bits` bits are below j
+__global__ void __launch_bounds__(kChTB) k_ch_dir(const uint64_t* __restrict__ nkeys, uint32_t base,
+                                                  const uint32_t* __restrict__ extra_p, uint32_t extra_max,
+                                                  uint32_t bits, uint32_t* __restrict__ dir) {
+  const uint64_t j = (uint64_t)blockIdx.x * kChTB + threadIdx.x;
+  const uint64_t slots = 1ull << bits;
+  if (j > slots) return;
+  const uint32_t n = base + ch_min(*extra_p, extra_max);
+  if (j == slots) {
+    dir[j] = n;
+    return;
+  }
+  if (j == 0) {
+    dir[0] = 0;
+    return;
+  }
+  const uint64_t thr = j << (64 - bits);  // bits >= 1 here: 0 < j < 2^bits
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (nkeys[mid] < thr) lo = mid + 1;
+    else hi = mid;
+  }
+  dir[j] = lo;
+}
+
+// masks[4 b + wave]: the lanes whose entry stays; l1[b]: how many of workgroup b's do
+__global__ void __launch_bounds__(kChTB) k_ch_rm_mark(const uint64_t* __restrict__ values, uint32_t n,
+                                                      const uint64_t* __restrict__ removed, uint32_t r,
+                                                      unsigned long long* __restrict__ masks,
+                                                      uint32_t* __restrict__ l1) {
+  __shared__ uint32_t s_w[kChTB / 64];
+  const uint32_t i = blockIdx.x * kChTB + threadIdx.x;
+  bool keep = false;
+  if (i < n) {
+    const uint64_t v = values ? values[i] : 0ull;
+    uint32_t lo = 0, hi = r;
+    while (lo < hi) {  // the first of removed that is not below v
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      if (removed[mid] < v) lo = mid + 1;
+      else hi = mid;
+    }
+    keep = !(lo < r && removed[lo] == v);
+  }
+  const uint64_t bal = __ballot(keep);
+  if ((threadIdx.x & 63) == 0) masks[(size_t)blockIdx.x * (kChTB / 64) + (threadIdx.x >> 6)] = bal;
+  uint32_t total;
+  (void)ch_rank(keep, s_w, &total);
+  if (threadIdx.x == 0) l1[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(kChTB) k_ch_rm_scatter(IndexView old, const unsigned long long* __restrict__ masks,
+                                                         const uint32_t* __restrict__ l1,
+                                                         const uint32_t* __restrict__ l2,
+                                                         const uint32_t* __restrict__ l3, IndexOut out, uint32_t cap) {
+  const uint32_t i = blockIdx.x * kChTB + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long* mk = masks + (size_t)blockIdx.x * (kChTB / 64);
+  uint32_t before = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kChTB / 64; ++w) before += w < wave ? (uint32_t)__popcll(mk[w]) : 0u;
+  const uint64_t bal = mk[wave];
+  if (i >= old.n || !((bal >> lane) & 1ull)) return;
+  const uint32_t at = ch_base(l1, l2, l3, blockIdx.x) + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+  if (at >= cap) return;  // never: a rank among at most n_old kept entries
+  out.keys[at] = old.keys[i];
+  ch_store(out.digests, at, ch_digest(old.digests, i));
+  out.values[at] = old.values ? old.values[i] : 0ull;
+}
+
+// entries_old, removed, entries_new, values
+__global__ void k_ch_rm_totals(const uint32_t* __restrict__ kept_p, uint32_t n_old, uint32_t r,
+                               unsigned long long* __restrict__ counts) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const uint32_t kept = ch_min(*kept_p, n_old);
+    counts[0] = n_old;
+    counts[1] = n_old - kept;
+    counts[2] = kept;
+    counts[3] = r;
+  }
+}
+
+inline uint32_t ch_blocks(uint64_t items) { return (uint32_t)((items + kChTB - 1) / kChTB); }
+
+template <typename T>
+inline T* at(uint8_t* ws, uint64_t off) {
+  return reinterpret_cast<T*>(ws + off);
+}
+
+// the per-workgroup counts in l1 scanned; the sum of all in tot[0]
+inline void ch_scan(uint8_t* ws, const HoldersScanLayout& s, hipStream_t st) {
+  uint32_t* l1 = at<uint32_t>(ws, s.l1);
+  uint32_t* l2 = at<uint32_t>(ws, s.l2);
+  uint32_t* l3 = at<uint32_t>(ws, s.l3);
+  uint32_t* tot = at<uint32_t>(ws, s.tot);
+  hipLaunchKernelGGL(k_ch_scan, dim3(s.n2), dim3(kChTB), 0, st, l1, s.n1, l2);
+  hipLaunchKernelGGL(k_ch_scan, dim3(s.n3), dim3(kChTB), 0, st, l2, s.n2, l3);
+  hipLaunchKernelGGL(k_ch_scan, dim3(1), dim3(kChTB), 0, st, l3, s.n3, tot);  // n3 <= 64
+}
+
+}  // namespace
+
+int holders_check(const uint64_t* keys, const uint8_t* digests, const uint64_t* values, const uint32_t* dir, uint64_t n,
+                  uint32_t bits, uint64_t* bad) {
+  for (uint64_t i = 1; i < n; ++i) {
+    bool less = keys[i - 1] < keys[i];
+    if (keys[i - 1] == keys[i]) {
+      const int c = memcmp(digests + 32 * (i - 1), digests + 32 * i, 32);
+      less = c < 0 || (c == 0 && values && values[i - 1] < values[i]);
+    }
+    if (!less) {
+      *bad = i;
+      return 1;
+    }
+  }
+  const uint64_t slots = 1ull << bits;
+  uint64_t i = 0;  // the entries whose bucket is below j
+  for (uint64_t j = 0; j <= slots; ++j) {
+    if (j == slots) {
+      i = n;
+    } else if (bits) {
+      while (i < n && (keys[i] >> (64 - bits)) < j) ++i;
+    }
+    if (dir[j] != i) {
+      *bad = j;
+      return 2;
+    }
+  }
+  return 0;
+}
+
+hipError_t holders_match(const IndexView& idx, const uint64_t* keys, const uint8_t* digests, const uint8_t* valid,
+                         uint32_t m, int64_t* pos, uint64_t* value, uint32_t* holders, unsigned long long* counts,
+                         hipStream_t st) {
+  hipError_t e;
+  if (counts && (e = hipMemsetAsync(counts, 0, kIndexMatchCounts * sizeof(unsigned long long), st))) return e;
+  if (!pos && !value && !holders && !counts) return hipSuccess;
+  hipLaunchKernelGGL(k_ch_match, dim3(ch_blocks(m)), dim3(kChTB), 0, st, idx, keys, digests, valid, m, pos, value,
+                     holders, counts);
+  return hipGetLastError();
+}
+
+hipError_t holders_add(uint8_t* ws, const IndexView& old, const uint64_t* keys, const uint8_t* digests,
+                       const uint64_t* values, const uint8_t* valid, uint32_t m, const IndexOut& out, int64_t* pos,
+                       uint8_t* flags, unsigned long long* counts, hipStream_t st) {
+  const HoldersAddLayout l = holders_add_layout(m);
+  uint32_t* src = at<uint32_t>(ws, l.ord_a);
+  uint32_t* dst = at<uint32_t>(ws, l.ord_b);
+  uint32_t* lbf = at<uint32_t>(ws, l.lbf);
+  uint32_t* lbs = at<uint32_t>(ws, l.lbs);
+  uint32_t* l1 = at<uint32_t>(ws, l.scan.l1);
+  uint32_t* l2 = at<uint32_t>(ws, l.scan.l2);
+  uint32_t* l3 = at<uint32_t>(ws, l.scan.l3);
+  uint32_t* na = at<uint32_t>(ws, l.scan.tot);
+  unsigned long long* cts = at<unsigned long long>(ws, l.counts);
+  const uint32_t cap = old.n + m;
+  const dim3 block(kChTB), grid(ch_blocks(m));
+  hipError_t e;
+  if ((e = hipMemsetAsync(na, 0, l.bytes - l.scan.tot, st))) return e;  // tot and counts
+  if (m) {
+    hipLaunchKernelGGL(k_ch_iota, grid, block, 0, st, src, m);
+    for (uint64_t w = 1; w < m; w <<= 1) {
+      hipLaunchKernelGGL(k_ch_merge, grid, block, 0, st, (const uint32_t*)src, dst, keys, digests, values, valid,
+                         (uint32_t)w, m);
+      uint32_t* t = src;
+      src = dst, dst = t;
+    }
+    if ((e = hipGetLastError())) return e;
+    hipLaunchKernelGGL(k_ch_head, grid, block, 0, st, old, (const uint32_t*)src, keys, digests, values, valid, m, lbf,
+                       l1);
+    ch_scan(ws, l.scan, st);
+    hipLaunchKernelGGL(k_ch_place, grid, block, 0, st, (const uint32_t*)src, (const uint32_t*)lbf,
+                       (const uint32_t*)l1, (const uint32_t*)l2, (const uint32_t*)l3, keys, digests, values, valid, m,
+                       out, cap, lbs, pos, flags, cts);
+    if ((e = hipGetLastError())) return e;
+  }
+  if (old.n)
+    hipLaunchKernelGGL(k_ch_place_old, dim3(ch_blocks(old.n)), block, 0, st, old, (const uint32_t*)lbs,
+                       (const uint32_t*)na, m, out, cap);
+  hipLaunchKernelGGL(k_ch_dir, dim3(ch_blocks(index_dir_slots(out.bits))), block, 0, st, (const uint64_t*)out.keys,
+                     old.n, (const uint32_t*)na, m, out.bits, out.dir);
+  if ((e = hipGetLastError())) return e;
+  if (counts) {
+    hipLaunchKernelGGL(k_ch_add_totals, dim3(1), dim3(64), 0, st, (const uint32_t*)na, m, old.n, cts);
+    if ((e = hipGetLastError())) return e;
+    return hipMemcpyAsync(counts, cts, kIndexAddCounts * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
+  }
+  return hipSuccess;
+}
+
+hipError_t holders_remove(uint8_t* ws, const IndexView& old, const uint64_t* removed, uint32_t r, const IndexOut& out,
+                          unsigned long long* counts, hipStream_t st) {
+  const HoldersRemoveLayout l = holders_remove_layout(old.n);
+  unsigned long long* masks = at<unsigned long long>(ws, l.masks);
+  uint32_t* l1 = at<uint32_t>(ws, l.scan.l1);
+  uint32_t* l2 = at<uint32_t>(ws, l.scan.l2);
+  uint32_t* l3 = at<uint32_t>(ws, l.scan.l3);
+  uint32_t* kept = at<uint32_t>(ws, l.scan.tot);
+  unsigned long long* cts = at<unsigned long long>(ws, l.counts);
+  const dim3 block(kChTB), grid(ch_blocks(old.n));
+  hipError_t e;
+  if ((e = hipMemsetAsync(kept, 0, l.bytes - l.scan.tot, st))) return e;  // tot and counts
+  if (old.n) {
+    hipLaunchKernelGGL(k_ch_rm_mark, grid, block, 0, st, old.values, old.n, removed, r, masks, l1);
+    ch_scan(ws, l.scan, st);
+    hipLaunchKernelGGL(k_ch_rm_scatter, grid, block, 0, st, old, (const unsigned long long*)masks,
+                       (const uint32_t*)l1, (const uint32_t*)l2, (const uint32_t*)l3, out, old.n);
+    if ((e = hipGetLastError())) return e;
+  }
+  hipLaunchKernelGGL(k_ch_dir, dim3(ch_blocks(index_dir_slots(out.bits))), block, 0, st, (const uint64_t*)out.keys, 0u,
+                     (const uint32_t*)kept, old.n, out.bits, out.dir);
+  if ((e = hipGetLastError())) return e;
+  if (counts) {
+    hipLaunchKernelGGL(k_ch_rm_totals, dim3(1), dim3(64), 0, st, (const uint32_t*)kept, old.n, r, cts);
+    if ((e = hipGetLastError())) return e;
+    return hipMemcpyAsync(counts, cts, kHoldersRemoveCounts * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
+  }
+  return hipSuccess;
+}
+
+}  // namespace sdcas

@@ -34,6 +34,7 @@
 #include "dupsets.h"
 #include "dirtree.h"
 #include "cdc.h"
+#include "chunk_holders.h"
 #include "chunk_index.h"
 #include "dist_dedup.h"
 #include "synth.h"
@@ -230,6 +231,9 @@ struct sdcas_ctx {
   // the chunk index (chunk_index.hip): the add's workspace, and the host
   // calls' device copies of their arrays
   DevBuf<uint8_t> ci_ws, ci_io;
+  // the holders index (chunk_holders.hip): the add's and the remove's
+  // workspace (the host calls' device copies are ci_io)
+  DevBuf<uint8_t> ch_ws;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -866,6 +870,7 @@ void sdcas_destroy(sdcas_ctx* c) {
   c->cd_stage.release();
   c->ci_ws.release();
   c->ci_io.release();
+  c->ch_ws.release();
   c->dist.release();
   c->sm_d_files.release();
   c->sm_nodes.release();
@@ -2974,6 +2979,296 @@ int sdcas_chunk_index_add(sdcas_ctx* c, const uint64_t* old_keys, const uint8_t*
       (m && out_flags && (e = hipMemcpyAsync(out_flags, io + o_fl, m, hipMemcpyDeviceToHost, st))))
     return c->hip_fail(e, "chunk_index_add D2H");
   if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_index_add sync");
+  if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+// ---- the holders index (chunk_holders.hip) --------------------------------------------
+
+int sdcas_chunk_holders_check(const uint64_t* keys, const uint8_t* digests32, const uint64_t* values,
+                              const uint32_t* dir, uint64_t n, uint32_t bits, uint64_t* out_first_bad) {
+  if (n > kIndexMaxEntries || bits > kIndexMaxBits) return SDCAS_E_CAPACITY;
+  if (!dir || (n && (!keys || !digests32))) return SDCAS_E_INVALID;
+  uint64_t bad = 0;
+  if (holders_check(keys, digests32, values, dir, n, bits, &bad)) {
+    if (out_first_bad) *out_first_bad = bad;
+    return SDCAS_E_INVALID;
+  }
+  return SDCAS_OK;
+}
+
+// the holders calls' workspace grown to `need` bytes; the stream waits first,
+// as an earlier call's kernels may still use what is freed
+static int holders_ws(sdcas_ctx* c, size_t need, hipStream_t st) {
+  if (need <= c->ch_ws.cap) return SDCAS_OK;
+  hipError_t e = c->scratch_sync();
+  if (!e) e = hipStreamSynchronize(st);
+  if (!e) e = c->ch_ws.ensure(need);
+  return e ? c->hip_fail(e, "chunk holders workspace") : SDCAS_OK;
+}
+
+// the remove's arguments: limits, the arrays it needs, old and removed against new
+static int holders_remove_args(sdcas_ctx* c, const char* who, const void* old_keys, const void* old_digests,
+                               const void* old_values, const void* old_dir, uint64_t n_old, uint32_t bits_old,
+                               const void* removed, size_t r, const void* new_keys, const void* new_digests,
+                               const void* new_values, const void* new_dir, uint32_t bits_new) {
+  if (int rc = index_view_args(c, who, old_keys, old_digests, old_dir, n_old, bits_old)) return rc;
+  if (bits_new > kIndexMaxBits) return c->fail(SDCAS_E_CAPACITY, "%s: a directory of %u bits exceeds 28", who, bits_new);
+  if (r > kIndexMaxEntries) return c->fail(SDCAS_E_CAPACITY, "%s: %zu removed values exceed 2^30", who, r);
+  if (r && !removed) return c->fail(SDCAS_E_INVALID, "%s: null removed values", who);
+  if (!new_dir || (n_old && (!new_keys || !new_digests || !new_values)))
+    return c->fail(SDCAS_E_INVALID, "%s: null array of the new index", who);
+  const void* o[5] = {old_keys, old_digests, old_values, old_dir, removed};
+  const uint64_t ob[5] = {8 * n_old, 32 * n_old, 8 * n_old, n_old ? 4 * index_dir_slots(bits_old) : 0, 8 * (uint64_t)r};
+  const void* w[4] = {new_keys, new_digests, new_values, new_dir};
+  const uint64_t wb[4] = {8 * n_old, 32 * n_old, 8 * n_old, 4 * index_dir_slots(bits_new)};
+  for (int i = 0; i < 5; ++i)
+    for (int j = 0; j < 4; ++j)
+      if (index_ranges_meet(o[i], ob[i], w[j], wb[j]))
+        return c->fail(SDCAS_E_INVALID, "%s: the new index overlaps the old one or the removed values", who);
+  return SDCAS_OK;
+}
+
+int sdcas_dev_chunk_holders_match(sdcas_ctx* c, const uint64_t* d_idx_keys, const uint8_t* d_idx_digests32,
+                                  const uint64_t* d_idx_values, const uint32_t* d_idx_dir, uint64_t n, uint32_t bits,
+                                  const uint64_t* d_keys, const uint8_t* d_digests32, const uint8_t* d_valid,
+                                  size_t m, int64_t* d_out_pos, uint64_t* d_out_value, uint32_t* d_out_holders,
+                                  uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_view_args(c, "dev_chunk_holders_match", d_idx_keys, d_idx_digests32, d_idx_dir, n, bits)) return rc;
+  if (int rc = index_batch_args(c, "dev_chunk_holders_match", d_keys, d_digests32, m)) return rc;
+  if ((((uintptr_t)d_idx_digests32 | (uintptr_t)d_digests32) & 15) ||
+      (((uintptr_t)d_idx_keys | (uintptr_t)d_idx_values | (uintptr_t)d_keys | (uintptr_t)d_out_pos |
+        (uintptr_t)d_out_value | (uintptr_t)d_counts) & 7) ||
+      (((uintptr_t)d_idx_dir | (uintptr_t)d_out_holders) & 3))
+    return c->fail(SDCAS_E_INVALID, "dev_chunk_holders_match: an array is misaligned (digests 16 B, directory and holders 4 B, others 8 B)");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  if (m == 0) {
+    if (d_counts && (e = hipMemsetAsync(d_counts, 0, kIndexMatchCounts * sizeof(uint64_t), call.st)))
+      return c->hip_fail(e, "counts");
+    return SDCAS_OK;
+  }
+  const IndexView v{d_idx_keys, d_idx_digests32, d_idx_values, d_idx_dir, (uint32_t)n, bits};
+  e = holders_match(v, d_keys, d_digests32, d_valid, (uint32_t)m, d_out_pos, d_out_value, d_out_holders,
+                    (unsigned long long*)d_counts, call.st);
+  return e ? c->hip_fail(e, "dev_chunk_holders_match") : SDCAS_OK;
+}
+
+int sdcas_chunk_holders_match(sdcas_ctx* c, const uint64_t* idx_keys, const uint8_t* idx_digests32,
+                              const uint64_t* idx_values, const uint32_t* idx_dir, uint64_t n, uint32_t bits,
+                              const uint64_t* keys, const uint8_t* digests32, const uint8_t* valid, size_t m,
+                              int64_t* out_pos, uint64_t* out_value, uint32_t* out_holders,
+                              sdcas_index_match_counts* out_counts) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_view_args(c, "chunk_holders_match", idx_keys, idx_digests32, idx_dir, n, bits)) return rc;
+  if (int rc = index_batch_args(c, "chunk_holders_match", keys, digests32, m)) return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  if (m == 0) return SDCAS_OK;
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = call.st;
+  const size_t dir_bytes = n ? 4 * (size_t)index_dir_slots(bits) : 0;
+  Parts p;
+  const size_t o_ik = p.take(8 * n), o_id = p.take(32 * n), o_iv = p.take(8 * n), o_dir = p.take(dir_bytes),
+               o_k = p.take(8 * m), o_d = p.take(32 * m), o_v = p.take(m), o_pos = p.take(8 * m),
+               o_val = p.take(8 * m), o_h = p.take(4 * m), o_cts = p.take(8 * kIndexMatchCounts);
+  if (int rc = index_io(c, p.o, st)) return rc;
+  uint8_t* io = c->ci_io.p;
+  if ((n && ((e = hipMemcpyAsync(io + o_ik, idx_keys, 8 * n, hipMemcpyHostToDevice, st)) ||
+             (e = hipMemcpyAsync(io + o_id, idx_digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
+             (idx_values && (e = hipMemcpyAsync(io + o_iv, idx_values, 8 * n, hipMemcpyHostToDevice, st))) ||
+             (e = hipMemcpyAsync(io + o_dir, idx_dir, dir_bytes, hipMemcpyHostToDevice, st)))) ||
+      (e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
+      (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
+      (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))
+    return c->hip_fail(e, "chunk_holders_match H2D");
+  const IndexView v{reinterpret_cast<const uint64_t*>(io + o_ik), io + o_id,
+                    idx_values ? reinterpret_cast<const uint64_t*>(io + o_iv) : nullptr,
+                    reinterpret_cast<const uint32_t*>(io + o_dir), (uint32_t)n, bits};
+  if ((e = holders_match(v, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d, valid ? io + o_v : nullptr,
+                         (uint32_t)m, out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr,
+                         out_value ? reinterpret_cast<uint64_t*>(io + o_val) : nullptr,
+                         out_holders ? reinterpret_cast<uint32_t*>(io + o_h) : nullptr,
+                         out_counts ? reinterpret_cast<unsigned long long*>(io + o_cts) : nullptr, st)))
+    return c->hip_fail(e, "chunk_holders_match");
+  if ((out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
+      (out_value && (e = hipMemcpyAsync(out_value, io + o_val, 8 * m, hipMemcpyDeviceToHost, st))) ||
+      (out_holders && (e = hipMemcpyAsync(out_holders, io + o_h, 4 * m, hipMemcpyDeviceToHost, st))) ||
+      (out_counts && (e = hipMemcpyAsync(out_counts, io + o_cts, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
+    return c->hip_fail(e, "chunk_holders_match D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_holders_match sync");
+  return SDCAS_OK;
+}
+
+int sdcas_dev_chunk_holders_add(sdcas_ctx* c, const uint64_t* d_old_keys, const uint8_t* d_old_digests32,
+                                const uint64_t* d_old_values, const uint32_t* d_old_dir, uint64_t n_old,
+                                uint32_t bits_old, const uint64_t* d_keys, const uint8_t* d_digests32,
+                                const uint64_t* d_values, const uint8_t* d_valid, size_t m, uint64_t* d_new_keys,
+                                uint8_t* d_new_digests32, uint64_t* d_new_values, uint32_t* d_new_dir,
+                                uint32_t bits_new, int64_t* d_out_pos, uint8_t* d_out_flags, uint64_t* d_counts,
+                                void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_add_args(c, "dev_chunk_holders_add", d_old_keys, d_old_digests32, d_old_values, d_old_dir, n_old,
+                              bits_old, d_keys, d_digests32, m, d_new_keys, d_new_digests32, d_new_values, d_new_dir,
+                              bits_new))
+    return rc;
+  if ((((uintptr_t)d_old_digests32 | (uintptr_t)d_digests32 | (uintptr_t)d_new_digests32) & 15) ||
+      (((uintptr_t)d_old_keys | (uintptr_t)d_old_values | (uintptr_t)d_keys | (uintptr_t)d_values |
+        (uintptr_t)d_new_keys | (uintptr_t)d_new_values | (uintptr_t)d_out_pos | (uintptr_t)d_counts) & 7) ||
+      (((uintptr_t)d_old_dir | (uintptr_t)d_new_dir) & 3))
+    return c->fail(SDCAS_E_INVALID, "dev_chunk_holders_add: an array is misaligned (digests 16 B, directories 4 B, others 8 B)");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = holders_ws(c, (size_t)holders_add_layout(m).bytes, call.st)) return rc;
+  const IndexView old{d_old_keys, d_old_digests32, d_old_values, d_old_dir, (uint32_t)n_old, bits_old};
+  const IndexOut out{d_new_keys, d_new_digests32, d_new_values, d_new_dir, bits_new};
+  hipError_t e = holders_add(c->ch_ws.p, old, d_keys, d_digests32, d_values, d_valid, (uint32_t)m, out, d_out_pos,
+                             d_out_flags, (unsigned long long*)d_counts, call.st);
+  return e ? c->hip_fail(e, "dev_chunk_holders_add") : SDCAS_OK;
+}
+
+int sdcas_chunk_holders_add(sdcas_ctx* c, const uint64_t* old_keys, const uint8_t* old_digests32,
+                            const uint64_t* old_values, const uint32_t* old_dir, uint64_t n_old, uint32_t bits_old,
+                            const uint64_t* keys, const uint8_t* digests32, const uint64_t* values,
+                            const uint8_t* valid, size_t m, uint64_t* new_keys, uint8_t* new_digests32,
+                            uint64_t* new_values, uint32_t* new_dir, uint32_t bits_new, int64_t* out_pos,
+                            uint8_t* out_flags, sdcas_index_add_counts* out_counts) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_add_args(c, "chunk_holders_add", old_keys, old_digests32, old_values, old_dir, n_old, bits_old,
+                              keys, digests32, m, new_keys, new_digests32, new_values, new_dir, bits_new))
+    return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = call.st;
+  const size_t n = n_old, cap = n_old + m;
+  const size_t odir_bytes = n ? 4 * (size_t)index_dir_slots(bits_old) : 0, ndir_bytes = 4 * (size_t)index_dir_slots(bits_new);
+  Parts p;
+  const size_t o_ok = p.take(8 * n), o_od = p.take(32 * n), o_ov = p.take(8 * n), o_odir = p.take(odir_bytes),
+               o_k = p.take(8 * m), o_d = p.take(32 * m), o_val = p.take(8 * m), o_v = p.take(m),
+               o_nk = p.take(8 * cap), o_nd = p.take(32 * cap), o_nv = p.take(8 * cap), o_ndir = p.take(ndir_bytes),
+               o_pos = p.take(8 * m), o_fl = p.take(m), o_cts = p.take(8 * kIndexAddCounts);
+  if (int rc = index_io(c, p.o, st)) return rc;
+  if (int rc = holders_ws(c, (size_t)holders_add_layout(m).bytes, st)) return rc;
+  uint8_t* io = c->ci_io.p;
+  if ((n && ((e = hipMemcpyAsync(io + o_ok, old_keys, 8 * n, hipMemcpyHostToDevice, st)) ||
+             (e = hipMemcpyAsync(io + o_od, old_digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
+             (old_values && (e = hipMemcpyAsync(io + o_ov, old_values, 8 * n, hipMemcpyHostToDevice, st))) ||
+             (e = hipMemcpyAsync(io + o_odir, old_dir, odir_bytes, hipMemcpyHostToDevice, st)))) ||
+      (m && ((e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
+             (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
+             (values && (e = hipMemcpyAsync(io + o_val, values, 8 * m, hipMemcpyHostToDevice, st))) ||
+             (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))))
+    return c->hip_fail(e, "chunk_holders_add H2D");
+  const IndexView old{reinterpret_cast<const uint64_t*>(io + o_ok), io + o_od,
+                      old_values ? reinterpret_cast<const uint64_t*>(io + o_ov) : nullptr,
+                      reinterpret_cast<const uint32_t*>(io + o_odir), (uint32_t)n, bits_old};
+  const IndexOut out{reinterpret_cast<uint64_t*>(io + o_nk), io + o_nd, reinterpret_cast<uint64_t*>(io + o_nv),
+                     reinterpret_cast<uint32_t*>(io + o_ndir), bits_new};
+  if ((e = holders_add(c->ch_ws.p, old, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d,
+                       values ? reinterpret_cast<const uint64_t*>(io + o_val) : nullptr, valid ? io + o_v : nullptr,
+                       (uint32_t)m, out, out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr,
+                       out_flags ? io + o_fl : nullptr, reinterpret_cast<unsigned long long*>(io + o_cts), st)))
+    return c->hip_fail(e, "chunk_holders_add");
+  // the counts down first: they say how many entries of the new arrays follow
+  sdcas_index_add_counts cts;
+  if ((e = hipMemcpyAsync(&cts, io + o_cts, sizeof cts, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
+    return c->hip_fail(e, "chunk_holders_add counts");
+  const size_t nn = (size_t)cts.entries_new;
+  if (nn > cap) return c->fail(SDCAS_E_HIP, "chunk_holders_add: counts out of range");
+  if ((nn && ((e = hipMemcpyAsync(new_keys, io + o_nk, 8 * nn, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(new_digests32, io + o_nd, 32 * nn, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(new_values, io + o_nv, 8 * nn, hipMemcpyDeviceToHost, st)))) ||
+      (e = hipMemcpyAsync(new_dir, io + o_ndir, ndir_bytes, hipMemcpyDeviceToHost, st)) ||
+      (m && out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
+      (m && out_flags && (e = hipMemcpyAsync(out_flags, io + o_fl, m, hipMemcpyDeviceToHost, st))))
+    return c->hip_fail(e, "chunk_holders_add D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_holders_add sync");
+  if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+int sdcas_dev_chunk_holders_remove(sdcas_ctx* c, const uint64_t* d_old_keys, const uint8_t* d_old_digests32,
+                                   const uint64_t* d_old_values, const uint32_t* d_old_dir, uint64_t n_old,
+                                   uint32_t bits_old, const uint64_t* d_removed, size_t r, uint64_t* d_new_keys,
+                                   uint8_t* d_new_digests32, uint64_t* d_new_values, uint32_t* d_new_dir,
+                                   uint32_t bits_new, uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = holders_remove_args(c, "dev_chunk_holders_remove", d_old_keys, d_old_digests32, d_old_values, d_old_dir,
+                                   n_old, bits_old, d_removed, r, d_new_keys, d_new_digests32, d_new_values, d_new_dir,
+                                   bits_new))
+    return rc;
+  if ((((uintptr_t)d_old_digests32 | (uintptr_t)d_new_digests32) & 15) ||
+      (((uintptr_t)d_old_keys | (uintptr_t)d_old_values | (uintptr_t)d_removed | (uintptr_t)d_new_keys |
+        (uintptr_t)d_new_values | (uintptr_t)d_counts) & 7) ||
+      (((uintptr_t)d_old_dir | (uintptr_t)d_new_dir) & 3))
+    return c->fail(SDCAS_E_INVALID, "dev_chunk_holders_remove: an array is misaligned (digests 16 B, directories 4 B, others 8 B)");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = holders_ws(c, (size_t)holders_remove_layout(n_old).bytes, call.st)) return rc;
+  const IndexView old{d_old_keys, d_old_digests32, d_old_values, d_old_dir, (uint32_t)n_old, bits_old};
+  const IndexOut out{d_new_keys, d_new_digests32, d_new_values, d_new_dir, bits_new};
+  hipError_t e = holders_remove(c->ch_ws.p, old, d_removed, (uint32_t)r, out, (unsigned long long*)d_counts, call.st);
+  return e ? c->hip_fail(e, "dev_chunk_holders_remove") : SDCAS_OK;
+}
+
+int sdcas_chunk_holders_remove(sdcas_ctx* c, const uint64_t* old_keys, const uint8_t* old_digests32,
+                               const uint64_t* old_values, const uint32_t* old_dir, uint64_t n_old,
+                               uint32_t bits_old, const uint64_t* removed, size_t r, uint64_t* new_keys,
+                               uint8_t* new_digests32, uint64_t* new_values, uint32_t* new_dir, uint32_t bits_new,
+                               sdcas_holders_remove_counts* out_counts) {
+  static_assert(sizeof(sdcas_holders_remove_counts) == kHoldersRemoveCounts * sizeof(uint64_t), "four u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = holders_remove_args(c, "chunk_holders_remove", old_keys, old_digests32, old_values, old_dir, n_old,
+                                   bits_old, removed, r, new_keys, new_digests32, new_values, new_dir, bits_new))
+    return rc;
+  for (size_t i = 1; i < r; ++i)
+    if (removed[i - 1] >= removed[i])
+      return c->fail(SDCAS_E_INVALID, "chunk_holders_remove: removed value %zu does not ascend", i);
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = call.st;
+  const size_t n = n_old;
+  const size_t odir_bytes = n ? 4 * (size_t)index_dir_slots(bits_old) : 0, ndir_bytes = 4 * (size_t)index_dir_slots(bits_new);
+  Parts p;
+  const size_t o_ok = p.take(8 * n), o_od = p.take(32 * n), o_ov = p.take(8 * n), o_odir = p.take(odir_bytes),
+               o_r = p.take(8 * r), o_nk = p.take(8 * n), o_nd = p.take(32 * n), o_nv = p.take(8 * n),
+               o_ndir = p.take(ndir_bytes), o_cts = p.take(8 * kHoldersRemoveCounts);
+  if (int rc = index_io(c, p.o, st)) return rc;
+  if (int rc = holders_ws(c, (size_t)holders_remove_layout(n).bytes, st)) return rc;
+  uint8_t* io = c->ci_io.p;
+  if ((n && ((e = hipMemcpyAsync(io + o_ok, old_keys, 8 * n, hipMemcpyHostToDevice, st)) ||
+             (e = hipMemcpyAsync(io + o_od, old_digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
+             (old_values && (e = hipMemcpyAsync(io + o_ov, old_values, 8 * n, hipMemcpyHostToDevice, st))) ||
+             (e = hipMemcpyAsync(io + o_odir, old_dir, odir_bytes, hipMemcpyHostToDevice, st)))) ||
+      (r && (e = hipMemcpyAsync(io + o_r, removed, 8 * r, hipMemcpyHostToDevice, st))))
+    return c->hip_fail(e, "chunk_holders_remove H2D");
+  const IndexView old{reinterpret_cast<const uint64_t*>(io + o_ok), io + o_od,
+                      old_values ? reinterpret_cast<const uint64_t*>(io + o_ov) : nullptr,
+                      reinterpret_cast<const uint32_t*>(io + o_odir), (uint32_t)n, bits_old};
+  const IndexOut out{reinterpret_cast<uint64_t*>(io + o_nk), io + o_nd, reinterpret_cast<uint64_t*>(io + o_nv),
+                     reinterpret_cast<uint32_t*>(io + o_ndir), bits_new};
+  if ((e = holders_remove(c->ch_ws.p, old, reinterpret_cast<const uint64_t*>(io + o_r), (uint32_t)r, out,
+                          reinterpret_cast<unsigned long long*>(io + o_cts), st)))
+    return c->hip_fail(e, "chunk_holders_remove");
+  // the counts down first: they say how many entries of the new arrays follow
+  sdcas_holders_remove_counts cts;
+  if ((e = hipMemcpyAsync(&cts, io + o_cts, sizeof cts, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
+    return c->hip_fail(e, "chunk_holders_remove counts");
+  const size_t nn = (size_t)cts.entries_new;
+  if (nn > n) return c->fail(SDCAS_E_HIP, "chunk_holders_remove: counts out of range");
+  if ((nn && ((e = hipMemcpyAsync(new_keys, io + o_nk, 8 * nn, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(new_digests32, io + o_nd, 32 * nn, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(new_values, io + o_nv, 8 * nn, hipMemcpyDeviceToHost, st)))) ||
+      (e = hipMemcpyAsync(new_dir, io + o_ndir, ndir_bytes, hipMemcpyDeviceToHost, st)))
+    return c->hip_fail(e, "chunk_holders_remove D2H");
+  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_holders_remove sync");
   if (out_counts) *out_counts = cts;
   return SDCAS_OK;
 }

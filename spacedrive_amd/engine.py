@@ -811,13 +811,98 @@ class Engine:
         e = int(counts.entries_new)
         return (nk[:e].copy(), nd[:e].copy(), nv[:e].copy(), ndir, bits_new), pos, flags, counts.as_dict()
 
+    # -- the holders index: a chunk index that keeps every holder and can forget files --
+    @staticmethod
+    def chunk_holders_check(keys, digests, values, dir, bits):
+        """sdcas_chunk_holders_check (no GPU) over host arrays -> (rc,
+        first_bad) as chunk_index_check, in the order of the triple (key,
+        digest, value); values None: all 0"""
+        keys, digests, dir = _arr(keys, np.uint64), _arr(digests, np.uint8), _arr(dir, np.uint32)
+        values = None if values is None else _arr(values, np.uint64)
+        n = keys.size
+        if digests.size != 32 * n or (values is not None and values.size != n):
+            raise ValueError(f"chunk_holders_check: {n} keys, {digests.size} digest bytes")
+        if int(bits) <= N.SDCAS_INDEX_MAX_BITS and dir.size != (1 << int(bits)) + 1:
+            raise ValueError(f"chunk_holders_check: {dir.size} directory slots for {int(bits)} bits")
+        bad = ctypes.c_uint64(0)
+        rc = N.load().sdcas_chunk_holders_check(_ptr(keys), _ptr(digests), _ptr(values), _ptr(dir), n, int(bits),
+                                                ctypes.byref(bad))
+        return rc, int(bad.value) if rc == N.SDCAS_E_INVALID else None
+
+    def chunk_holders_match(self, index, keys, digests, valid=None):
+        """sdcas_chunk_holders_match over host arrays; index as for
+        chunk_index_match -> (pos int64[m]: the FIRST entry with the query's
+        pair or -1, value uint64[m]: its value (the lowest holder) or 0,
+        holders uint32[m]: the entries with the pair, counts)"""
+        ik, idg, iv, idir, bits = self._index_arrays(index, "chunk_holders_match")
+        keys, digests, va = self._index_batch(keys, digests, valid, "chunk_holders_match")
+        m = keys.size
+        pos, value, holders = np.zeros(m, np.int64), np.zeros(m, np.uint64), np.zeros(m, np.uint32)
+        counts = N.IndexMatchCounts()
+        self._check(self.L.sdcas_chunk_holders_match(self.ctx, _ptr(ik), _ptr(idg), _ptr(iv), _ptr(idir), ik.size,
+                                                     bits, _ptr(keys), _ptr(digests), _ptr(va), m, _ptr(pos),
+                                                     _ptr(value), _ptr(holders), ctypes.byref(counts)),
+                    "sdcas_chunk_holders_match")
+        return pos, value, holders, counts.as_dict()
+
+    def chunk_holders_add(self, index, keys, digests, values, valid=None, bits_new=None):
+        """sdcas_chunk_holders_add over host arrays: the sorted distinct union
+        of the index's triples and the batch's valid (key, digest, value)
+        triples -> (new index tuple, trimmed to entries_new, pos int64[m],
+        flags uint8[m], counts), as chunk_index_add but read per triple"""
+        ik, idg, iv, idir, bits = self._index_arrays(index, "chunk_holders_add")
+        keys, digests, va = self._index_batch(keys, digests, valid, "chunk_holders_add")
+        m, n = keys.size, ik.size
+        values = None if values is None else _arr(values, np.uint64)
+        if values is not None and values.size != m:
+            raise ValueError(f"chunk_holders_add: {m} keys, {values.size} values")
+        if bits_new is None:
+            bits_new = self.chunk_index_dir_bits(n + m)
+        bits_new = int(bits_new)
+        if not 0 <= bits_new <= N.SDCAS_INDEX_MAX_BITS:
+            raise N.SdcasError(N.SDCAS_E_CAPACITY, f"chunk_holders_add: a directory of {bits_new} bits")
+        nk, nd, nv = np.zeros(n + m, np.uint64), np.zeros((n + m, 32), np.uint8), np.zeros(n + m, np.uint64)
+        ndir = np.zeros((1 << bits_new) + 1, np.uint32)
+        pos, flags = np.zeros(m, np.int64), np.zeros(m, np.uint8)
+        counts = N.IndexAddCounts()
+        self._check(self.L.sdcas_chunk_holders_add(self.ctx, _ptr(ik), _ptr(idg), _ptr(iv), _ptr(idir), n, bits,
+                                                   _ptr(keys), _ptr(digests), _ptr(values), _ptr(va), m,
+                                                   nk.ctypes.data, nd.ctypes.data, nv.ctypes.data, ndir.ctypes.data,
+                                                   bits_new, _ptr(pos), _ptr(flags), ctypes.byref(counts)),
+                    "sdcas_chunk_holders_add")
+        e = int(counts.entries_new)
+        return (nk[:e].copy(), nd[:e].copy(), nv[:e].copy(), ndir, bits_new), pos, flags, counts.as_dict()
+
+    def chunk_holders_remove(self, index, removed, bits_new=None):
+        """sdcas_chunk_holders_remove over host arrays: the index's entries
+        whose value is not in `removed` (uint64, strictly ascending), in their
+        order, with the directory at bits_new (None: the index's width) ->
+        (new index tuple, trimmed to entries_new, counts: dict of
+        sdcas_holders_remove_counts' four fields)"""
+        ik, idg, iv, idir, bits = self._index_arrays(index, "chunk_holders_remove")
+        removed = _arr(removed, np.uint64)
+        n = ik.size
+        bits_new = bits if bits_new is None else int(bits_new)
+        if not 0 <= bits_new <= N.SDCAS_INDEX_MAX_BITS:
+            raise N.SdcasError(N.SDCAS_E_CAPACITY, f"chunk_holders_remove: a directory of {bits_new} bits")
+        nk, nd, nv = np.zeros(n, np.uint64), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint64)
+        ndir = np.zeros((1 << bits_new) + 1, np.uint32)
+        counts = N.HoldersRemoveCounts()
+        self._check(self.L.sdcas_chunk_holders_remove(self.ctx, _ptr(ik), _ptr(idg), _ptr(iv), _ptr(idir), n, bits,
+                                                      _ptr(removed), removed.size, nk.ctypes.data, nd.ctypes.data,
+                                                      nv.ctypes.data, ndir.ctypes.data, bits_new,
+                                                      ctypes.byref(counts)), "sdcas_chunk_holders_remove")
+        e = int(counts.entries_new)
+        return (nk[:e].copy(), nd[:e].copy(), nv[:e].copy(), ndir, bits_new), counts.as_dict()
+
     def similar_files_indexed(self, paths, file_ids, index, params=None, window_bytes=256 << 20):
         """similar_files_streamed against what earlier calls stored: the files
         are chunked through chunk_stream, their chunks confirmed within the
-        batch, matched against `index` (a ChunkIndex) and then added to it
-        with the value file_ids[chunk_file]. The origin of a chunk is the
-        stored value when the index holds it, else the id of the file of its
-        lowest copy in the batch; `peer` is a FILE ID (from file_ids or a
+        batch, matched against `index` (a ChunkIndex or a ChunkHolders) and
+        then added to it with the value file_ids[chunk_file]. The origin of a
+        chunk is the stored value when the index holds it (a ChunkIndex: the
+        first owner; a ChunkHolders: the lowest holder that was not removed),
+        else the id of the file of its lowest copy in the batch; `peer` is a FILE ID (from file_ids or a
         stored value; ties go to the lowest id), -1 for none. Every listed
         file has its own id, also a path listed twice. -> dict with the per-file
         arrays "sizes", "new_bytes", "self_bytes", "other_bytes",
@@ -910,6 +995,44 @@ class Engine:
                                                      new_values or None, new_dir or None, int(bits_new), pos or None,
                                                      flags or None, counts or None, stream or None),
                     "dev_chunk_index_add")
+
+    def dev_chunk_holders_match(self, idx_keys, idx_digests, idx_values, idx_dir, n, bits, keys, digests, valid, m,
+                                pos=0, value=0, holders=0, counts=0, stream=0):
+        """chunk_holders_match over device arrays (sdcas_dev_chunk_holders_match);
+        idx_values, valid and any output may be 0; holders uint32[m], counts
+        four uint64; nothing waits for the device and no workspace is used"""
+        self._check(self.L.sdcas_dev_chunk_holders_match(self.ctx, idx_keys or None, idx_digests or None,
+                                                         idx_values or None, idx_dir or None, int(n), int(bits),
+                                                         keys or None, digests or None, valid or None, int(m),
+                                                         pos or None, value or None, holders or None, counts or None,
+                                                         stream or None), "dev_chunk_holders_match")
+
+    def dev_chunk_holders_add(self, old_keys, old_digests, old_values, old_dir, n_old, bits_old, keys, digests, values,
+                              valid, m, new_keys, new_digests, new_values, new_dir, bits_new, pos=0, flags=0,
+                              counts=0, stream=0):
+        """chunk_holders_add over device arrays (sdcas_dev_chunk_holders_add),
+        with dev_chunk_index_add's arguments and rules"""
+        self._check(self.L.sdcas_dev_chunk_holders_add(self.ctx, old_keys or None, old_digests or None,
+                                                       old_values or None, old_dir or None, int(n_old), int(bits_old),
+                                                       keys or None, digests or None, values or None, valid or None,
+                                                       int(m), new_keys or None, new_digests or None,
+                                                       new_values or None, new_dir or None, int(bits_new),
+                                                       pos or None, flags or None, counts or None, stream or None),
+                    "dev_chunk_holders_add")
+
+    def dev_chunk_holders_remove(self, old_keys, old_digests, old_values, old_dir, n_old, bits_old, removed, r,
+                                 new_keys, new_digests, new_values, new_dir, bits_new, counts=0, stream=0):
+        """chunk_holders_remove over device arrays (sdcas_dev_chunk_holders_remove):
+        the new arrays hold n_old entries (the directory 2^bits_new + 1) and
+        must overlap neither the old ones nor `removed` (uint64[r], strictly
+        ascending); counts four uint64, entries_new among them; nothing waits
+        for the device once the workspace for n_old exists"""
+        self._check(self.L.sdcas_dev_chunk_holders_remove(self.ctx, old_keys or None, old_digests or None,
+                                                          old_values or None, old_dir or None, int(n_old),
+                                                          int(bits_old), removed or None, int(r), new_keys or None,
+                                                          new_digests or None, new_values or None, new_dir or None,
+                                                          int(bits_new), counts or None, stream or None),
+                    "dev_chunk_holders_remove")
 
     def dev_chunk_windows(self, blob, offs, lens, final, n, max_chunks, max_slots, params=None, file_chunks=0,
                           chunk_off=0, chunk_len=0, chunk_file=0, keys=0, digests=0, consumed=0, counts=0, stream=0):
@@ -1218,6 +1341,166 @@ class ChunkIndex:
         rc, bad = Engine.chunk_index_check(keys, digests, dir, bits)
         if rc != N.SDCAS_OK:
             raise ValueError(f"{path}: not a chunk index (sdcas error {rc}" +
+                             (f", first at entry or slot {bad})" if bad is not None else ")"))
+        ix = cls(engine, device)
+        with torch.cuda.stream(ix.stream):
+            ix.keys, ix.digests = ix._upload(keys, np.int64), ix._upload(digests, np.uint8)
+            ix.values, ix.dir = ix._upload(values, np.int64), ix._upload(dir, np.int32)
+        ix.n, ix.bits = n, bits
+        return ix
+
+
+class ChunkHolders(ChunkIndex):
+    """A holders index (include/sdcas.h) kept on the device: a ChunkIndex that
+    stores EVERY file that holds a pair, one entry per (key, digest, file id),
+    sorted by that triple, and so can forget files again. `match` gives a
+    pair's lowest holder and the number of its holders; `add` merges the
+    batch's unseen triples; `remove(file_ids)` streams the index through once
+    and leaves, byte for byte, the index built from the files that remain.
+
+    The tensors, the stream and the `_upload` / `_match_dev` / `_add_dev`
+    contract are ChunkIndex's, so Engine.similar_files_indexed takes either
+    kind; with this one the origin of a stored chunk is its lowest holder."""
+
+    # -- match ----------------------------------------------------------------------
+    def _match_holders_dev(self, d_keys, d_digests, d_valid):
+        """device tensors in, device tensors out: (pos int64[m], value
+        int64[m]: the uint64's bits, holders int32[m], counts dict — reading
+        them is the wait)"""
+        import torch
+        m = d_keys.numel()
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else 0
+        with torch.cuda.stream(self.stream):
+            pos = torch.empty(m, dtype=torch.int64, device=self.device)
+            value = torch.empty(m, dtype=torch.int64, device=self.device)
+            holders = torch.empty(m, dtype=torch.int32, device=self.device)
+            counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+            self.engine.dev_chunk_holders_match(p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n,
+                                                self.bits, p(d_keys), p(d_digests), p(d_valid), m, p(pos), p(value),
+                                                p(holders), counts.data_ptr(), stream=self.stream.cuda_stream)
+            c = [int(v) for v in counts.cpu()]
+        return pos, value, holders, dict(zip((name for name, _ in N.IndexMatchCounts._fields_), c))
+
+    def _match_dev(self, d_keys, d_digests, d_valid):
+        """ChunkIndex._match_dev's triple: pos is the pair's first entry, value
+        its lowest holder"""
+        pos, value, _, counts = self._match_holders_dev(d_keys, d_digests, d_valid)
+        return pos, value, counts
+
+    def match(self, keys, digests, valid=None):
+        """only the batch goes up -> (pos int64[m], value uint64[m], holders
+        uint32[m], counts), as Engine.chunk_holders_match"""
+        import torch
+        with torch.cuda.stream(self.stream):
+            d_keys, d_dig, d_valid = self._batch(keys, digests, valid, "ChunkHolders.match")
+            pos, value, holders, counts = self._match_holders_dev(d_keys, d_dig, d_valid)
+            return (pos.cpu().numpy(), value.cpu().numpy().view(np.uint64), holders.cpu().numpy().view(np.uint32),
+                    counts)
+
+    # -- add ------------------------------------------------------------------------
+    def _add_dev(self, d_keys, d_digests, d_values, d_valid):
+        """ChunkIndex._add_dev with the holders add: the batch's unseen
+        (key, digest, value) triples merged in"""
+        import torch
+        m = d_keys.numel()
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else 0
+        bits_new = self.engine.chunk_index_dir_bits(self.n + m)
+        with torch.cuda.stream(self.stream):
+            if m == 0:  # nothing to merge: the index stays as it is
+                return (torch.empty(0, dtype=torch.int64, device=self.device),
+                        torch.empty(0, dtype=torch.uint8, device=self.device),
+                        dict(zip((name for name, _ in N.IndexAddCounts._fields_), (0, 0, 0, 0, self.n, self.n))))
+            cap = self.n + m
+            keys = torch.empty(cap, dtype=torch.int64, device=self.device)
+            digests = torch.empty(32 * cap, dtype=torch.uint8, device=self.device)
+            values = torch.empty(cap, dtype=torch.int64, device=self.device)
+            dir = torch.empty((1 << bits_new) + 1, dtype=torch.int32, device=self.device)
+            pos = torch.empty(m, dtype=torch.int64, device=self.device)
+            flags = torch.empty(m, dtype=torch.uint8, device=self.device)
+            counts = torch.zeros(6, dtype=torch.int64, device=self.device)
+            self.engine.dev_chunk_holders_add(p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n,
+                                              self.bits, p(d_keys), p(d_digests), p(d_values), p(d_valid), m, p(keys),
+                                              p(digests), p(values), dir.data_ptr(), bits_new, p(pos), p(flags),
+                                              counts.data_ptr(), stream=self.stream.cuda_stream)
+            c = [int(v) for v in counts.cpu()]
+            n_new = c[5]
+            if not self.n <= n_new <= cap:
+                raise N.SdcasError(N.SDCAS_E_HIP, f"ChunkHolders.add: {n_new} entries from {self.n} and a batch of {m}")
+            self.keys, self.digests, self.values, self.dir = keys[:n_new], digests[:32 * n_new], values[:n_new], dir
+            self.n, self.bits = n_new, bits_new
+        return pos, flags, dict(zip((name for name, _ in N.IndexAddCounts._fields_), c))
+
+    # -- remove ---------------------------------------------------------------------
+    def remove(self, file_ids, bits_new=None):
+        """every entry whose value is one of file_ids taken out (the ids are
+        sorted and made distinct here): new arrays of n entries, the directory
+        at bits_new (None: the width the index has; a wide directory is legal
+        and only costs memory), entries_new read (the one wait), the arrays
+        swapped -> counts: dict of sdcas_holders_remove_counts' four fields"""
+        import torch
+        ids = np.unique(_arr(file_ids, np.uint64).reshape(-1))
+        bits_new = self.bits if bits_new is None else int(bits_new)
+        if not 0 <= bits_new <= N.SDCAS_INDEX_MAX_BITS:
+            raise N.SdcasError(N.SDCAS_E_CAPACITY, f"ChunkHolders.remove: a directory of {bits_new} bits")
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else 0
+        n = self.n
+        with torch.cuda.stream(self.stream):
+            d_ids = self._upload(ids, np.int64)
+            keys = torch.empty(n, dtype=torch.int64, device=self.device)
+            digests = torch.empty(32 * n, dtype=torch.uint8, device=self.device)
+            values = torch.empty(n, dtype=torch.int64, device=self.device)
+            dir = torch.empty((1 << bits_new) + 1, dtype=torch.int32, device=self.device)
+            counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+            self.engine.dev_chunk_holders_remove(p(self.keys), p(self.digests), p(self.values), p(self.dir), n,
+                                                 self.bits, p(d_ids), ids.size, p(keys), p(digests), p(values),
+                                                 dir.data_ptr(), bits_new, counts.data_ptr(),
+                                                 stream=self.stream.cuda_stream)
+            c = [int(v) for v in counts.cpu()]
+            n_new = c[2]
+            if not 0 <= n_new <= n:
+                raise N.SdcasError(N.SDCAS_E_HIP, f"ChunkHolders.remove: {n_new} entries left of {n}")
+            self.keys, self.digests, self.values, self.dir = keys[:n_new], digests[:32 * n_new], values[:n_new], dir
+            self.n, self.bits = n_new, bits_new
+        return dict(zip((name for name, _ in N.HoldersRemoveCounts._fields_), c))
+
+    # -- other sources ----------------------------------------------------------------
+    @classmethod
+    def from_index(cls, chunk_index):
+        """a ChunkIndex's arrays adopted by device copy: every chunk index is a
+        holders index, in which each pair has the one holder that came first"""
+        import torch
+        ix = cls(chunk_index.engine, chunk_index.device)
+        ready = torch.cuda.Event()
+        ready.record(chunk_index.stream)
+        ix.stream.wait_event(ready)
+        with torch.cuda.stream(ix.stream):  # the copies are this index's own; the source may change once they are made
+            ix.keys, ix.digests, ix.values, ix.dir = (t.clone() for t in (chunk_index.keys, chunk_index.digests,
+                                                                          chunk_index.values, chunk_index.dir))
+        ix.stream.synchronize()
+        ix.n, ix.bits = chunk_index.n, chunk_index.bits
+        return ix
+
+    @classmethod
+    def load(cls, engine, path, device=None):
+        """an index saved by `save`: checked (sdcas_chunk_holders_check)
+        before anything goes to the device; ValueError when it is not a
+        holders index"""
+        import torch
+        import zipfile
+        try:  # the archive's own checksums catch a byte that changed on disk
+            with np.load(path) as z:
+                keys, digests, values, dir, bits = (z["keys"].astype(np.uint64), z["digests"].astype(np.uint8),
+                                                    z["values"].astype(np.uint64), z["dir"].astype(np.uint32),
+                                                    int(z["bits"]))
+        except (zipfile.BadZipFile, KeyError, EOFError, OSError, ValueError) as e:
+            raise ValueError(f"{path}: not a saved holders index ({e})") from e
+        n = keys.size
+        if digests.size != 32 * n or values.size != n or not 0 <= bits <= N.SDCAS_INDEX_MAX_BITS or \
+                dir.size != (1 << bits) + 1:
+            raise ValueError(f"{path}: the arrays' sizes do not make an index")
+        rc, bad = Engine.chunk_holders_check(keys, digests, values, dir, bits)
+        if rc != N.SDCAS_OK:
+            raise ValueError(f"{path}: not a holders index (sdcas error {rc}" +
                              (f", first at entry or slot {bad})" if bad is not None else ")"))
         ix = cls(engine, device)
         with torch.cuda.stream(ix.stream):
