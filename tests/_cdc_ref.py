@@ -5,6 +5,7 @@ the code under test.
 
 gear_table()           G[b] = high 32 bits of sds_mix64("SDCDC001" + b)
 window_hash(x)         h(p) = sum over k in 0..min(31, p) of G[x[p - k]] << k, by 32 shifted adds
+window_with_hash(t, r) 32 bytes whose window hash is t wherever they lie
 cuts(x, params)        the literal cut loop -> (ends, kinds), ends exclusive and relative to the file
 chunk_files(...)       the arrays and counts sdcas_chunk_messages returns for a list of files
 sharing(...)           the sharing pass with dicts
@@ -37,6 +38,30 @@ def window_hash(x):
     for k in range(min(32, x.size)):
         h[k:] += g[:x.size - k] << np.uint64(k)
     return (h & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+
+def window_with_hash(target, rng, last=None):
+    """32 bytes w whose window hash is `target` wherever they lie in a file
+    (window_hash(x)[p] == target for w's last byte at p >= 31). The byte with
+    shift k, w[31 - k], decides bit k of the sum once the bytes with lower
+    shifts are chosen, so the bytes are drawn for k = 0..31 in turn, each among
+    the values whose table entry has the parity that bit needs. last: the value
+    w[31] must take (its entry's parity must be target's bit 0)"""
+    target = int(target) & 0xFFFFFFFF
+    odd = [np.flatnonzero((_G & 1) == v) for v in (0, 1)]
+    w = np.zeros(32, np.uint8)
+    total = 0
+    for k in range(32):
+        need = ((target >> k) ^ (total >> k)) & 1
+        if k == 0 and last is not None:
+            b = int(last)
+            assert int(_G[b]) & 1 == need, "the given last byte cannot give this hash"
+        else:
+            b = int(rng.choice(odd[need]))
+        w[31 - k] = b
+        total = (total + (int(_G[b]) << k)) & 0xFFFFFFFF
+    assert total == target
+    return w
 
 
 def params_valid(params):
@@ -86,17 +111,18 @@ def chunk_plan(lens, params=DEFAULT_PARAMS):
     return max_chunks, sum((int(n) + 1023) // 1024 for n in lens) + max_chunks
 
 
-def chunk_files(files, offsets, params=DEFAULT_PARAMS):
+def chunk_files(files, offsets, params=DEFAULT_PARAMS, known=None):
     """files: list of uint8 arrays; offsets: where each starts in the blob ->
     dict of file_chunks uint64[n + 1], chunk_off uint64[m] (blob offsets),
     chunk_len uint64[m], chunk_file uint32[m], kinds uint8[m] and counts (files,
-    chunks, total_bytes, hash_cuts, max_cuts, end_chunks)"""
+    chunks, total_bytes, hash_cuts, max_cuts, end_chunks). known: cuts(file,
+    params) of every file, where the caller has them already"""
     fc = [0]
     off, ln, fl, kd = [], [], [], []
     for i, (x, o) in enumerate(zip(files, offsets)):
         x = np.asarray(x, np.uint8)
         if x.size:
-            ends, kinds = cuts(x, params)
+            ends, kinds = known[i] if known is not None else cuts(x, params)
             starts = np.concatenate([[0], ends[:-1]])
             off += [int(o) + int(s) for s in starts]
             ln += [int(e - s) for s, e in zip(starts, ends)]

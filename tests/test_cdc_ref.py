@@ -2,6 +2,7 @@
 pinned with the definition: table entries, window hashes, cut
 lists, the chunk bound and the sharing pass on a hand-made case. No GPU."""
 import numpy as np
+import pytest
 
 from tests import _cdc_ref as R
 from tests._oracle import content, content_key
@@ -31,6 +32,30 @@ def test_window_hash_pinned_and_recurrence():
     y[:100] ^= 0x5A
     assert (R.window_hash(y)[131:] == h[131:]).all()
     assert R.window_hash(np.zeros(0, np.uint8)).size == 0
+
+
+def test_window_with_hash_gives_the_hash_anywhere():
+    rng = np.random.default_rng(32)
+    targets = [0, 127, 128, 511, 512, 1 << 25, (1 << 27) - 1, (1 << 32) - 1]
+    targets += [int(t) for t in rng.integers(0, 1 << 32, 200, dtype=np.uint64)]
+    seen = set()
+    for t in targets:
+        w = R.window_with_hash(t, rng)
+        assert w.dtype == np.uint8 and w.size == 32
+        seen.add(w.tobytes())
+        assert int(R.window_hash(w)[31]) == t  # at the start of a file
+        for lead in (1, 31, 32, 77):  # and after any bytes
+            x = np.concatenate([rng.integers(0, 256, lead, dtype=np.uint8), w, rng.integers(0, 256, 5, dtype=np.uint8)])
+            assert int(R.window_hash(x)[lead + 31]) == t, (t, lead)
+    assert len(seen) == len(targets)  # the free choices are drawn, not fixed
+    # the last byte given: the same hash, or refused where its parity cannot give it
+    g = R.gear_table()
+    for b in (0, 138, 255):
+        t = 0x12345678 ^ (int(g[b]) & 1)
+        w = R.window_with_hash(t, rng, last=b)
+        assert w[31] == b and int(R.window_hash(w)[31]) == t
+        with pytest.raises(AssertionError):
+            R.window_with_hash(t ^ 1, rng, last=b)
 
 
 def test_cuts_pattern251_pinned():
