@@ -23,64 +23,44 @@
 //                  lower bound; that rank also places every later copy and
 //                  every hit, so pos and flags are written here, and the
 //                  counts
-//   k_ch_place_old an old entry goes to its index plus the number of new
-//                  lower bounds that are <= it (as k_ci_place_old)
-//   k_ch_dir       one lower bound in the new keys per directory slot
+//   index_place_old  an old entry goes to its index plus the number of new
+//                  lower bounds that are <= it: the chunk index's kernel
+//                  (chunk_index.hip: k_ix_place_old)
+//   index_build_dir  one lower bound in the new keys per directory slot
+//                  (k_ix_dir)
 // The remove, one thread per old entry:
 //   k_ch_rm_mark   membership of the entry's value in `removed` by halving;
 //                  the waves' keep masks and the kept per workgroup
 //   k_ch_scan      as above
 //   k_ch_rm_scatter a kept entry goes to the kept before its workgroup plus
 //                  its rank in it: the order is preserved
-//   k_ch_dir       the directory of what is left
+//   index_build_dir  the directory of what is left
 // Every directory value is clamped to n, every computed place is checked
-// against the arrays' bound before a store.
+// against the arrays' bound before a store. The digest, the searches and the
+// bucket are index_device.h's.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include "chunk_holders.h"
+#include "index_device.h"
 
 namespace sdcas {
 
 namespace {
 
 constexpr uint32_t kChTB = kHoldersTB;
+static_assert(kHoldersTB == kIndexTB, "a scan tile is one workgroup's items");
 constexpr uint32_t kChHitBit = 0x80000000u, kChNewBit = 0x40000000u, kChLbMask = 0x3FFFFFFFu;
 constexpr uint8_t kChHit = 1, kChAdded = 2, kChSkipped = 4;  // SDCAS_INDEX_*
 
-struct ChDigest {
-  uint4 a, b;
-};
-__device__ __forceinline__ ChDigest ch_digest(const uint8_t* __restrict__ digests, uint32_t i) {
-  const uint4* p = reinterpret_cast<const uint4*>(digests) + 2 * (size_t)i;
-  return ChDigest{p[0], p[1]};
-}
-__device__ __forceinline__ void ch_store(uint8_t* __restrict__ digests, uint32_t i, const ChDigest& d) {
-  uint4* p = reinterpret_cast<uint4*>(digests) + 2 * (size_t)i;
-  p[0] = d.a;
-  p[1] = d.b;
-}
-// memcmp of the 32 bytes: < 0, 0, > 0 (little-endian word loads, byte-swapped to compare)
-__device__ __forceinline__ int ch_cmp(const ChDigest& x, const ChDigest& y) {
-  const uint32_t xs[8] = {x.a.x, x.a.y, x.a.z, x.a.w, x.b.x, x.b.y, x.b.z, x.b.w};
-  const uint32_t ys[8] = {y.a.x, y.a.y, y.a.z, y.a.w, y.b.x, y.b.y, y.b.z, y.b.w};
-#pragma unroll
-  for (uint32_t w = 0; w < 8; ++w) {
-    if (xs[w] != ys[w]) return __builtin_bswap32(xs[w]) < __builtin_bswap32(ys[w]) ? -1 : 1;
-  }
-  return 0;
-}
-
-__device__ __forceinline__ uint32_t ch_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
-
 struct ChTriple {
   uint64_t key;
-  ChDigest dig;
+  IxDigest dig;
   uint64_t val;
 };
 __device__ __forceinline__ ChTriple ch_triple(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ digests,
                                               const uint64_t* __restrict__ values, uint32_t i) {
-  return ChTriple{keys[i], ch_digest(digests, i), values ? values[i] : 0ull};
+  return ChTriple{keys[i], ix_digest(digests, i), values ? values[i] : 0ull};
 }
 // entry i of (keys, digests, values) against t: < 0, 0, > 0. The digest is read
 // only where the keys are equal, the value only where the digests are.
@@ -88,24 +68,16 @@ __device__ __forceinline__ int ch_cmp3(const uint64_t* __restrict__ keys, const 
                                        const uint64_t* __restrict__ values, uint32_t i, const ChTriple& t) {
   const uint64_t k = keys[i];
   if (k != t.key) return k < t.key ? -1 : 1;
-  const int c = ch_cmp(ch_digest(digests, i), t.dig);
+  const int c = ix_cmp(ix_digest(digests, i), t.dig);
   if (c) return c;
   const uint64_t v = values ? values[i] : 0ull;
   return v == t.val ? 0 : (v < t.val ? -1 : 1);
 }
 
-// the bucket of `key`: [lo, hi), both clamped to n
-__device__ __forceinline__ void ch_bucket(const IndexView& ix, uint64_t key, uint32_t& lo, uint32_t& hi) {
-  const uint32_t b = ix.bits ? (uint32_t)(key >> (64 - ix.bits)) : 0u;
-  lo = ch_min(ix.dir[b], ix.n);
-  hi = ch_min(ix.dir[b + 1], ix.n);
-  if (hi < lo) hi = lo;
-}
-
 // the first entry of [lo, hi) whose pair is not below (key, dig) — or, with
 // `after`, the first whose pair is above it
 __device__ __forceinline__ uint32_t ch_pair_bound(const IndexView& ix, uint32_t lo, uint32_t hi, uint64_t key,
-                                                  const ChDigest& dig, bool after) {
+                                                  const IxDigest& dig, bool after) {
   while (lo < hi) {
     const uint32_t mid = lo + ((hi - lo) >> 1);
     const uint64_t k = ix.keys[mid];
@@ -113,7 +85,7 @@ __device__ __forceinline__ uint32_t ch_pair_bound(const IndexView& ix, uint32_t 
     if (k != key) {
       below = k < key;
     } else {
-      const int c = ch_cmp(ch_digest(ix.digests, mid), dig);
+      const int c = ix_cmp(ix_digest(ix.digests, mid), dig);
       below = after ? c <= 0 : c < 0;
     }
     if (below) lo = mid + 1;
@@ -127,7 +99,7 @@ __device__ __forceinline__ uint32_t ch_lower_bound3(const IndexView& ix, const C
   found = false;
   if (!ix.n) return 0;
   uint32_t lo, hi;
-  ch_bucket(ix, t.key, lo, hi);
+  ix_bucket(ix, t.key, lo, hi);
   while (lo < hi) {
     const uint32_t mid = lo + ((hi - lo) >> 1);
     const int c = ch_cmp3(ix.keys, ix.digests, ix.values, mid, t);
@@ -136,16 +108,6 @@ __device__ __forceinline__ uint32_t ch_lower_bound3(const IndexView& ix, const C
       return mid;
     }
     if (c < 0) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// the number of a[0 .. len) that are <= v, looked for in [lo, hi] (a ascending)
-__device__ __forceinline__ uint32_t ch_upper(const uint32_t* __restrict__ a, uint32_t lo, uint32_t hi, uint32_t v) {
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= v) lo = mid + 1;
     else hi = mid;
   }
   return lo;
@@ -217,9 +179,9 @@ __global__ void __launch_bounds__(kChTB) k_ch_match(IndexView ix, const uint64_t
     uint32_t first = 0, end = 0;
     if (take && ix.n) {
       const uint64_t key = keys[c];
-      const ChDigest dig = ch_digest(digests, c);
+      const IxDigest dig = ix_digest(digests, c);
       uint32_t lo, hi;
-      ch_bucket(ix, key, lo, hi);
+      ix_bucket(ix, key, lo, hi);
       first = ch_pair_bound(ix, lo, hi, key, dig, false);
       // the run's end lies in the same bucket: its entries share the key
       end = ch_pair_bound(ix, first, hi, key, dig, true);
@@ -261,7 +223,7 @@ __global__ void __launch_bounds__(kChTB) k_ch_merge(const uint32_t* __restrict__
   const uint32_t c = in[p];
   if (c >= m) return;  // never: `in` holds batch positions
   const uint32_t first = p / (2 * w) * (2 * w);  // w <= 2^29: 2 w fits
-  const uint32_t mid = ch_min(first + w, m), end = ch_min(first + 2 * w, m);
+  const uint32_t mid = ix_min(first + w, m), end = ix_min(first + 2 * w, m);
   const bool left = p < mid;
   uint32_t lo = left ? mid : first, hi = left ? end : mid;
   const uint32_t sib = lo;
@@ -362,7 +324,7 @@ __global__ void __launch_bounds__(kChTB) k_ch_place(const uint32_t* __restrict__
             if (rank < m) lbs[rank] = lb;
             if (at < (int64_t)cap) {  // always with an index that is one: lb <= n_old, rank < m
               out.keys[at] = keys[c];
-              ch_store(out.digests, (uint32_t)at, ch_digest(digests, c));
+              ix_store(out.digests, (uint32_t)at, ix_digest(digests, c));
               out.values[at] = values ? values[c] : 0ull;
             }
           }
@@ -379,62 +341,6 @@ __global__ void __launch_bounds__(kChTB) k_ch_place(const uint32_t* __restrict__
   }
   __syncthreads();
   if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
-}
-
-__global__ void __launch_bounds__(kChTB) k_ch_place_old(IndexView old, const uint32_t* __restrict__ lbs,
-                                                        const uint32_t* __restrict__ na_p, uint32_t m, IndexOut out,
-                                                        uint32_t cap) {
-  __shared__ uint32_t s_span[2];
-  const uint32_t na = ch_min(*na_p, m);
-  const uint32_t first = blockIdx.x * kChTB;
-  if (threadIdx.x < 2) {
-    const uint32_t v = threadIdx.x == 0 ? first : ch_min(first + kChTB - 1, old.n - 1);
-    s_span[threadIdx.x] = ch_upper(lbs, 0, na, v);
-  }
-  __syncthreads();
-  const uint32_t i = first + threadIdx.x;
-  if (i >= old.n) return;
-  const uint32_t at = i + ch_upper(lbs, s_span[0], s_span[1], i);
-  if (at >= cap) return;  // never: at most na <= m added triples stand before an old entry
-  out.keys[at] = old.keys[i];
-  ch_store(out.digests, at, ch_digest(old.digests, i));
-  out.values[at] = old.values ? old.values[i] : 0ull;
-}
-
-// entries_old, entries_new
-__global__ void k_ch_add_totals(const uint32_t* __restrict__ na_p, uint32_t m, uint32_t n_old,
-                                unsigned long long* __restrict__ counts) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    counts[4] = n_old;
-    counts[5] = (unsigned long long)n_old + ch_min(*na_p, m);
-  }
-}
-
-// dir[j] <- the number of the n = base + min(*extra_p, extra_max) entries
-// whose key's top `bits` bits are below j
-__global__ void __launch_bounds__(kChTB) k_ch_dir(const uint64_t* __restrict__ nkeys, uint32_t base,
-                                                  const uint32_t* __restrict__ extra_p, uint32_t extra_max,
-                                                  uint32_t bits, uint32_t* __restrict__ dir) {
-  const uint64_t j = (uint64_t)blockIdx.x * kChTB + threadIdx.x;
-  const uint64_t slots = 1ull << bits;
-  if (j > slots) return;
-  const uint32_t n = base + ch_min(*extra_p, extra_max);
-  if (j == slots) {
-    dir[j] = n;
-    return;
-  }
-  if (j == 0) {
-    dir[0] = 0;
-    return;
-  }
-  const uint64_t thr = j << (64 - bits);  // bits >= 1 here: 0 < j < 2^bits
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (nkeys[mid] < thr) lo = mid + 1;
-    else hi = mid;
-  }
-  dir[j] = lo;
 }
 
 // masks[4 b + wave]: the lanes whose entry stays; l1[b]: how many of workgroup b's do
@@ -477,7 +383,7 @@ __global__ void __launch_bounds__(kChTB) k_ch_rm_scatter(IndexView old, const un
   const uint32_t at = ch_base(l1, l2, l3, blockIdx.x) + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
   if (at >= cap) return;  // never: a rank among at most n_old kept entries
   out.keys[at] = old.keys[i];
-  ch_store(out.digests, at, ch_digest(old.digests, i));
+  ix_store(out.digests, at, ix_digest(old.digests, i));
   out.values[at] = old.values ? old.values[i] : 0ull;
 }
 
@@ -485,7 +391,7 @@ __global__ void __launch_bounds__(kChTB) k_ch_rm_scatter(IndexView old, const un
 __global__ void k_ch_rm_totals(const uint32_t* __restrict__ kept_p, uint32_t n_old, uint32_t r,
                                unsigned long long* __restrict__ counts) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    const uint32_t kept = ch_min(*kept_p, n_old);
+    const uint32_t kept = ix_min(*kept_p, n_old);
     counts[0] = n_old;
     counts[1] = n_old - kept;
     counts[2] = kept;
@@ -493,19 +399,12 @@ __global__ void k_ch_rm_totals(const uint32_t* __restrict__ kept_p, uint32_t n_o
   }
 }
 
-inline uint32_t ch_blocks(uint64_t items) { return (uint32_t)((items + kChTB - 1) / kChTB); }
-
-template <typename T>
-inline T* at(uint8_t* ws, uint64_t off) {
-  return reinterpret_cast<T*>(ws + off);
-}
-
 // the per-workgroup counts in l1 scanned; the sum of all in tot[0]
 inline void ch_scan(uint8_t* ws, const HoldersScanLayout& s, hipStream_t st) {
-  uint32_t* l1 = at<uint32_t>(ws, s.l1);
-  uint32_t* l2 = at<uint32_t>(ws, s.l2);
-  uint32_t* l3 = at<uint32_t>(ws, s.l3);
-  uint32_t* tot = at<uint32_t>(ws, s.tot);
+  uint32_t* l1 = index_at<uint32_t>(ws, s.l1);
+  uint32_t* l2 = index_at<uint32_t>(ws, s.l2);
+  uint32_t* l3 = index_at<uint32_t>(ws, s.l3);
+  uint32_t* tot = index_at<uint32_t>(ws, s.tot);
   hipLaunchKernelGGL(k_ch_scan, dim3(s.n2), dim3(kChTB), 0, st, l1, s.n1, l2);
   hipLaunchKernelGGL(k_ch_scan, dim3(s.n3), dim3(kChTB), 0, st, l2, s.n2, l3);
   hipLaunchKernelGGL(k_ch_scan, dim3(1), dim3(kChTB), 0, st, l3, s.n3, tot);  // n3 <= 64
@@ -526,20 +425,7 @@ int holders_check(const uint64_t* keys, const uint8_t* digests, const uint64_t* 
       return 1;
     }
   }
-  const uint64_t slots = 1ull << bits;
-  uint64_t i = 0;  // the entries whose bucket is below j
-  for (uint64_t j = 0; j <= slots; ++j) {
-    if (j == slots) {
-      i = n;
-    } else if (bits) {
-      while (i < n && (keys[i] >> (64 - bits)) < j) ++i;
-    }
-    if (dir[j] != i) {
-      *bad = j;
-      return 2;
-    }
-  }
-  return 0;
+  return index_dir_check(keys, dir, n, bits, bad);
 }
 
 hipError_t holders_match(const IndexView& idx, const uint64_t* keys, const uint8_t* digests, const uint8_t* valid,
@@ -548,7 +434,7 @@ hipError_t holders_match(const IndexView& idx, const uint64_t* keys, const uint8
   hipError_t e;
   if (counts && (e = hipMemsetAsync(counts, 0, kIndexMatchCounts * sizeof(unsigned long long), st))) return e;
   if (!pos && !value && !holders && !counts) return hipSuccess;
-  hipLaunchKernelGGL(k_ch_match, dim3(ch_blocks(m)), dim3(kChTB), 0, st, idx, keys, digests, valid, m, pos, value,
+  hipLaunchKernelGGL(k_ch_match, dim3(index_blocks(m)), dim3(kChTB), 0, st, idx, keys, digests, valid, m, pos, value,
                      holders, counts);
   return hipGetLastError();
 }
@@ -557,17 +443,17 @@ hipError_t holders_add(uint8_t* ws, const IndexView& old, const uint64_t* keys, 
                        const uint64_t* values, const uint8_t* valid, uint32_t m, const IndexOut& out, int64_t* pos,
                        uint8_t* flags, unsigned long long* counts, hipStream_t st) {
   const HoldersAddLayout l = holders_add_layout(m);
-  uint32_t* src = at<uint32_t>(ws, l.ord_a);
-  uint32_t* dst = at<uint32_t>(ws, l.ord_b);
-  uint32_t* lbf = at<uint32_t>(ws, l.lbf);
-  uint32_t* lbs = at<uint32_t>(ws, l.lbs);
-  uint32_t* l1 = at<uint32_t>(ws, l.scan.l1);
-  uint32_t* l2 = at<uint32_t>(ws, l.scan.l2);
-  uint32_t* l3 = at<uint32_t>(ws, l.scan.l3);
-  uint32_t* na = at<uint32_t>(ws, l.scan.tot);
-  unsigned long long* cts = at<unsigned long long>(ws, l.counts);
+  uint32_t* src = index_at<uint32_t>(ws, l.ord_a);
+  uint32_t* dst = index_at<uint32_t>(ws, l.ord_b);
+  uint32_t* lbf = index_at<uint32_t>(ws, l.lbf);
+  uint32_t* lbs = index_at<uint32_t>(ws, l.lbs);
+  uint32_t* l1 = index_at<uint32_t>(ws, l.scan.l1);
+  uint32_t* l2 = index_at<uint32_t>(ws, l.scan.l2);
+  uint32_t* l3 = index_at<uint32_t>(ws, l.scan.l3);
+  uint32_t* na = index_at<uint32_t>(ws, l.scan.tot);
+  unsigned long long* cts = index_at<unsigned long long>(ws, l.counts);
   const uint32_t cap = old.n + m;
-  const dim3 block(kChTB), grid(ch_blocks(m));
+  const dim3 block(kChTB), grid(index_blocks(m));
   hipError_t e;
   if ((e = hipMemsetAsync(na, 0, l.bytes - l.scan.tot, st))) return e;  // tot and counts
   if (m) {
@@ -587,14 +473,11 @@ hipError_t holders_add(uint8_t* ws, const IndexView& old, const uint64_t* keys, 
                        out, cap, lbs, pos, flags, cts);
     if ((e = hipGetLastError())) return e;
   }
-  if (old.n)
-    hipLaunchKernelGGL(k_ch_place_old, dim3(ch_blocks(old.n)), block, 0, st, old, (const uint32_t*)lbs,
-                       (const uint32_t*)na, m, out, cap);
-  hipLaunchKernelGGL(k_ch_dir, dim3(ch_blocks(index_dir_slots(out.bits))), block, 0, st, (const uint64_t*)out.keys,
-                     old.n, (const uint32_t*)na, m, out.bits, out.dir);
+  if (old.n) index_place_old(old, lbs, na, m, out, cap, st);
+  index_build_dir(out.keys, old.n, na, m, out.bits, out.dir, st);
   if ((e = hipGetLastError())) return e;
   if (counts) {
-    hipLaunchKernelGGL(k_ch_add_totals, dim3(1), dim3(64), 0, st, (const uint32_t*)na, m, old.n, cts);
+    index_add_totals(na, m, old.n, cts, st);
     if ((e = hipGetLastError())) return e;
     return hipMemcpyAsync(counts, cts, kIndexAddCounts * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
   }
@@ -604,13 +487,13 @@ hipError_t holders_add(uint8_t* ws, const IndexView& old, const uint64_t* keys, 
 hipError_t holders_remove(uint8_t* ws, const IndexView& old, const uint64_t* removed, uint32_t r, const IndexOut& out,
                           unsigned long long* counts, hipStream_t st) {
   const HoldersRemoveLayout l = holders_remove_layout(old.n);
-  unsigned long long* masks = at<unsigned long long>(ws, l.masks);
-  uint32_t* l1 = at<uint32_t>(ws, l.scan.l1);
-  uint32_t* l2 = at<uint32_t>(ws, l.scan.l2);
-  uint32_t* l3 = at<uint32_t>(ws, l.scan.l3);
-  uint32_t* kept = at<uint32_t>(ws, l.scan.tot);
-  unsigned long long* cts = at<unsigned long long>(ws, l.counts);
-  const dim3 block(kChTB), grid(ch_blocks(old.n));
+  unsigned long long* masks = index_at<unsigned long long>(ws, l.masks);
+  uint32_t* l1 = index_at<uint32_t>(ws, l.scan.l1);
+  uint32_t* l2 = index_at<uint32_t>(ws, l.scan.l2);
+  uint32_t* l3 = index_at<uint32_t>(ws, l.scan.l3);
+  uint32_t* kept = index_at<uint32_t>(ws, l.scan.tot);
+  unsigned long long* cts = index_at<unsigned long long>(ws, l.counts);
+  const dim3 block(kChTB), grid(index_blocks(old.n));
   hipError_t e;
   if ((e = hipMemsetAsync(kept, 0, l.bytes - l.scan.tot, st))) return e;  // tot and counts
   if (old.n) {
@@ -620,8 +503,7 @@ hipError_t holders_remove(uint8_t* ws, const IndexView& old, const uint64_t* rem
                        (const uint32_t*)l1, (const uint32_t*)l2, (const uint32_t*)l3, out, old.n);
     if ((e = hipGetLastError())) return e;
   }
-  hipLaunchKernelGGL(k_ch_dir, dim3(ch_blocks(index_dir_slots(out.bits))), block, 0, st, (const uint64_t*)out.keys, 0u,
-                     (const uint32_t*)kept, old.n, out.bits, out.dir);
+  index_build_dir(out.keys, 0u, kept, old.n, out.bits, out.dir, st);
   if ((e = hipGetLastError())) return e;
   if (counts) {
     hipLaunchKernelGGL(k_ch_rm_totals, dim3(1), dim3(64), 0, st, (const uint32_t*)kept, old.n, r, cts);

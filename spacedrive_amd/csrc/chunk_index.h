@@ -44,10 +44,34 @@ inline uint32_t index_dir_bits(uint64_t n) {
 }
 inline uint64_t index_dir_slots(uint32_t bits) { return (1ull << bits) + 1; }
 
+// every kernel of the two indexes: workgroups of 256, one item per thread
+constexpr uint32_t kIndexTB = 256;
+inline uint32_t index_blocks(uint64_t items) { return (uint32_t)((items + kIndexTB - 1) / kIndexTB); }
+// the part of a workspace that starts `off` bytes in
+template <typename T>
+inline T* index_at(uint8_t* ws, uint64_t off) {
+  return reinterpret_cast<T*>(ws + off);
+}
+
 // 0: an index; 1: entry *bad does not order after the one before; 2: directory
 // slot *bad does not hold its count. Host arrays.
 int index_check(const uint64_t* keys, const uint8_t* digests, const uint32_t* dir, uint64_t n, uint32_t bits,
                 uint64_t* bad);
+// the directory half of a check: 0, or 2 with the first slot that is wrong in *bad
+int index_dir_check(const uint64_t* keys, const uint32_t* dir, uint64_t n, uint32_t bits, uint64_t* bad);
+
+// The three steps both indexes' adds (and the holders' remove) end with, each
+// one kernel enqueued on st; the caller reads hipGetLastError.
+// An old entry goes to its index plus the number of lbs[0 .. min(*na_p, m))
+// (the added entries' lower bounds, ascending) that are <= it.
+void index_place_old(const IndexView& old, const uint32_t* lbs, const uint32_t* na_p, uint32_t m, const IndexOut& out,
+                     uint32_t cap, hipStream_t st);
+// dir[j] <- the number of the n = base + min(*extra_p, extra_max) entries of
+// nkeys whose key's top `bits` bits are below j
+void index_build_dir(const uint64_t* nkeys, uint32_t base, const uint32_t* extra_p, uint32_t extra_max, uint32_t bits,
+                     uint32_t* dir, hipStream_t st);
+// cts[4], cts[5] <- entries_old, entries_new
+void index_add_totals(const uint32_t* na_p, uint32_t m, uint32_t n_old, unsigned long long* cts, hipStream_t st);
 
 // The add's workspace for a batch of m, in bytes from its start (every part
 // 16-byte aligned):

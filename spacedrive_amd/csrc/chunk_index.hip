@@ -25,55 +25,37 @@
 //                  always and works on 0 items otherwise
 //   k_ci_place_new an added pair goes to its rank plus its lower bound in the
 //                  old index; the lower bounds, now ascending, are kept
-//   k_ci_place_old an old entry goes to its index plus the number of kept
+//   k_ix_place_old an old entry goes to its index plus the number of kept
 //                  lower bounds that are <= it: a search in a contiguous u32
 //                  array, narrowed per workgroup to what its 256 entries span
 //   k_ci_add_out   pos and flags per batch position, the counts
-//   k_ci_dir       one lower bound in the new keys per directory slot
+//   k_ix_dir       one lower bound in the new keys per directory slot
 // Every directory value is clamped to n, every computed place is checked
 // against the arrays' bound before a store.
+// k_ix_place_old, k_ix_dir and k_ix_add_totals are the holders index's too
+// (chunk_holders.hip): it reaches them through index_place_old,
+// index_build_dir and index_add_totals, since a kernel cannot be launched
+// from another file without relocatable device code. The digest, the searches
+// and the bucket are index_device.h's.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include "chunk_index.h"
+#include "index_device.h"
 
 namespace sdcas {
 
 namespace {
 
-constexpr uint32_t kCiTB = 256;
+constexpr uint32_t kCiTB = kIndexTB;
 constexpr uint32_t kCiHitBit = 0x80000000u;
 constexpr uint32_t kCiRunCap = 64;
 constexpr uint8_t kCiHit = 1, kCiAdded = 2, kCiSkipped = 4;  // SDCAS_INDEX_*
 
-struct CiDigest {
-  uint4 a, b;
-};
-__device__ __forceinline__ CiDigest ci_digest(const uint8_t* __restrict__ digests, uint32_t i) {
-  const uint4* p = reinterpret_cast<const uint4*>(digests) + 2 * (size_t)i;
-  return CiDigest{p[0], p[1]};
-}
-__device__ __forceinline__ void ci_store(uint8_t* __restrict__ digests, uint32_t i, const CiDigest& d) {
-  uint4* p = reinterpret_cast<uint4*>(digests) + 2 * (size_t)i;
-  p[0] = d.a;
-  p[1] = d.b;
-}
-// memcmp of the 32 bytes: < 0, 0, > 0. The words are little-endian loads, so
-// each is byte-swapped before it is compared.
-__device__ __forceinline__ int ci_cmp(const CiDigest& x, const CiDigest& y) {
-  const uint32_t xs[8] = {x.a.x, x.a.y, x.a.z, x.a.w, x.b.x, x.b.y, x.b.z, x.b.w};
-  const uint32_t ys[8] = {y.a.x, y.a.y, y.a.z, y.a.w, y.b.x, y.b.y, y.b.z, y.b.w};
-#pragma unroll
-  for (uint32_t w = 0; w < 8; ++w) {
-    if (xs[w] != ys[w]) return __builtin_bswap32(xs[w]) < __builtin_bswap32(ys[w]) ? -1 : 1;
-  }
-  return 0;
-}
-
 // the first entry of [lo, hi) that is not below (key, dig); found: it is equal
 __device__ __forceinline__ uint32_t ci_lower_bound(const uint64_t* __restrict__ keys,
                                                    const uint8_t* __restrict__ digests, uint32_t lo, uint32_t hi,
-                                                   uint64_t key, const CiDigest& dig, bool& found) {
+                                                   uint64_t key, const IxDigest& dig, bool& found) {
   found = false;
   while (lo < hi) {
     const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -82,7 +64,7 @@ __device__ __forceinline__ uint32_t ci_lower_bound(const uint64_t* __restrict__ 
     if (k != key) {
       below = k < key;
     } else {
-      const int c = ci_cmp(ci_digest(digests, mid), dig);
+      const int c = ix_cmp(ix_digest(digests, mid), dig);
       if (c == 0) {
         found = true;
         return mid;
@@ -94,18 +76,6 @@ __device__ __forceinline__ uint32_t ci_lower_bound(const uint64_t* __restrict__ 
   }
   return lo;
 }
-
-// the number of a[0 .. len) that are <= v, looked for in [lo, hi] (a ascending)
-__device__ __forceinline__ uint32_t ci_upper(const uint32_t* __restrict__ a, uint32_t lo, uint32_t hi, uint32_t v) {
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ uint32_t ci_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
 // pos / value / counts: the match's outputs; mlb: the add's (the lower bound,
 // with kCiHitBit when the pair is there; 0 for a skipped query)
@@ -126,11 +96,9 @@ __global__ void __launch_bounds__(kCiTB) k_ci_match(IndexView ix, const uint64_t
     uint32_t at = 0;
     if (take && ix.n) {
       const uint64_t key = keys[c];
-      const CiDigest dig = ci_digest(digests, c);
-      const uint32_t b = ix.bits ? (uint32_t)(key >> (64 - ix.bits)) : 0u;
-      const uint32_t lo = ci_min(ix.dir[b], ix.n);
-      uint32_t hi = ci_min(ix.dir[b + 1], ix.n);
-      if (hi < lo) hi = lo;
+      const IxDigest dig = ix_digest(digests, c);
+      uint32_t lo, hi;
+      ix_bucket(ix, key, lo, hi);
       at = ci_lower_bound(ix.keys, ix.digests, lo, hi, key, dig, found);
     }
     if (pos) pos[c] = found ? (int64_t)at : -1;
@@ -183,7 +151,7 @@ __global__ void __launch_bounds__(kCiTB) k_ci_fix(const uint32_t* __restrict__ v
                                                   const uint8_t* __restrict__ digests, uint32_t m,
                                                   const uint32_t* __restrict__ na_p, uint32_t* __restrict__ ord,
                                                   uint32_t* __restrict__ long_run) {
-  const uint32_t na = ci_min(*na_p, m);
+  const uint32_t na = ix_min(*na_p, m);
   const uint32_t p = blockIdx.x * kCiTB + threadIdx.x;
   if (p >= na) return;
   const uint32_t c = vals[p];
@@ -208,10 +176,10 @@ __global__ void __launch_bounds__(kCiTB) k_ci_fix(const uint32_t* __restrict__ v
   }
   uint32_t below = 0;
   if (hi != lo) {
-    const CiDigest dig = ci_digest(digests, c);
+    const IxDigest dig = ix_digest(digests, c);
     for (uint32_t q = lo; q <= hi; ++q) {
       const uint32_t e = vals[q];
-      if (q != p && e < m) below += ci_cmp(ci_digest(digests, e), dig) < 0;
+      if (q != p && e < m) below += ix_cmp(ix_digest(digests, e), dig) < 0;
     }
   }
   ord[lo + below] = c;  // lo + below <= hi < na <= m
@@ -221,7 +189,7 @@ __global__ void __launch_bounds__(kCiTB) k_ci_fix(const uint32_t* __restrict__ v
 // order, else 0: the number of items the long path's passes work on
 __global__ void k_ci_gate(const uint32_t* __restrict__ long_run, const uint32_t* __restrict__ na_p, uint32_t m,
                           uint32_t* __restrict__ gate) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *gate = *long_run ? ci_min(*na_p, m) : 0u;
+  if (threadIdx.x == 0 && blockIdx.x == 0) *gate = *long_run ? ix_min(*na_p, m) : 0u;
 }
 
 // The long path: one pass of a merge sort by (key, digest) over the first
@@ -235,25 +203,25 @@ __global__ void __launch_bounds__(kCiTB) k_ci_merge(const uint32_t* __restrict__
                                                     const uint64_t* __restrict__ keys,
                                                     const uint8_t* __restrict__ digests, uint32_t w, uint32_t m,
                                                     const uint32_t* __restrict__ gate) {
-  const uint32_t n = ci_min(*gate, m);
+  const uint32_t n = ix_min(*gate, m);
   const uint32_t p = blockIdx.x * kCiTB + threadIdx.x;
   if (p >= n) return;
   const uint32_t c = in[p];
   if (c >= m) return;  // never: `in` holds batch positions
   const uint32_t first = p / (2 * w) * (2 * w);  // w <= 2^29: 2 w fits
-  const uint32_t mid = ci_min(first + w, n), end = ci_min(first + 2 * w, n);
+  const uint32_t mid = ix_min(first + w, n), end = ix_min(first + 2 * w, n);
   const bool left = p < mid;
   uint32_t lo = left ? mid : first, hi = left ? end : mid;
   const uint32_t sib = lo;
   const uint64_t key = keys[c];
-  const CiDigest dig = ci_digest(digests, c);
+  const IxDigest dig = ix_digest(digests, c);
   while (lo < hi) {  // the sibling run's pairs below (key, dig)
     const uint32_t q = lo + ((hi - lo) >> 1);
     const uint32_t e = in[q];
     bool below = false;
     if (e < m) {  // always
       const uint64_t k = keys[e];
-      below = k != key ? k < key : ci_cmp(ci_digest(digests, e), dig) < 0;
+      below = k != key ? k < key : ix_cmp(ix_digest(digests, e), dig) < 0;
     }
     if (below) lo = q + 1;
     else hi = q;
@@ -267,7 +235,7 @@ __global__ void __launch_bounds__(kCiTB) k_ci_take(const uint32_t* __restrict__ 
                                                    const uint32_t* __restrict__ sorted, uint32_t m,
                                                    uint32_t* __restrict__ ord) {
   const uint32_t p = blockIdx.x * kCiTB + threadIdx.x;
-  if (p < ci_min(*gate, m)) ord[p] = sorted[p];
+  if (p < ix_min(*gate, m)) ord[p] = sorted[p];
 }
 
 __global__ void __launch_bounds__(kCiTB) k_ci_place_new(const uint32_t* __restrict__ ord,
@@ -279,7 +247,7 @@ __global__ void __launch_bounds__(kCiTB) k_ci_place_new(const uint32_t* __restri
                                                         uint32_t cap, uint32_t* __restrict__ npos,
                                                         uint32_t* __restrict__ lbs) {
   const uint32_t p = blockIdx.x * kCiTB + threadIdx.x;
-  if (p >= ci_min(*na_p, m)) return;
+  if (p >= ix_min(*na_p, m)) return;
   const uint32_t c = ord[p];
   if (c >= m) return;  // never
   const uint32_t lb = mlb[c] & ~kCiHitBit;
@@ -288,27 +256,28 @@ __global__ void __launch_bounds__(kCiTB) k_ci_place_new(const uint32_t* __restri
   npos[c] = at;
   if (at >= cap) return;  // never with an index that is one: lb <= n_old, p < m
   out.keys[at] = keys[c];
-  ci_store(out.digests, at, ci_digest(digests, c));
+  ix_store(out.digests, at, ix_digest(digests, c));
   out.values[at] = values ? values[c] : 0ull;
 }
 
-__global__ void __launch_bounds__(kCiTB) k_ci_place_old(IndexView old, const uint32_t* __restrict__ lbs,
+// Shared with the holders index (chunk_index.h: index_place_old)
+__global__ void __launch_bounds__(kCiTB) k_ix_place_old(IndexView old, const uint32_t* __restrict__ lbs,
                                                         const uint32_t* __restrict__ na_p, uint32_t m, IndexOut out,
                                                         uint32_t cap) {
   __shared__ uint32_t s_span[2];
-  const uint32_t na = ci_min(*na_p, m);
+  const uint32_t na = ix_min(*na_p, m);
   const uint32_t first = blockIdx.x * kCiTB;
   if (threadIdx.x < 2) {
-    const uint32_t v = threadIdx.x == 0 ? first : ci_min(first + kCiTB - 1, old.n - 1);
-    s_span[threadIdx.x] = ci_upper(lbs, 0, na, v);
+    const uint32_t v = threadIdx.x == 0 ? first : ix_min(first + kCiTB - 1, old.n - 1);
+    s_span[threadIdx.x] = ix_upper(lbs, 0, na, v);
   }
   __syncthreads();
   const uint32_t i = first + threadIdx.x;
   if (i >= old.n) return;
-  const uint32_t at = i + ci_upper(lbs, s_span[0], s_span[1], i);
-  if (at >= cap) return;  // never: at most na <= m added pairs stand before an old entry
+  const uint32_t at = i + ix_upper(lbs, s_span[0], s_span[1], i);
+  if (at >= cap) return;  // never: at most na <= m added entries stand before an old entry
   out.keys[at] = old.keys[i];
-  ci_store(out.digests, at, ci_digest(old.digests, i));
+  ix_store(out.digests, at, ix_digest(old.digests, i));
   out.values[at] = old.values ? old.values[i] : 0ull;
 }
 
@@ -322,7 +291,7 @@ __global__ void __launch_bounds__(kCiTB) k_ci_add_out(const int64_t* __restrict_
   __shared__ uint32_t s_cnt[4];
   if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
   __syncthreads();
-  const uint32_t na = ci_min(*na_p, m);
+  const uint32_t na = ix_min(*na_p, m);
   const uint32_t c = blockIdx.x * kCiTB + threadIdx.x;
   bool add[4] = {false, false, false, false};  // queries, hits, added, batch_duplicates
   if (c < m) {
@@ -334,7 +303,7 @@ __global__ void __launch_bounds__(kCiTB) k_ci_add_out(const int64_t* __restrict_
       add[0] = true;
       if (w & kCiHitBit) {
         const uint32_t i = w & ~kCiHitBit;
-        at = (int64_t)i + ci_upper(lbs, 0, na, i);
+        at = (int64_t)i + ix_upper(lbs, 0, na, i);
         fl = kCiHit, add[1] = true;
       } else if (r == (int64_t)c) {
         at = npos[c];
@@ -356,23 +325,24 @@ __global__ void __launch_bounds__(kCiTB) k_ci_add_out(const int64_t* __restrict_
   if (threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
 }
 
-// entries_old, entries_new
-__global__ void k_ci_totals(const uint32_t* __restrict__ na_p, uint32_t m, uint32_t n_old,
-                            unsigned long long* __restrict__ counts) {
+// entries_old, entries_new (index_add_totals)
+__global__ void k_ix_add_totals(const uint32_t* __restrict__ na_p, uint32_t m, uint32_t n_old,
+                                unsigned long long* __restrict__ counts) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     counts[4] = n_old;
-    counts[5] = (unsigned long long)n_old + ci_min(*na_p, m);
+    counts[5] = (unsigned long long)n_old + ix_min(*na_p, m);
   }
 }
 
-// dir[j] <- the number of new entries whose key's top `bits` bits are below j
-__global__ void __launch_bounds__(kCiTB) k_ci_dir(const uint64_t* __restrict__ nkeys,
-                                                  const uint32_t* __restrict__ na_p, uint32_t m, uint32_t n_old,
+// dir[j] <- the number of the n = base + min(*extra_p, extra_max) entries
+// whose key's top `bits` bits are below j (index_build_dir)
+__global__ void __launch_bounds__(kCiTB) k_ix_dir(const uint64_t* __restrict__ nkeys, uint32_t base,
+                                                  const uint32_t* __restrict__ extra_p, uint32_t extra_max,
                                                   uint32_t bits, uint32_t* __restrict__ dir) {
   const uint64_t j = (uint64_t)blockIdx.x * kCiTB + threadIdx.x;
   const uint64_t slots = 1ull << bits;
   if (j > slots) return;
-  const uint32_t n = n_old + ci_min(*na_p, m);
+  const uint32_t n = base + ix_min(*extra_p, extra_max);
   if (j == slots) {
     dir[j] = n;
     return;
@@ -391,13 +361,6 @@ __global__ void __launch_bounds__(kCiTB) k_ci_dir(const uint64_t* __restrict__ n
   dir[j] = lo;
 }
 
-inline uint32_t ci_blocks(uint64_t items) { return (uint32_t)((items + kCiTB - 1) / kCiTB); }
-
-template <typename T>
-inline T* at(uint8_t* ws, uint64_t off) {
-  return reinterpret_cast<T*>(ws + off);
-}
-
 // memcmp order of two host pairs
 inline bool host_pair_less(uint64_t ka, const uint8_t* da, uint64_t kb, const uint8_t* db) {
   if (ka != kb) return ka < kb;
@@ -414,6 +377,10 @@ int index_check(const uint64_t* keys, const uint8_t* digests, const uint32_t* di
       return 1;
     }
   }
+  return index_dir_check(keys, dir, n, bits, bad);
+}
+
+int index_dir_check(const uint64_t* keys, const uint32_t* dir, uint64_t n, uint32_t bits, uint64_t* bad) {
   const uint64_t slots = 1ull << bits;
   uint64_t i = 0;  // the entries whose bucket is below j
   for (uint64_t j = 0; j <= slots; ++j) {
@@ -430,12 +397,27 @@ int index_check(const uint64_t* keys, const uint8_t* digests, const uint32_t* di
   return 0;
 }
 
+void index_place_old(const IndexView& old, const uint32_t* lbs, const uint32_t* na_p, uint32_t m, const IndexOut& out,
+                     uint32_t cap, hipStream_t st) {
+  hipLaunchKernelGGL(k_ix_place_old, dim3(index_blocks(old.n)), dim3(kCiTB), 0, st, old, lbs, na_p, m, out, cap);
+}
+
+void index_build_dir(const uint64_t* nkeys, uint32_t base, const uint32_t* extra_p, uint32_t extra_max, uint32_t bits,
+                     uint32_t* dir, hipStream_t st) {
+  hipLaunchKernelGGL(k_ix_dir, dim3(index_blocks(index_dir_slots(bits))), dim3(kCiTB), 0, st, nkeys, base, extra_p,
+                     extra_max, bits, dir);
+}
+
+void index_add_totals(const uint32_t* na_p, uint32_t m, uint32_t n_old, unsigned long long* cts, hipStream_t st) {
+  hipLaunchKernelGGL(k_ix_add_totals, dim3(1), dim3(64), 0, st, na_p, m, n_old, cts);
+}
+
 hipError_t index_match(const IndexView& idx, const uint64_t* keys, const uint8_t* digests, const uint8_t* valid,
                        uint32_t m, int64_t* pos, uint64_t* value, unsigned long long* counts, hipStream_t st) {
   hipError_t e;
   if (counts && (e = hipMemsetAsync(counts, 0, kIndexMatchCounts * sizeof(unsigned long long), st))) return e;
   if (!pos && !value && !counts) return hipSuccess;
-  hipLaunchKernelGGL(k_ci_match, dim3(ci_blocks(m)), dim3(kCiTB), 0, st, idx, keys, digests, valid, m, pos, value,
+  hipLaunchKernelGGL(k_ci_match, dim3(index_blocks(m)), dim3(kCiTB), 0, st, idx, keys, digests, valid, m, pos, value,
                      (uint32_t*)nullptr, counts);
   return hipGetLastError();
 }
@@ -444,24 +426,24 @@ hipError_t index_add(uint8_t* ws, uint32_t* cf_ws, const IndexView& old, const u
                      const uint64_t* values, const uint8_t* valid, uint32_t m, const IndexOut& out, int64_t* pos,
                      uint8_t* flags, unsigned long long* counts, hipStream_t st) {
   const IndexAddLayout l = index_add_layout(m);
-  int64_t* rep = at<int64_t>(ws, l.rep);
-  uint32_t* mlb = at<uint32_t>(ws, l.mlb);
-  uint32_t* npos = at<uint32_t>(ws, l.npos);
-  uint64_t* key_a = at<uint64_t>(ws, l.key_a);
-  uint64_t* key_b = at<uint64_t>(ws, l.key_b);
-  uint32_t* val_a = at<uint32_t>(ws, l.val_a);
-  uint32_t* val_b = at<uint32_t>(ws, l.val_b);
-  uint32_t* ord = at<uint32_t>(ws, l.ord);
-  uint32_t* lbs = at<uint32_t>(ws, l.lbs);
-  uint32_t* hist = at<uint32_t>(ws, l.hist);
-  uint32_t* bsum = at<uint32_t>(ws, l.bsum);
-  uint32_t* tot = at<uint32_t>(ws, l.tot);
-  unsigned long long* cts = at<unsigned long long>(ws, l.counts);
+  int64_t* rep = index_at<int64_t>(ws, l.rep);
+  uint32_t* mlb = index_at<uint32_t>(ws, l.mlb);
+  uint32_t* npos = index_at<uint32_t>(ws, l.npos);
+  uint64_t* key_a = index_at<uint64_t>(ws, l.key_a);
+  uint64_t* key_b = index_at<uint64_t>(ws, l.key_b);
+  uint32_t* val_a = index_at<uint32_t>(ws, l.val_a);
+  uint32_t* val_b = index_at<uint32_t>(ws, l.val_b);
+  uint32_t* ord = index_at<uint32_t>(ws, l.ord);
+  uint32_t* lbs = index_at<uint32_t>(ws, l.lbs);
+  uint32_t* hist = index_at<uint32_t>(ws, l.hist);
+  uint32_t* bsum = index_at<uint32_t>(ws, l.bsum);
+  uint32_t* tot = index_at<uint32_t>(ws, l.tot);
+  unsigned long long* cts = index_at<unsigned long long>(ws, l.counts);
   uint32_t* na = tot + 0;
   uint32_t* long_run = tot + 1;
   uint32_t* gate = tot + 2;
   const uint32_t cap = old.n + m;
-  const dim3 block(kCiTB), grid(ci_blocks(m));
+  const dim3 block(kCiTB), grid(index_blocks(m));
   hipError_t e;
   if ((e = hipMemsetAsync(tot, 0, l.bytes - l.tot, st))) return e;  // tot and counts
   if (m) {
@@ -493,17 +475,14 @@ hipError_t index_add(uint8_t* ws, uint32_t* cf_ws, const IndexView& old, const u
                        (const uint32_t*)mlb, keys, digests, values, m, out, cap, npos, lbs);
     if ((e = hipGetLastError())) return e;
   }
-  if (old.n)
-    hipLaunchKernelGGL(k_ci_place_old, dim3(ci_blocks(old.n)), block, 0, st, old, (const uint32_t*)lbs,
-                       (const uint32_t*)na, m, out, cap);
+  if (old.n) index_place_old(old, lbs, na, m, out, cap, st);
   if (m && (pos || flags || counts))
     hipLaunchKernelGGL(k_ci_add_out, grid, block, 0, st, (const int64_t*)rep, (const uint32_t*)mlb,
                        (const uint32_t*)npos, (const uint32_t*)lbs, (const uint32_t*)na, m, pos, flags, cts);
-  hipLaunchKernelGGL(k_ci_dir, dim3(ci_blocks(index_dir_slots(out.bits))), block, 0, st, (const uint64_t*)out.keys,
-                     (const uint32_t*)na, m, old.n, out.bits, out.dir);
+  index_build_dir(out.keys, old.n, na, m, out.bits, out.dir, st);
   if ((e = hipGetLastError())) return e;
   if (counts) {
-    hipLaunchKernelGGL(k_ci_totals, dim3(1), dim3(64), 0, st, (const uint32_t*)na, m, old.n, cts);
+    index_add_totals(na, m, old.n, cts, st);
     if ((e = hipGetLastError())) return e;
     return hipMemcpyAsync(counts, cts, kIndexAddCounts * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
   }

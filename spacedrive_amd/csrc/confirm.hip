@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "confirm.h"
+#include "index_device.h"
 
 namespace sdcas {
 
@@ -45,21 +46,14 @@ __device__ __forceinline__ uint64_t cf_mix(uint64_t x) {
   return x;
 }
 
-// the digest of file i as two 16-byte loads
-struct CfDigest {
-  uint4 a, b;
-};
-__device__ __forceinline__ CfDigest cf_digest(const uint8_t* __restrict__ digests, uint32_t i) {
-  const uint4* p = reinterpret_cast<const uint4*>(digests) + 2 * (size_t)i;
-  return CfDigest{p[0], p[1]};
-}
-__device__ __forceinline__ bool cf_same(const CfDigest& x, const CfDigest& y) {
+// (the digest of file i as two 16-byte loads: IxDigest / ix_digest, index_device.h)
+__device__ __forceinline__ bool cf_same(const IxDigest& x, const IxDigest& y) {
   return x.a.x == y.a.x && x.a.y == y.a.y && x.a.z == y.a.z && x.a.w == y.a.w && x.b.x == y.b.x && x.b.y == y.b.y &&
          x.b.z == y.b.z && x.b.w == y.b.w;
 }
 // every digest byte enters the class hash (digests that differ in one byte
 // land in different places, not at the end of one probe chain)
-__device__ __forceinline__ uint32_t cf_class_hash(uint64_t key, const CfDigest& d) {
+__device__ __forceinline__ uint32_t cf_class_hash(uint64_t key, const IxDigest& d) {
   constexpr uint64_t P = 0x9E3779B97F4A7C15ull;
   uint64_t h = cf_mix(key);
   h = (h ^ ((uint64_t)d.a.y << 32 | d.a.x)) * P;
@@ -84,7 +78,7 @@ __global__ void k_cf_insert(const uint64_t* __restrict__ keys, const uint8_t* __
     return;
   }
   const uint64_t key = keys[i];
-  const CfDigest dig = cf_digest(digests, i);
+  const IxDigest dig = ix_digest(digests, i);
   // the class table: key and digest
   uint32_t h = cf_class_hash(key, dig) & mask;
   for (;;) {
@@ -94,7 +88,7 @@ __global__ void k_cf_insert(const uint64_t* __restrict__ keys, const uint8_t* __
       if (prev == kCfEmpty) break;
       cur = prev;
     }
-    if (keys[cur] == key && cf_same(cf_digest(digests, cur), dig)) {
+    if (keys[cur] == key && cf_same(ix_digest(digests, cur), dig)) {
       if (cur > i) atomicMin(&tab_c[h], i);
       break;
     }

@@ -351,6 +351,18 @@ struct sdcas_ctx {
 
 namespace {
 
+// A workspace grown to `need` elements for a call on st. The host waits first
+// for the scratch and for st, as an earlier call's kernels may still use the
+// buffer about to be freed; a buffer that is large enough costs nothing.
+template <class T>
+int grow_synced(sdcas_ctx* c, DevBuf<T>& buf, size_t need, hipStream_t st, const char* what) {
+  if (need <= buf.cap) return SDCAS_OK;
+  hipError_t e = c->scratch_sync();
+  if (!e) e = hipStreamSynchronize(st);
+  if (!e) e = buf.ensure(need);
+  return e ? c->hip_fail(e, what) : SDCAS_OK;
+}
+
 int reserve_ws(sdcas_ctx* c, size_t max_msgs, uint64_t max_chunks) {
   hipError_t e;
   // the chunk scan takes an int count (hipcub)
@@ -1964,15 +1976,9 @@ int sdcas_dev_dedup(sdcas_ctx* c, const uint64_t* d_keys, const uint8_t* d_has_k
 
 // ---- duplicates confirmed by checksum (confirm.hip) ------------------------------
 
-// the group-by's workspace grown to n files; the stream waits first, as an
-// earlier call's kernels may still use the workspace about to be freed
+// the group-by's workspace grown to n files
 static int confirm_ws(sdcas_ctx* c, size_t n, hipStream_t st) {
-  const size_t need = (size_t)confirm_ws_words(n);
-  if (need <= c->cf_ws.cap) return SDCAS_OK;
-  hipError_t e = c->scratch_sync();
-  if (!e) e = hipStreamSynchronize(st);
-  if (!e) e = c->cf_ws.ensure(need);
-  return e ? c->hip_fail(e, "confirm workspace") : SDCAS_OK;
+  return grow_synced(c, c->cf_ws, (size_t)confirm_ws_words(n), st, "confirm workspace");
 }
 
 int sdcas_dev_confirm_duplicates(sdcas_ctx* c, const uint64_t* d_keys, const uint8_t* d_digests32,
@@ -2035,15 +2041,9 @@ int sdcas_confirm_duplicates(sdcas_ctx* c, const uint64_t* keys, const uint8_t* 
 
 // ---- duplicate sets (dupsets.hip) ----------------------------------------------
 
-// the workspace grown to n files; the stream waits first, as an earlier call's
-// kernels may still use the workspace about to be freed
+// the workspace grown to n files
 static int dupsets_ws(sdcas_ctx* c, size_t n, hipStream_t st) {
-  const size_t need = (size_t)dupsets_ws_words(n);
-  if (need <= c->ds_ws.cap) return SDCAS_OK;
-  hipError_t e = c->scratch_sync();
-  if (!e) e = hipStreamSynchronize(st);
-  if (!e) e = c->ds_ws.ensure(need);
-  return e ? c->hip_fail(e, "duplicate sets workspace") : SDCAS_OK;
+  return grow_synced(c, c->ds_ws, (size_t)dupsets_ws_words(n), st, "duplicate sets workspace");
 }
 
 static int dupsets_args(sdcas_ctx* c, const char* who, const void* rep, const void* sizes, size_t n, uint32_t order) {
@@ -2279,15 +2279,9 @@ int sdcas_tree_digests(sdcas_ctx* c, const int64_t* parent, const uint8_t* is_di
   return SDCAS_OK;
 }
 
-// the workspace grown to n entries; the stream waits first, as an earlier
-// call's kernels may still use the workspace about to be freed
+// the workspace grown to n entries
 static int tree_top_ws(sdcas_ctx* c, size_t n, hipStream_t st) {
-  const size_t need = (size_t)tree_top_ws_words(n);
-  if (need <= c->tt_ws.cap) return SDCAS_OK;
-  hipError_t e = c->scratch_sync();
-  if (!e) e = hipStreamSynchronize(st);
-  if (!e) e = c->tt_ws.ensure(need);
-  return e ? c->hip_fail(e, "tree_top workspace") : SDCAS_OK;
+  return grow_synced(c, c->tt_ws, (size_t)tree_top_ws_words(n), st, "tree_top workspace");
 }
 
 int sdcas_dev_tree_top(sdcas_ctx* c, const int64_t* d_parent, const int64_t* d_rep, size_t n, int64_t* d_out_top_rep,
@@ -2659,15 +2653,9 @@ static int sharing_args(sdcas_ctx* c, const char* who, const void* chunk_file, c
   return SDCAS_OK;
 }
 
-// the workspace grown to m chunks of n_files files; the stream waits first, as
-// an earlier call's kernels may still use the workspace about to be freed
+// the workspace grown to m chunks of n_files files
 static int sharing_ws(sdcas_ctx* c, size_t m, size_t n_files, hipStream_t st) {
-  const size_t need = (size_t)cdc_share_ws_bytes(m, n_files);
-  if (need <= c->cs_ws.cap) return SDCAS_OK;
-  hipError_t e = c->scratch_sync();
-  if (!e) e = hipStreamSynchronize(st);
-  if (!e) e = c->cs_ws.ensure(need);
-  return e ? c->hip_fail(e, "chunk sharing workspace") : SDCAS_OK;
+  return grow_synced(c, c->cs_ws, (size_t)cdc_share_ws_bytes(m, n_files), st, "chunk sharing workspace");
 }
 
 int sdcas_dev_chunk_sharing(sdcas_ctx* c, const uint32_t* d_chunk_file, const uint64_t* d_chunk_len,
@@ -2790,50 +2778,51 @@ static int index_add_args(sdcas_ctx* c, const char* who, const void* old_keys, c
   return SDCAS_OK;
 }
 
-// the add's workspace (and the group-by's) grown to a batch of m; the stream
-// waits first, as an earlier call's kernels may still use what is freed
-static int index_add_ws(sdcas_ctx* c, size_t m, hipStream_t st) {
-  const size_t need = (size_t)index_add_layout(m).bytes;
-  if (need > c->ci_ws.cap) {
-    hipError_t e = c->scratch_sync();
-    if (!e) e = hipStreamSynchronize(st);
-    if (!e) e = c->ci_ws.ensure(need);
-    if (e) return c->hip_fail(e, "chunk index workspace");
-  }
+// The chunk index holds pairs, the holders index (chunk_holders.hip) triples:
+// every add and match entry point of the two is one body, told which by this.
+enum IndexKind { kPairs, kTriples };
+
+static int index_io(sdcas_ctx* c, size_t bytes, hipStream_t st) {
+  return grow_synced(c, c->ci_io, bytes, st, "chunk index buffers");
+}
+static int holders_ws(sdcas_ctx* c, size_t need, hipStream_t st) {
+  return grow_synced(c, c->ch_ws, need, st, "chunk holders workspace");
+}
+// the add's workspace (for pairs the group-by's too) grown to a batch of m
+static int index_add_ws(sdcas_ctx* c, IndexKind kind, size_t m, hipStream_t st) {
+  if (kind == kTriples) return holders_ws(c, (size_t)holders_add_layout(m).bytes, st);
+  if (int rc = grow_synced(c, c->ci_ws, (size_t)index_add_layout(m).bytes, st, "chunk index workspace")) return rc;
   return m ? confirm_ws(c, m, st) : SDCAS_OK;
 }
-static int index_io(sdcas_ctx* c, size_t bytes, hipStream_t st) {
-  if (bytes <= c->ci_io.cap) return SDCAS_OK;
-  hipError_t e = c->scratch_sync();
-  if (!e) e = hipStreamSynchronize(st);
-  if (!e) e = c->ci_io.ensure(bytes);
-  return e ? c->hip_fail(e, "chunk index buffers") : SDCAS_OK;
+static hipError_t index_add_kind(sdcas_ctx* c, IndexKind kind, const IndexView& old, const uint64_t* keys,
+                                 const uint8_t* digests, const uint64_t* values, const uint8_t* valid, uint32_t m,
+                                 const IndexOut& out, int64_t* pos, uint8_t* flags, unsigned long long* counts,
+                                 hipStream_t st) {
+  if (kind == kTriples)
+    return holders_add(c->ch_ws.p, old, keys, digests, values, valid, m, out, pos, flags, counts, st);
+  return index_add(c->ci_ws.p, c->cf_ws.p, old, keys, digests, values, valid, m, out, pos, flags, counts, st);
+}
+static hipError_t index_match_kind(IndexKind kind, const IndexView& v, const uint64_t* keys, const uint8_t* digests,
+                                   const uint8_t* valid, uint32_t m, int64_t* pos, uint64_t* value, uint32_t* holders,
+                                   unsigned long long* counts, hipStream_t st) {
+  if (kind == kTriples) return holders_match(v, keys, digests, valid, m, pos, value, holders, counts, st);
+  return index_match(v, keys, digests, valid, m, pos, value, counts, st);
 }
 
-int sdcas_dev_chunk_index_match(sdcas_ctx* c, const uint64_t* d_idx_keys, const uint8_t* d_idx_digests32,
-                                const uint64_t* d_idx_values, const uint32_t* d_idx_dir, uint64_t n, uint32_t bits,
-                                const uint64_t* d_keys, const uint8_t* d_digests32, const uint8_t* d_valid, size_t m,
-                                int64_t* d_out_pos, uint64_t* d_out_value, uint64_t* d_counts, void* stream) {
-  if (!c) return SDCAS_E_INVALID;
-  if (int rc = index_view_args(c, "dev_chunk_index_match", d_idx_keys, d_idx_digests32, d_idx_dir, n, bits)) return rc;
-  if (int rc = index_batch_args(c, "dev_chunk_index_match", d_keys, d_digests32, m)) return rc;
-  if ((((uintptr_t)d_idx_digests32 | (uintptr_t)d_digests32) & 15) ||
-      (((uintptr_t)d_idx_keys | (uintptr_t)d_idx_values | (uintptr_t)d_keys | (uintptr_t)d_out_pos |
-        (uintptr_t)d_out_value | (uintptr_t)d_counts) & 7) ||
-      ((uintptr_t)d_idx_dir & 3))
-    return c->fail(SDCAS_E_INVALID, "dev_chunk_index_match: an array is misaligned (digests 16 B, directory 4 B, others 8 B)");
-  DevCall call(c, stream);
-  if (call.rc) return call.rc;
-  hipError_t e;
-  if (m == 0) {
-    if (d_counts && (e = hipMemsetAsync(d_counts, 0, kIndexMatchCounts * sizeof(uint64_t), call.st)))
-      return c->hip_fail(e, "counts");
-    return SDCAS_OK;
-  }
-  const IndexView v{d_idx_keys, d_idx_digests32, d_idx_values, d_idx_dir, (uint32_t)n, bits};
-  e = index_match(v, d_keys, d_digests32, d_valid, (uint32_t)m, d_out_pos, d_out_value, (unsigned long long*)d_counts,
-                  call.st);
-  return e ? c->hip_fail(e, "dev_chunk_index_match") : SDCAS_OK;
+// a HIP error of entry point `who` at `step` ("", " H2D", ...)
+static int index_hip_fail(sdcas_ctx* c, hipError_t e, const char* who, const char* step) {
+  return c->hip_fail(e, (std::string(who) + step).c_str());
+}
+
+// a pointer of the first group off 16 bytes, of the second off 8, of the third
+// off 4 (a null pointer passes)
+static bool index_misaligned(std::initializer_list<const void*> p16, std::initializer_list<const void*> p8,
+                             std::initializer_list<const void*> p4) {
+  uintptr_t a = 0, b = 0, d = 0;
+  for (const void* p : p16) a |= (uintptr_t)p;
+  for (const void* p : p8) b |= (uintptr_t)p;
+  for (const void* p : p4) d |= (uintptr_t)p;
+  return (a & 15) || (b & 7) || (d & 3);
 }
 
 namespace {
@@ -2846,51 +2835,216 @@ struct Parts {
     return at;
   }
 };
+// an index's four arrays among the parts of ci_io
+struct IndexParts {
+  size_t k, d, v, dir, dir_bytes;
+};
 }  // namespace
 
-int sdcas_chunk_index_match(sdcas_ctx* c, const uint64_t* idx_keys, const uint8_t* idx_digests32,
-                            const uint64_t* idx_values, const uint32_t* idx_dir, uint64_t n, uint32_t bits,
-                            const uint64_t* keys, const uint8_t* digests32, const uint8_t* valid, size_t m,
-                            int64_t* out_pos, uint64_t* out_value, sdcas_index_match_counts* out_counts) {
+static IndexParts index_parts(Parts& p, size_t entries, size_t dir_bytes) {
+  IndexParts x{};
+  x.k = p.take(8 * entries), x.d = p.take(32 * entries), x.v = p.take(8 * entries), x.dir = p.take(dir_bytes);
+  x.dir_bytes = dir_bytes;
+  return x;
+}
+// the directory bytes an index of n entries is read with
+static size_t index_old_dir_bytes(uint64_t n, uint32_t bits) { return n ? 4 * (size_t)index_dir_slots(bits) : 0; }
+
+// a host index's arrays up into their parts of ci_io; *v <- its view there
+static hipError_t index_stage(uint8_t* io, const IndexParts& x, const uint64_t* keys, const uint8_t* digests,
+                              const uint64_t* values, const uint32_t* dir, size_t n, uint32_t bits, hipStream_t st,
+                              IndexView* v) {
+  hipError_t e;
+  if (n && ((e = hipMemcpyAsync(io + x.k, keys, 8 * n, hipMemcpyHostToDevice, st)) ||
+            (e = hipMemcpyAsync(io + x.d, digests, 32 * n, hipMemcpyHostToDevice, st)) ||
+            (values && (e = hipMemcpyAsync(io + x.v, values, 8 * n, hipMemcpyHostToDevice, st))) ||
+            (e = hipMemcpyAsync(io + x.dir, dir, x.dir_bytes, hipMemcpyHostToDevice, st))))
+    return e;
+  *v = IndexView{reinterpret_cast<const uint64_t*>(io + x.k), io + x.d,
+                 values ? reinterpret_cast<const uint64_t*>(io + x.v) : nullptr,
+                 reinterpret_cast<const uint32_t*>(io + x.dir), (uint32_t)n, bits};
+  return hipSuccess;
+}
+static IndexOut index_out_parts(uint8_t* io, const IndexParts& x, uint32_t bits) {
+  return IndexOut{reinterpret_cast<uint64_t*>(io + x.k), io + x.d, reinterpret_cast<uint64_t*>(io + x.v),
+                  reinterpret_cast<uint32_t*>(io + x.dir), bits};
+}
+// A new index down from its parts, the counts first: they say how many entries
+// of the new arrays follow. Waits for the counts, enqueues the rest.
+static int index_fetch(sdcas_ctx* c, const char* who, const uint8_t* io, const IndexParts& x, size_t o_cts, void* cts,
+                       size_t cts_bytes, const uint64_t* entries_new, size_t cap, uint64_t* new_keys,
+                       uint8_t* new_digests, uint64_t* new_values, uint32_t* new_dir, hipStream_t st) {
+  hipError_t e;
+  if ((e = hipMemcpyAsync(cts, io + o_cts, cts_bytes, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
+    return index_hip_fail(c, e, who, " counts");
+  const size_t nn = (size_t)*entries_new;
+  if (nn > cap) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
+  if ((nn && ((e = hipMemcpyAsync(new_keys, io + x.k, 8 * nn, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(new_digests, io + x.d, 32 * nn, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(new_values, io + x.v, 8 * nn, hipMemcpyDeviceToHost, st)))) ||
+      (e = hipMemcpyAsync(new_dir, io + x.dir, x.dir_bytes, hipMemcpyDeviceToHost, st)))
+    return index_hip_fail(c, e, who, " D2H");
+  return SDCAS_OK;
+}
+
+static int index_dev_match(sdcas_ctx* c, IndexKind kind, const char* who, const uint64_t* d_idx_keys,
+                           const uint8_t* d_idx_digests32, const uint64_t* d_idx_values, const uint32_t* d_idx_dir,
+                           uint64_t n, uint32_t bits, const uint64_t* d_keys, const uint8_t* d_digests32,
+                           const uint8_t* d_valid, size_t m, int64_t* d_out_pos, uint64_t* d_out_value,
+                           uint32_t* d_out_holders, uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_view_args(c, who, d_idx_keys, d_idx_digests32, d_idx_dir, n, bits)) return rc;
+  if (int rc = index_batch_args(c, who, d_keys, d_digests32, m)) return rc;
+  if (index_misaligned({d_idx_digests32, d_digests32},
+                       {d_idx_keys, d_idx_values, d_keys, d_out_pos, d_out_value, d_counts},
+                       {d_idx_dir, d_out_holders}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (digests 16 B, %s 4 B, others 8 B)", who,
+                   kind == kTriples ? "directory and holders" : "directory");
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  if (m == 0) {
+    if (d_counts && (e = hipMemsetAsync(d_counts, 0, kIndexMatchCounts * sizeof(uint64_t), call.st)))
+      return c->hip_fail(e, "counts");
+    return SDCAS_OK;
+  }
+  const IndexView v{d_idx_keys, d_idx_digests32, d_idx_values, d_idx_dir, (uint32_t)n, bits};
+  e = index_match_kind(kind, v, d_keys, d_digests32, d_valid, (uint32_t)m, d_out_pos, d_out_value, d_out_holders,
+                       (unsigned long long*)d_counts, call.st);
+  return e ? index_hip_fail(c, e, who, "") : SDCAS_OK;
+}
+
+static int index_host_match(sdcas_ctx* c, IndexKind kind, const char* who, const uint64_t* idx_keys,
+                            const uint8_t* idx_digests32, const uint64_t* idx_values, const uint32_t* idx_dir,
+                            uint64_t n, uint32_t bits, const uint64_t* keys, const uint8_t* digests32,
+                            const uint8_t* valid, size_t m, int64_t* out_pos, uint64_t* out_value,
+                            uint32_t* out_holders, sdcas_index_match_counts* out_counts) {
   static_assert(sizeof(sdcas_index_match_counts) == kIndexMatchCounts * sizeof(uint64_t), "four u64 counts");
   if (!c) return SDCAS_E_INVALID;
-  if (int rc = index_view_args(c, "chunk_index_match", idx_keys, idx_digests32, idx_dir, n, bits)) return rc;
-  if (int rc = index_batch_args(c, "chunk_index_match", keys, digests32, m)) return rc;
+  if (int rc = index_view_args(c, who, idx_keys, idx_digests32, idx_dir, n, bits)) return rc;
+  if (int rc = index_batch_args(c, who, keys, digests32, m)) return rc;
   if (out_counts) memset(out_counts, 0, sizeof *out_counts);
   if (m == 0) return SDCAS_OK;
   DevCall call(c, nullptr);
   if (call.rc) return call.rc;
   hipError_t e;
   hipStream_t st = call.st;
-  const size_t dir_bytes = n ? 4 * (size_t)index_dir_slots(bits) : 0;
   Parts p;
-  const size_t o_ik = p.take(8 * n), o_id = p.take(32 * n), o_iv = p.take(8 * n), o_dir = p.take(dir_bytes),
-               o_k = p.take(8 * m), o_d = p.take(32 * m), o_v = p.take(m), o_pos = p.take(8 * m),
-               o_val = p.take(8 * m), o_cts = p.take(8 * kIndexMatchCounts);
+  const IndexParts ip = index_parts(p, n, index_old_dir_bytes(n, bits));
+  const size_t o_k = p.take(8 * m), o_d = p.take(32 * m), o_v = p.take(m), o_pos = p.take(8 * m),
+               o_val = p.take(8 * m), o_h = p.take(kind == kTriples ? 4 * m : 0),
+               o_cts = p.take(8 * kIndexMatchCounts);
   if (int rc = index_io(c, p.o, st)) return rc;
   uint8_t* io = c->ci_io.p;
-  if ((n && ((e = hipMemcpyAsync(io + o_ik, idx_keys, 8 * n, hipMemcpyHostToDevice, st)) ||
-             (e = hipMemcpyAsync(io + o_id, idx_digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
-             (idx_values && (e = hipMemcpyAsync(io + o_iv, idx_values, 8 * n, hipMemcpyHostToDevice, st))) ||
-             (e = hipMemcpyAsync(io + o_dir, idx_dir, dir_bytes, hipMemcpyHostToDevice, st)))) ||
+  IndexView v{};
+  if ((e = index_stage(io, ip, idx_keys, idx_digests32, idx_values, idx_dir, n, bits, st, &v)) ||
       (e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
       (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
       (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))
-    return c->hip_fail(e, "chunk_index_match H2D");
-  const IndexView v{reinterpret_cast<const uint64_t*>(io + o_ik), io + o_id,
-                    idx_values ? reinterpret_cast<const uint64_t*>(io + o_iv) : nullptr,
-                    reinterpret_cast<const uint32_t*>(io + o_dir), (uint32_t)n, bits};
-  if ((e = index_match(v, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d, valid ? io + o_v : nullptr,
-                       (uint32_t)m, out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr,
-                       out_value ? reinterpret_cast<uint64_t*>(io + o_val) : nullptr,
-                       out_counts ? reinterpret_cast<unsigned long long*>(io + o_cts) : nullptr, st)))
-    return c->hip_fail(e, "chunk_index_match");
+    return index_hip_fail(c, e, who, " H2D");
+  if ((e = index_match_kind(kind, v, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d, valid ? io + o_v : nullptr,
+                            (uint32_t)m, out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr,
+                            out_value ? reinterpret_cast<uint64_t*>(io + o_val) : nullptr,
+                            out_holders ? reinterpret_cast<uint32_t*>(io + o_h) : nullptr,
+                            out_counts ? reinterpret_cast<unsigned long long*>(io + o_cts) : nullptr, st)))
+    return index_hip_fail(c, e, who, "");
   if ((out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
       (out_value && (e = hipMemcpyAsync(out_value, io + o_val, 8 * m, hipMemcpyDeviceToHost, st))) ||
+      (out_holders && (e = hipMemcpyAsync(out_holders, io + o_h, 4 * m, hipMemcpyDeviceToHost, st))) ||
       (out_counts && (e = hipMemcpyAsync(out_counts, io + o_cts, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, "chunk_index_match D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_index_match sync");
+    return index_hip_fail(c, e, who, " D2H");
+  if ((e = hipStreamSynchronize(st))) return index_hip_fail(c, e, who, " sync");
   return SDCAS_OK;
+}
+
+static int index_dev_add(sdcas_ctx* c, IndexKind kind, const char* who, const uint64_t* d_old_keys,
+                         const uint8_t* d_old_digests32, const uint64_t* d_old_values, const uint32_t* d_old_dir,
+                         uint64_t n_old, uint32_t bits_old, const uint64_t* d_keys, const uint8_t* d_digests32,
+                         const uint64_t* d_values, const uint8_t* d_valid, size_t m, uint64_t* d_new_keys,
+                         uint8_t* d_new_digests32, uint64_t* d_new_values, uint32_t* d_new_dir, uint32_t bits_new,
+                         int64_t* d_out_pos, uint8_t* d_out_flags, uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_add_args(c, who, d_old_keys, d_old_digests32, d_old_values, d_old_dir, n_old, bits_old, d_keys,
+                              d_digests32, m, d_new_keys, d_new_digests32, d_new_values, d_new_dir, bits_new))
+    return rc;
+  if (index_misaligned({d_old_digests32, d_digests32, d_new_digests32},
+                       {d_old_keys, d_old_values, d_keys, d_values, d_new_keys, d_new_values, d_out_pos, d_counts},
+                       {d_old_dir, d_new_dir}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (digests 16 B, directories 4 B, others 8 B)", who);
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = index_add_ws(c, kind, m, call.st)) return rc;
+  const IndexView old{d_old_keys, d_old_digests32, d_old_values, d_old_dir, (uint32_t)n_old, bits_old};
+  const IndexOut out{d_new_keys, d_new_digests32, d_new_values, d_new_dir, bits_new};
+  hipError_t e = index_add_kind(c, kind, old, d_keys, d_digests32, d_values, d_valid, (uint32_t)m, out, d_out_pos,
+                                d_out_flags, (unsigned long long*)d_counts, call.st);
+  return e ? index_hip_fail(c, e, who, "") : SDCAS_OK;
+}
+
+static int index_host_add(sdcas_ctx* c, IndexKind kind, const char* who, const uint64_t* old_keys,
+                          const uint8_t* old_digests32, const uint64_t* old_values, const uint32_t* old_dir,
+                          uint64_t n_old, uint32_t bits_old, const uint64_t* keys, const uint8_t* digests32,
+                          const uint64_t* values, const uint8_t* valid, size_t m, uint64_t* new_keys,
+                          uint8_t* new_digests32, uint64_t* new_values, uint32_t* new_dir, uint32_t bits_new,
+                          int64_t* out_pos, uint8_t* out_flags, sdcas_index_add_counts* out_counts) {
+  static_assert(sizeof(sdcas_index_add_counts) == kIndexAddCounts * sizeof(uint64_t), "six u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = index_add_args(c, who, old_keys, old_digests32, old_values, old_dir, n_old, bits_old, keys, digests32,
+                              m, new_keys, new_digests32, new_values, new_dir, bits_new))
+    return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipError_t e;
+  hipStream_t st = call.st;
+  const size_t n = n_old, cap = n_old + m;
+  Parts p;
+  const IndexParts op = index_parts(p, n, index_old_dir_bytes(n, bits_old));
+  const size_t o_k = p.take(8 * m), o_d = p.take(32 * m), o_val = p.take(8 * m), o_v = p.take(m);
+  const IndexParts np = index_parts(p, cap, 4 * (size_t)index_dir_slots(bits_new));
+  const size_t o_pos = p.take(8 * m), o_fl = p.take(m), o_cts = p.take(8 * kIndexAddCounts);
+  if (int rc = index_io(c, p.o, st)) return rc;
+  if (int rc = index_add_ws(c, kind, m, st)) return rc;
+  uint8_t* io = c->ci_io.p;
+  IndexView old{};
+  if ((e = index_stage(io, op, old_keys, old_digests32, old_values, old_dir, n, bits_old, st, &old)) ||
+      (m && ((e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
+             (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
+             (values && (e = hipMemcpyAsync(io + o_val, values, 8 * m, hipMemcpyHostToDevice, st))) ||
+             (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))))
+    return index_hip_fail(c, e, who, " H2D");
+  if ((e = index_add_kind(c, kind, old, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d,
+                          values ? reinterpret_cast<const uint64_t*>(io + o_val) : nullptr,
+                          valid ? io + o_v : nullptr, (uint32_t)m, index_out_parts(io, np, bits_new),
+                          out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr, out_flags ? io + o_fl : nullptr,
+                          reinterpret_cast<unsigned long long*>(io + o_cts), st)))
+    return index_hip_fail(c, e, who, "");
+  sdcas_index_add_counts cts;
+  if (int rc = index_fetch(c, who, io, np, o_cts, &cts, sizeof cts, &cts.entries_new, cap, new_keys, new_digests32,
+                           new_values, new_dir, st))
+    return rc;
+  if ((m && out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
+      (m && out_flags && (e = hipMemcpyAsync(out_flags, io + o_fl, m, hipMemcpyDeviceToHost, st))))
+    return index_hip_fail(c, e, who, " D2H");
+  if ((e = hipStreamSynchronize(st))) return index_hip_fail(c, e, who, " sync");
+  if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+int sdcas_dev_chunk_index_match(sdcas_ctx* c, const uint64_t* d_idx_keys, const uint8_t* d_idx_digests32,
+                                const uint64_t* d_idx_values, const uint32_t* d_idx_dir, uint64_t n, uint32_t bits,
+                                const uint64_t* d_keys, const uint8_t* d_digests32, const uint8_t* d_valid, size_t m,
+                                int64_t* d_out_pos, uint64_t* d_out_value, uint64_t* d_counts, void* stream) {
+  return index_dev_match(c, kPairs, "dev_chunk_index_match", d_idx_keys, d_idx_digests32, d_idx_values, d_idx_dir, n,
+                         bits, d_keys, d_digests32, d_valid, m, d_out_pos, d_out_value, nullptr, d_counts, stream);
+}
+
+int sdcas_chunk_index_match(sdcas_ctx* c, const uint64_t* idx_keys, const uint8_t* idx_digests32,
+                            const uint64_t* idx_values, const uint32_t* idx_dir, uint64_t n, uint32_t bits,
+                            const uint64_t* keys, const uint8_t* digests32, const uint8_t* valid, size_t m,
+                            int64_t* out_pos, uint64_t* out_value, sdcas_index_match_counts* out_counts) {
+  return index_host_match(c, kPairs, "chunk_index_match", idx_keys, idx_digests32, idx_values, idx_dir, n, bits, keys,
+                          digests32, valid, m, out_pos, out_value, nullptr, out_counts);
 }
 
 int sdcas_dev_chunk_index_add(sdcas_ctx* c, const uint64_t* d_old_keys, const uint8_t* d_old_digests32,
@@ -2900,24 +3054,9 @@ int sdcas_dev_chunk_index_add(sdcas_ctx* c, const uint64_t* d_old_keys, const ui
                               uint8_t* d_new_digests32, uint64_t* d_new_values, uint32_t* d_new_dir,
                               uint32_t bits_new, int64_t* d_out_pos, uint8_t* d_out_flags, uint64_t* d_counts,
                               void* stream) {
-  if (!c) return SDCAS_E_INVALID;
-  if (int rc = index_add_args(c, "dev_chunk_index_add", d_old_keys, d_old_digests32, d_old_values, d_old_dir, n_old,
-                              bits_old, d_keys, d_digests32, m, d_new_keys, d_new_digests32, d_new_values, d_new_dir,
-                              bits_new))
-    return rc;
-  if ((((uintptr_t)d_old_digests32 | (uintptr_t)d_digests32 | (uintptr_t)d_new_digests32) & 15) ||
-      (((uintptr_t)d_old_keys | (uintptr_t)d_old_values | (uintptr_t)d_keys | (uintptr_t)d_values |
-        (uintptr_t)d_new_keys | (uintptr_t)d_new_values | (uintptr_t)d_out_pos | (uintptr_t)d_counts) & 7) ||
-      (((uintptr_t)d_old_dir | (uintptr_t)d_new_dir) & 3))
-    return c->fail(SDCAS_E_INVALID, "dev_chunk_index_add: an array is misaligned (digests 16 B, directories 4 B, others 8 B)");
-  DevCall call(c, stream);
-  if (call.rc) return call.rc;
-  if (int rc = index_add_ws(c, m, call.st)) return rc;
-  const IndexView old{d_old_keys, d_old_digests32, d_old_values, d_old_dir, (uint32_t)n_old, bits_old};
-  const IndexOut out{d_new_keys, d_new_digests32, d_new_values, d_new_dir, bits_new};
-  hipError_t e = index_add(c->ci_ws.p, c->cf_ws.p, old, d_keys, d_digests32, d_values, d_valid, (uint32_t)m, out,
-                           d_out_pos, d_out_flags, (unsigned long long*)d_counts, call.st);
-  return e ? c->hip_fail(e, "dev_chunk_index_add") : SDCAS_OK;
+  return index_dev_add(c, kPairs, "dev_chunk_index_add", d_old_keys, d_old_digests32, d_old_values, d_old_dir, n_old,
+                       bits_old, d_keys, d_digests32, d_values, d_valid, m, d_new_keys, d_new_digests32, d_new_values,
+                       d_new_dir, bits_new, d_out_pos, d_out_flags, d_counts, stream);
 }
 
 int sdcas_chunk_index_add(sdcas_ctx* c, const uint64_t* old_keys, const uint8_t* old_digests32,
@@ -2926,61 +3065,9 @@ int sdcas_chunk_index_add(sdcas_ctx* c, const uint64_t* old_keys, const uint8_t*
                           const uint8_t* valid, size_t m, uint64_t* new_keys, uint8_t* new_digests32,
                           uint64_t* new_values, uint32_t* new_dir, uint32_t bits_new, int64_t* out_pos,
                           uint8_t* out_flags, sdcas_index_add_counts* out_counts) {
-  static_assert(sizeof(sdcas_index_add_counts) == kIndexAddCounts * sizeof(uint64_t), "six u64 counts");
-  if (!c) return SDCAS_E_INVALID;
-  if (int rc = index_add_args(c, "chunk_index_add", old_keys, old_digests32, old_values, old_dir, n_old, bits_old, keys,
-                              digests32, m, new_keys, new_digests32, new_values, new_dir, bits_new))
-    return rc;
-  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
-  DevCall call(c, nullptr);
-  if (call.rc) return call.rc;
-  hipError_t e;
-  hipStream_t st = call.st;
-  const size_t n = n_old, cap = n_old + m;
-  const size_t odir_bytes = n ? 4 * (size_t)index_dir_slots(bits_old) : 0, ndir_bytes = 4 * (size_t)index_dir_slots(bits_new);
-  Parts p;
-  const size_t o_ok = p.take(8 * n), o_od = p.take(32 * n), o_ov = p.take(8 * n), o_odir = p.take(odir_bytes),
-               o_k = p.take(8 * m), o_d = p.take(32 * m), o_val = p.take(8 * m), o_v = p.take(m),
-               o_nk = p.take(8 * cap), o_nd = p.take(32 * cap), o_nv = p.take(8 * cap), o_ndir = p.take(ndir_bytes),
-               o_pos = p.take(8 * m), o_fl = p.take(m), o_cts = p.take(8 * kIndexAddCounts);
-  if (int rc = index_io(c, p.o, st)) return rc;
-  if (int rc = index_add_ws(c, m, st)) return rc;
-  uint8_t* io = c->ci_io.p;
-  if ((n && ((e = hipMemcpyAsync(io + o_ok, old_keys, 8 * n, hipMemcpyHostToDevice, st)) ||
-             (e = hipMemcpyAsync(io + o_od, old_digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
-             (old_values && (e = hipMemcpyAsync(io + o_ov, old_values, 8 * n, hipMemcpyHostToDevice, st))) ||
-             (e = hipMemcpyAsync(io + o_odir, old_dir, odir_bytes, hipMemcpyHostToDevice, st)))) ||
-      (m && ((e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
-             (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
-             (values && (e = hipMemcpyAsync(io + o_val, values, 8 * m, hipMemcpyHostToDevice, st))) ||
-             (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))))
-    return c->hip_fail(e, "chunk_index_add H2D");
-  const IndexView old{reinterpret_cast<const uint64_t*>(io + o_ok), io + o_od,
-                      old_values ? reinterpret_cast<const uint64_t*>(io + o_ov) : nullptr,
-                      reinterpret_cast<const uint32_t*>(io + o_odir), (uint32_t)n, bits_old};
-  const IndexOut out{reinterpret_cast<uint64_t*>(io + o_nk), io + o_nd, reinterpret_cast<uint64_t*>(io + o_nv),
-                     reinterpret_cast<uint32_t*>(io + o_ndir), bits_new};
-  if ((e = index_add(c->ci_ws.p, c->cf_ws.p, old, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d,
-                     values ? reinterpret_cast<const uint64_t*>(io + o_val) : nullptr, valid ? io + o_v : nullptr,
-                     (uint32_t)m, out, out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr,
-                     out_flags ? io + o_fl : nullptr, reinterpret_cast<unsigned long long*>(io + o_cts), st)))
-    return c->hip_fail(e, "chunk_index_add");
-  // the counts down first: they say how many entries of the new arrays follow
-  sdcas_index_add_counts cts;
-  if ((e = hipMemcpyAsync(&cts, io + o_cts, sizeof cts, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
-    return c->hip_fail(e, "chunk_index_add counts");
-  const size_t nn = (size_t)cts.entries_new;
-  if (nn > cap) return c->fail(SDCAS_E_HIP, "chunk_index_add: counts out of range");
-  if ((nn && ((e = hipMemcpyAsync(new_keys, io + o_nk, 8 * nn, hipMemcpyDeviceToHost, st)) ||
-              (e = hipMemcpyAsync(new_digests32, io + o_nd, 32 * nn, hipMemcpyDeviceToHost, st)) ||
-              (e = hipMemcpyAsync(new_values, io + o_nv, 8 * nn, hipMemcpyDeviceToHost, st)))) ||
-      (e = hipMemcpyAsync(new_dir, io + o_ndir, ndir_bytes, hipMemcpyDeviceToHost, st)) ||
-      (m && out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
-      (m && out_flags && (e = hipMemcpyAsync(out_flags, io + o_fl, m, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, "chunk_index_add D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_index_add sync");
-  if (out_counts) *out_counts = cts;
-  return SDCAS_OK;
+  return index_host_add(c, kPairs, "chunk_index_add", old_keys, old_digests32, old_values, old_dir, n_old, bits_old,
+                        keys, digests32, values, valid, m, new_keys, new_digests32, new_values, new_dir, bits_new,
+                        out_pos, out_flags, out_counts);
 }
 
 // ---- the holders index (chunk_holders.hip) --------------------------------------------
@@ -2995,16 +3082,6 @@ int sdcas_chunk_holders_check(const uint64_t* keys, const uint8_t* digests32, co
     return SDCAS_E_INVALID;
   }
   return SDCAS_OK;
-}
-
-// the holders calls' workspace grown to `need` bytes; the stream waits first,
-// as an earlier call's kernels may still use what is freed
-static int holders_ws(sdcas_ctx* c, size_t need, hipStream_t st) {
-  if (need <= c->ch_ws.cap) return SDCAS_OK;
-  hipError_t e = c->scratch_sync();
-  if (!e) e = hipStreamSynchronize(st);
-  if (!e) e = c->ch_ws.ensure(need);
-  return e ? c->hip_fail(e, "chunk holders workspace") : SDCAS_OK;
 }
 
 // the remove's arguments: limits, the arrays it needs, old and removed against new
@@ -3034,26 +3111,9 @@ int sdcas_dev_chunk_holders_match(sdcas_ctx* c, const uint64_t* d_idx_keys, cons
                                   const uint64_t* d_keys, const uint8_t* d_digests32, const uint8_t* d_valid,
                                   size_t m, int64_t* d_out_pos, uint64_t* d_out_value, uint32_t* d_out_holders,
                                   uint64_t* d_counts, void* stream) {
-  if (!c) return SDCAS_E_INVALID;
-  if (int rc = index_view_args(c, "dev_chunk_holders_match", d_idx_keys, d_idx_digests32, d_idx_dir, n, bits)) return rc;
-  if (int rc = index_batch_args(c, "dev_chunk_holders_match", d_keys, d_digests32, m)) return rc;
-  if ((((uintptr_t)d_idx_digests32 | (uintptr_t)d_digests32) & 15) ||
-      (((uintptr_t)d_idx_keys | (uintptr_t)d_idx_values | (uintptr_t)d_keys | (uintptr_t)d_out_pos |
-        (uintptr_t)d_out_value | (uintptr_t)d_counts) & 7) ||
-      (((uintptr_t)d_idx_dir | (uintptr_t)d_out_holders) & 3))
-    return c->fail(SDCAS_E_INVALID, "dev_chunk_holders_match: an array is misaligned (digests 16 B, directory and holders 4 B, others 8 B)");
-  DevCall call(c, stream);
-  if (call.rc) return call.rc;
-  hipError_t e;
-  if (m == 0) {
-    if (d_counts && (e = hipMemsetAsync(d_counts, 0, kIndexMatchCounts * sizeof(uint64_t), call.st)))
-      return c->hip_fail(e, "counts");
-    return SDCAS_OK;
-  }
-  const IndexView v{d_idx_keys, d_idx_digests32, d_idx_values, d_idx_dir, (uint32_t)n, bits};
-  e = holders_match(v, d_keys, d_digests32, d_valid, (uint32_t)m, d_out_pos, d_out_value, d_out_holders,
-                    (unsigned long long*)d_counts, call.st);
-  return e ? c->hip_fail(e, "dev_chunk_holders_match") : SDCAS_OK;
+  return index_dev_match(c, kTriples, "dev_chunk_holders_match", d_idx_keys, d_idx_digests32, d_idx_values, d_idx_dir,
+                         n, bits, d_keys, d_digests32, d_valid, m, d_out_pos, d_out_value, d_out_holders, d_counts,
+                         stream);
 }
 
 int sdcas_chunk_holders_match(sdcas_ctx* c, const uint64_t* idx_keys, const uint8_t* idx_digests32,
@@ -3061,46 +3121,8 @@ int sdcas_chunk_holders_match(sdcas_ctx* c, const uint64_t* idx_keys, const uint
                               const uint64_t* keys, const uint8_t* digests32, const uint8_t* valid, size_t m,
                               int64_t* out_pos, uint64_t* out_value, uint32_t* out_holders,
                               sdcas_index_match_counts* out_counts) {
-  if (!c) return SDCAS_E_INVALID;
-  if (int rc = index_view_args(c, "chunk_holders_match", idx_keys, idx_digests32, idx_dir, n, bits)) return rc;
-  if (int rc = index_batch_args(c, "chunk_holders_match", keys, digests32, m)) return rc;
-  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
-  if (m == 0) return SDCAS_OK;
-  DevCall call(c, nullptr);
-  if (call.rc) return call.rc;
-  hipError_t e;
-  hipStream_t st = call.st;
-  const size_t dir_bytes = n ? 4 * (size_t)index_dir_slots(bits) : 0;
-  Parts p;
-  const size_t o_ik = p.take(8 * n), o_id = p.take(32 * n), o_iv = p.take(8 * n), o_dir = p.take(dir_bytes),
-               o_k = p.take(8 * m), o_d = p.take(32 * m), o_v = p.take(m), o_pos = p.take(8 * m),
-               o_val = p.take(8 * m), o_h = p.take(4 * m), o_cts = p.take(8 * kIndexMatchCounts);
-  if (int rc = index_io(c, p.o, st)) return rc;
-  uint8_t* io = c->ci_io.p;
-  if ((n && ((e = hipMemcpyAsync(io + o_ik, idx_keys, 8 * n, hipMemcpyHostToDevice, st)) ||
-             (e = hipMemcpyAsync(io + o_id, idx_digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
-             (idx_values && (e = hipMemcpyAsync(io + o_iv, idx_values, 8 * n, hipMemcpyHostToDevice, st))) ||
-             (e = hipMemcpyAsync(io + o_dir, idx_dir, dir_bytes, hipMemcpyHostToDevice, st)))) ||
-      (e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
-      (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
-      (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))
-    return c->hip_fail(e, "chunk_holders_match H2D");
-  const IndexView v{reinterpret_cast<const uint64_t*>(io + o_ik), io + o_id,
-                    idx_values ? reinterpret_cast<const uint64_t*>(io + o_iv) : nullptr,
-                    reinterpret_cast<const uint32_t*>(io + o_dir), (uint32_t)n, bits};
-  if ((e = holders_match(v, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d, valid ? io + o_v : nullptr,
-                         (uint32_t)m, out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr,
-                         out_value ? reinterpret_cast<uint64_t*>(io + o_val) : nullptr,
-                         out_holders ? reinterpret_cast<uint32_t*>(io + o_h) : nullptr,
-                         out_counts ? reinterpret_cast<unsigned long long*>(io + o_cts) : nullptr, st)))
-    return c->hip_fail(e, "chunk_holders_match");
-  if ((out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
-      (out_value && (e = hipMemcpyAsync(out_value, io + o_val, 8 * m, hipMemcpyDeviceToHost, st))) ||
-      (out_holders && (e = hipMemcpyAsync(out_holders, io + o_h, 4 * m, hipMemcpyDeviceToHost, st))) ||
-      (out_counts && (e = hipMemcpyAsync(out_counts, io + o_cts, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, "chunk_holders_match D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_holders_match sync");
-  return SDCAS_OK;
+  return index_host_match(c, kTriples, "chunk_holders_match", idx_keys, idx_digests32, idx_values, idx_dir, n, bits,
+                          keys, digests32, valid, m, out_pos, out_value, out_holders, out_counts);
 }
 
 int sdcas_dev_chunk_holders_add(sdcas_ctx* c, const uint64_t* d_old_keys, const uint8_t* d_old_digests32,
@@ -3110,24 +3132,9 @@ int sdcas_dev_chunk_holders_add(sdcas_ctx* c, const uint64_t* d_old_keys, const 
                                 uint8_t* d_new_digests32, uint64_t* d_new_values, uint32_t* d_new_dir,
                                 uint32_t bits_new, int64_t* d_out_pos, uint8_t* d_out_flags, uint64_t* d_counts,
                                 void* stream) {
-  if (!c) return SDCAS_E_INVALID;
-  if (int rc = index_add_args(c, "dev_chunk_holders_add", d_old_keys, d_old_digests32, d_old_values, d_old_dir, n_old,
-                              bits_old, d_keys, d_digests32, m, d_new_keys, d_new_digests32, d_new_values, d_new_dir,
-                              bits_new))
-    return rc;
-  if ((((uintptr_t)d_old_digests32 | (uintptr_t)d_digests32 | (uintptr_t)d_new_digests32) & 15) ||
-      (((uintptr_t)d_old_keys | (uintptr_t)d_old_values | (uintptr_t)d_keys | (uintptr_t)d_values |
-        (uintptr_t)d_new_keys | (uintptr_t)d_new_values | (uintptr_t)d_out_pos | (uintptr_t)d_counts) & 7) ||
-      (((uintptr_t)d_old_dir | (uintptr_t)d_new_dir) & 3))
-    return c->fail(SDCAS_E_INVALID, "dev_chunk_holders_add: an array is misaligned (digests 16 B, directories 4 B, others 8 B)");
-  DevCall call(c, stream);
-  if (call.rc) return call.rc;
-  if (int rc = holders_ws(c, (size_t)holders_add_layout(m).bytes, call.st)) return rc;
-  const IndexView old{d_old_keys, d_old_digests32, d_old_values, d_old_dir, (uint32_t)n_old, bits_old};
-  const IndexOut out{d_new_keys, d_new_digests32, d_new_values, d_new_dir, bits_new};
-  hipError_t e = holders_add(c->ch_ws.p, old, d_keys, d_digests32, d_values, d_valid, (uint32_t)m, out, d_out_pos,
-                             d_out_flags, (unsigned long long*)d_counts, call.st);
-  return e ? c->hip_fail(e, "dev_chunk_holders_add") : SDCAS_OK;
+  return index_dev_add(c, kTriples, "dev_chunk_holders_add", d_old_keys, d_old_digests32, d_old_values, d_old_dir,
+                       n_old, bits_old, d_keys, d_digests32, d_values, d_valid, m, d_new_keys, d_new_digests32,
+                       d_new_values, d_new_dir, bits_new, d_out_pos, d_out_flags, d_counts, stream);
 }
 
 int sdcas_chunk_holders_add(sdcas_ctx* c, const uint64_t* old_keys, const uint8_t* old_digests32,
@@ -3136,60 +3143,9 @@ int sdcas_chunk_holders_add(sdcas_ctx* c, const uint64_t* old_keys, const uint8_
                             const uint8_t* valid, size_t m, uint64_t* new_keys, uint8_t* new_digests32,
                             uint64_t* new_values, uint32_t* new_dir, uint32_t bits_new, int64_t* out_pos,
                             uint8_t* out_flags, sdcas_index_add_counts* out_counts) {
-  if (!c) return SDCAS_E_INVALID;
-  if (int rc = index_add_args(c, "chunk_holders_add", old_keys, old_digests32, old_values, old_dir, n_old, bits_old,
-                              keys, digests32, m, new_keys, new_digests32, new_values, new_dir, bits_new))
-    return rc;
-  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
-  DevCall call(c, nullptr);
-  if (call.rc) return call.rc;
-  hipError_t e;
-  hipStream_t st = call.st;
-  const size_t n = n_old, cap = n_old + m;
-  const size_t odir_bytes = n ? 4 * (size_t)index_dir_slots(bits_old) : 0, ndir_bytes = 4 * (size_t)index_dir_slots(bits_new);
-  Parts p;
-  const size_t o_ok = p.take(8 * n), o_od = p.take(32 * n), o_ov = p.take(8 * n), o_odir = p.take(odir_bytes),
-               o_k = p.take(8 * m), o_d = p.take(32 * m), o_val = p.take(8 * m), o_v = p.take(m),
-               o_nk = p.take(8 * cap), o_nd = p.take(32 * cap), o_nv = p.take(8 * cap), o_ndir = p.take(ndir_bytes),
-               o_pos = p.take(8 * m), o_fl = p.take(m), o_cts = p.take(8 * kIndexAddCounts);
-  if (int rc = index_io(c, p.o, st)) return rc;
-  if (int rc = holders_ws(c, (size_t)holders_add_layout(m).bytes, st)) return rc;
-  uint8_t* io = c->ci_io.p;
-  if ((n && ((e = hipMemcpyAsync(io + o_ok, old_keys, 8 * n, hipMemcpyHostToDevice, st)) ||
-             (e = hipMemcpyAsync(io + o_od, old_digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
-             (old_values && (e = hipMemcpyAsync(io + o_ov, old_values, 8 * n, hipMemcpyHostToDevice, st))) ||
-             (e = hipMemcpyAsync(io + o_odir, old_dir, odir_bytes, hipMemcpyHostToDevice, st)))) ||
-      (m && ((e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
-             (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
-             (values && (e = hipMemcpyAsync(io + o_val, values, 8 * m, hipMemcpyHostToDevice, st))) ||
-             (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))))
-    return c->hip_fail(e, "chunk_holders_add H2D");
-  const IndexView old{reinterpret_cast<const uint64_t*>(io + o_ok), io + o_od,
-                      old_values ? reinterpret_cast<const uint64_t*>(io + o_ov) : nullptr,
-                      reinterpret_cast<const uint32_t*>(io + o_odir), (uint32_t)n, bits_old};
-  const IndexOut out{reinterpret_cast<uint64_t*>(io + o_nk), io + o_nd, reinterpret_cast<uint64_t*>(io + o_nv),
-                     reinterpret_cast<uint32_t*>(io + o_ndir), bits_new};
-  if ((e = holders_add(c->ch_ws.p, old, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d,
-                       values ? reinterpret_cast<const uint64_t*>(io + o_val) : nullptr, valid ? io + o_v : nullptr,
-                       (uint32_t)m, out, out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr,
-                       out_flags ? io + o_fl : nullptr, reinterpret_cast<unsigned long long*>(io + o_cts), st)))
-    return c->hip_fail(e, "chunk_holders_add");
-  // the counts down first: they say how many entries of the new arrays follow
-  sdcas_index_add_counts cts;
-  if ((e = hipMemcpyAsync(&cts, io + o_cts, sizeof cts, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
-    return c->hip_fail(e, "chunk_holders_add counts");
-  const size_t nn = (size_t)cts.entries_new;
-  if (nn > cap) return c->fail(SDCAS_E_HIP, "chunk_holders_add: counts out of range");
-  if ((nn && ((e = hipMemcpyAsync(new_keys, io + o_nk, 8 * nn, hipMemcpyDeviceToHost, st)) ||
-              (e = hipMemcpyAsync(new_digests32, io + o_nd, 32 * nn, hipMemcpyDeviceToHost, st)) ||
-              (e = hipMemcpyAsync(new_values, io + o_nv, 8 * nn, hipMemcpyDeviceToHost, st)))) ||
-      (e = hipMemcpyAsync(new_dir, io + o_ndir, ndir_bytes, hipMemcpyDeviceToHost, st)) ||
-      (m && out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
-      (m && out_flags && (e = hipMemcpyAsync(out_flags, io + o_fl, m, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, "chunk_holders_add D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_holders_add sync");
-  if (out_counts) *out_counts = cts;
-  return SDCAS_OK;
+  return index_host_add(c, kTriples, "chunk_holders_add", old_keys, old_digests32, old_values, old_dir, n_old,
+                        bits_old, keys, digests32, values, valid, m, new_keys, new_digests32, new_values, new_dir,
+                        bits_new, out_pos, out_flags, out_counts);
 }
 
 int sdcas_dev_chunk_holders_remove(sdcas_ctx* c, const uint64_t* d_old_keys, const uint8_t* d_old_digests32,
@@ -3202,10 +3158,9 @@ int sdcas_dev_chunk_holders_remove(sdcas_ctx* c, const uint64_t* d_old_keys, con
                                    n_old, bits_old, d_removed, r, d_new_keys, d_new_digests32, d_new_values, d_new_dir,
                                    bits_new))
     return rc;
-  if ((((uintptr_t)d_old_digests32 | (uintptr_t)d_new_digests32) & 15) ||
-      (((uintptr_t)d_old_keys | (uintptr_t)d_old_values | (uintptr_t)d_removed | (uintptr_t)d_new_keys |
-        (uintptr_t)d_new_values | (uintptr_t)d_counts) & 7) ||
-      (((uintptr_t)d_old_dir | (uintptr_t)d_new_dir) & 3))
+  if (index_misaligned({d_old_digests32, d_new_digests32},
+                       {d_old_keys, d_old_values, d_removed, d_new_keys, d_new_values, d_counts},
+                       {d_old_dir, d_new_dir}))
     return c->fail(SDCAS_E_INVALID, "dev_chunk_holders_remove: an array is misaligned (digests 16 B, directories 4 B, others 8 B)");
   DevCall call(c, stream);
   if (call.rc) return call.rc;
@@ -3222,9 +3177,10 @@ int sdcas_chunk_holders_remove(sdcas_ctx* c, const uint64_t* old_keys, const uin
                                uint8_t* new_digests32, uint64_t* new_values, uint32_t* new_dir, uint32_t bits_new,
                                sdcas_holders_remove_counts* out_counts) {
   static_assert(sizeof(sdcas_holders_remove_counts) == kHoldersRemoveCounts * sizeof(uint64_t), "four u64 counts");
+  const char* who = "chunk_holders_remove";
   if (!c) return SDCAS_E_INVALID;
-  if (int rc = holders_remove_args(c, "chunk_holders_remove", old_keys, old_digests32, old_values, old_dir, n_old,
-                                   bits_old, removed, r, new_keys, new_digests32, new_values, new_dir, bits_new))
+  if (int rc = holders_remove_args(c, who, old_keys, old_digests32, old_values, old_dir, n_old, bits_old, removed, r,
+                                   new_keys, new_digests32, new_values, new_dir, bits_new))
     return rc;
   for (size_t i = 1; i < r; ++i)
     if (removed[i - 1] >= removed[i])
@@ -3235,40 +3191,26 @@ int sdcas_chunk_holders_remove(sdcas_ctx* c, const uint64_t* old_keys, const uin
   hipError_t e;
   hipStream_t st = call.st;
   const size_t n = n_old;
-  const size_t odir_bytes = n ? 4 * (size_t)index_dir_slots(bits_old) : 0, ndir_bytes = 4 * (size_t)index_dir_slots(bits_new);
   Parts p;
-  const size_t o_ok = p.take(8 * n), o_od = p.take(32 * n), o_ov = p.take(8 * n), o_odir = p.take(odir_bytes),
-               o_r = p.take(8 * r), o_nk = p.take(8 * n), o_nd = p.take(32 * n), o_nv = p.take(8 * n),
-               o_ndir = p.take(ndir_bytes), o_cts = p.take(8 * kHoldersRemoveCounts);
+  const IndexParts op = index_parts(p, n, index_old_dir_bytes(n, bits_old));
+  const size_t o_r = p.take(8 * r);
+  const IndexParts np = index_parts(p, n, 4 * (size_t)index_dir_slots(bits_new));
+  const size_t o_cts = p.take(8 * kHoldersRemoveCounts);
   if (int rc = index_io(c, p.o, st)) return rc;
   if (int rc = holders_ws(c, (size_t)holders_remove_layout(n).bytes, st)) return rc;
   uint8_t* io = c->ci_io.p;
-  if ((n && ((e = hipMemcpyAsync(io + o_ok, old_keys, 8 * n, hipMemcpyHostToDevice, st)) ||
-             (e = hipMemcpyAsync(io + o_od, old_digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
-             (old_values && (e = hipMemcpyAsync(io + o_ov, old_values, 8 * n, hipMemcpyHostToDevice, st))) ||
-             (e = hipMemcpyAsync(io + o_odir, old_dir, odir_bytes, hipMemcpyHostToDevice, st)))) ||
+  IndexView old{};
+  if ((e = index_stage(io, op, old_keys, old_digests32, old_values, old_dir, n, bits_old, st, &old)) ||
       (r && (e = hipMemcpyAsync(io + o_r, removed, 8 * r, hipMemcpyHostToDevice, st))))
-    return c->hip_fail(e, "chunk_holders_remove H2D");
-  const IndexView old{reinterpret_cast<const uint64_t*>(io + o_ok), io + o_od,
-                      old_values ? reinterpret_cast<const uint64_t*>(io + o_ov) : nullptr,
-                      reinterpret_cast<const uint32_t*>(io + o_odir), (uint32_t)n, bits_old};
-  const IndexOut out{reinterpret_cast<uint64_t*>(io + o_nk), io + o_nd, reinterpret_cast<uint64_t*>(io + o_nv),
-                     reinterpret_cast<uint32_t*>(io + o_ndir), bits_new};
-  if ((e = holders_remove(c->ch_ws.p, old, reinterpret_cast<const uint64_t*>(io + o_r), (uint32_t)r, out,
-                          reinterpret_cast<unsigned long long*>(io + o_cts), st)))
-    return c->hip_fail(e, "chunk_holders_remove");
-  // the counts down first: they say how many entries of the new arrays follow
+    return index_hip_fail(c, e, who, " H2D");
+  if ((e = holders_remove(c->ch_ws.p, old, reinterpret_cast<const uint64_t*>(io + o_r), (uint32_t)r,
+                          index_out_parts(io, np, bits_new), reinterpret_cast<unsigned long long*>(io + o_cts), st)))
+    return index_hip_fail(c, e, who, "");
   sdcas_holders_remove_counts cts;
-  if ((e = hipMemcpyAsync(&cts, io + o_cts, sizeof cts, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
-    return c->hip_fail(e, "chunk_holders_remove counts");
-  const size_t nn = (size_t)cts.entries_new;
-  if (nn > n) return c->fail(SDCAS_E_HIP, "chunk_holders_remove: counts out of range");
-  if ((nn && ((e = hipMemcpyAsync(new_keys, io + o_nk, 8 * nn, hipMemcpyDeviceToHost, st)) ||
-              (e = hipMemcpyAsync(new_digests32, io + o_nd, 32 * nn, hipMemcpyDeviceToHost, st)) ||
-              (e = hipMemcpyAsync(new_values, io + o_nv, 8 * nn, hipMemcpyDeviceToHost, st)))) ||
-      (e = hipMemcpyAsync(new_dir, io + o_ndir, ndir_bytes, hipMemcpyDeviceToHost, st)))
-    return c->hip_fail(e, "chunk_holders_remove D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_holders_remove sync");
+  if (int rc = index_fetch(c, who, io, np, o_cts, &cts, sizeof cts, &cts.entries_new, n, new_keys, new_digests32,
+                           new_values, new_dir, st))
+    return rc;
+  if ((e = hipStreamSynchronize(st))) return index_hip_fail(c, e, who, " sync");
   if (out_counts) *out_counts = cts;
   return SDCAS_OK;
 }

@@ -732,14 +732,21 @@ class Engine:
         (SDCAS_OK, None) for an index as include/sdcas.h defines it,
         (SDCAS_E_INVALID, the first entry or directory slot that is wrong),
         (SDCAS_E_CAPACITY, None) beyond the limits"""
+        return Engine._index_check(N.load().sdcas_chunk_index_check, "chunk_index_check", keys, digests, dir, bits)
+
+    @staticmethod
+    def _index_check(fn, who, keys, digests, dir, bits, *values):
+        """the two checks' body: library function `fn`, named `who` in
+        messages; `values` is the holders check's one extra array (or None)"""
         keys, digests, dir = _arr(keys, np.uint64), _arr(digests, np.uint8), _arr(dir, np.uint32)
+        values = [None if v is None else _arr(v, np.uint64) for v in values]
         n = keys.size
-        if digests.size != 32 * n:
-            raise ValueError(f"chunk_index_check: {n} keys, {digests.size} digest bytes")
+        if digests.size != 32 * n or any(v is not None and v.size != n for v in values):
+            raise ValueError(f"{who}: {n} keys, {digests.size} digest bytes")
         if int(bits) <= N.SDCAS_INDEX_MAX_BITS and dir.size != (1 << int(bits)) + 1:
-            raise ValueError(f"chunk_index_check: {dir.size} directory slots for {int(bits)} bits")
+            raise ValueError(f"{who}: {dir.size} directory slots for {int(bits)} bits")
         bad = ctypes.c_uint64(0)
-        rc = N.load().sdcas_chunk_index_check(_ptr(keys), _ptr(digests), _ptr(dir), n, int(bits), ctypes.byref(bad))
+        rc = fn(_ptr(keys), _ptr(digests), *map(_ptr, values), _ptr(dir), n, int(bits), ctypes.byref(bad))
         return rc, int(bad.value) if rc == N.SDCAS_E_INVALID else None
 
     @staticmethod
@@ -788,26 +795,29 @@ class Engine:
         -> (new index tuple, trimmed to entries_new, pos int64[m], flags
         uint8[m]: SDCAS_INDEX_HIT / ADDED / SKIPPED or 0, counts: dict of
         sdcas_index_add_counts' six fields)"""
-        ik, idg, iv, idir, bits = self._index_arrays(index, "chunk_index_add")
-        keys, digests, va = self._index_batch(keys, digests, valid, "chunk_index_add")
+        return self._index_add(self.L.sdcas_chunk_index_add, "chunk_index_add", index, keys, digests, values, valid,
+                               bits_new)
+
+    def _index_add(self, fn, who, index, keys, digests, values, valid, bits_new):
+        """the two host adds' body: library function `fn`, named `who` in messages"""
+        ik, idg, iv, idir, bits = self._index_arrays(index, who)
+        keys, digests, va = self._index_batch(keys, digests, valid, who)
         m, n = keys.size, ik.size
         values = None if values is None else _arr(values, np.uint64)
         if values is not None and values.size != m:
-            raise ValueError(f"chunk_index_add: {m} keys, {values.size} values")
+            raise ValueError(f"{who}: {m} keys, {values.size} values")
         if bits_new is None:
             bits_new = self.chunk_index_dir_bits(n + m)
         bits_new = int(bits_new)
         if not 0 <= bits_new <= N.SDCAS_INDEX_MAX_BITS:
-            raise N.SdcasError(N.SDCAS_E_CAPACITY, f"chunk_index_add: a directory of {bits_new} bits")
+            raise N.SdcasError(N.SDCAS_E_CAPACITY, f"{who}: a directory of {bits_new} bits")
         nk, nd, nv = np.zeros(n + m, np.uint64), np.zeros((n + m, 32), np.uint8), np.zeros(n + m, np.uint64)
         ndir = np.zeros((1 << bits_new) + 1, np.uint32)
         pos, flags = np.zeros(m, np.int64), np.zeros(m, np.uint8)
         counts = N.IndexAddCounts()
-        self._check(self.L.sdcas_chunk_index_add(self.ctx, _ptr(ik), _ptr(idg), _ptr(iv), _ptr(idir), n, bits,
-                                                 _ptr(keys), _ptr(digests), _ptr(values), _ptr(va), m,
-                                                 nk.ctypes.data, nd.ctypes.data, nv.ctypes.data, ndir.ctypes.data,
-                                                 bits_new, _ptr(pos), _ptr(flags), ctypes.byref(counts)),
-                    "sdcas_chunk_index_add")
+        self._check(fn(self.ctx, _ptr(ik), _ptr(idg), _ptr(iv), _ptr(idir), n, bits, _ptr(keys), _ptr(digests),
+                       _ptr(values), _ptr(va), m, nk.ctypes.data, nd.ctypes.data, nv.ctypes.data, ndir.ctypes.data,
+                       bits_new, _ptr(pos), _ptr(flags), ctypes.byref(counts)), "sdcas_" + who)
         e = int(counts.entries_new)
         return (nk[:e].copy(), nd[:e].copy(), nv[:e].copy(), ndir, bits_new), pos, flags, counts.as_dict()
 
@@ -817,17 +827,8 @@ class Engine:
         """sdcas_chunk_holders_check (no GPU) over host arrays -> (rc,
         first_bad) as chunk_index_check, in the order of the triple (key,
         digest, value); values None: all 0"""
-        keys, digests, dir = _arr(keys, np.uint64), _arr(digests, np.uint8), _arr(dir, np.uint32)
-        values = None if values is None else _arr(values, np.uint64)
-        n = keys.size
-        if digests.size != 32 * n or (values is not None and values.size != n):
-            raise ValueError(f"chunk_holders_check: {n} keys, {digests.size} digest bytes")
-        if int(bits) <= N.SDCAS_INDEX_MAX_BITS and dir.size != (1 << int(bits)) + 1:
-            raise ValueError(f"chunk_holders_check: {dir.size} directory slots for {int(bits)} bits")
-        bad = ctypes.c_uint64(0)
-        rc = N.load().sdcas_chunk_holders_check(_ptr(keys), _ptr(digests), _ptr(values), _ptr(dir), n, int(bits),
-                                                ctypes.byref(bad))
-        return rc, int(bad.value) if rc == N.SDCAS_E_INVALID else None
+        return Engine._index_check(N.load().sdcas_chunk_holders_check, "chunk_holders_check", keys, digests, dir, bits,
+                                   values)
 
     def chunk_holders_match(self, index, keys, digests, valid=None):
         """sdcas_chunk_holders_match over host arrays; index as for
@@ -850,28 +851,8 @@ class Engine:
         of the index's triples and the batch's valid (key, digest, value)
         triples -> (new index tuple, trimmed to entries_new, pos int64[m],
         flags uint8[m], counts), as chunk_index_add but read per triple"""
-        ik, idg, iv, idir, bits = self._index_arrays(index, "chunk_holders_add")
-        keys, digests, va = self._index_batch(keys, digests, valid, "chunk_holders_add")
-        m, n = keys.size, ik.size
-        values = None if values is None else _arr(values, np.uint64)
-        if values is not None and values.size != m:
-            raise ValueError(f"chunk_holders_add: {m} keys, {values.size} values")
-        if bits_new is None:
-            bits_new = self.chunk_index_dir_bits(n + m)
-        bits_new = int(bits_new)
-        if not 0 <= bits_new <= N.SDCAS_INDEX_MAX_BITS:
-            raise N.SdcasError(N.SDCAS_E_CAPACITY, f"chunk_holders_add: a directory of {bits_new} bits")
-        nk, nd, nv = np.zeros(n + m, np.uint64), np.zeros((n + m, 32), np.uint8), np.zeros(n + m, np.uint64)
-        ndir = np.zeros((1 << bits_new) + 1, np.uint32)
-        pos, flags = np.zeros(m, np.int64), np.zeros(m, np.uint8)
-        counts = N.IndexAddCounts()
-        self._check(self.L.sdcas_chunk_holders_add(self.ctx, _ptr(ik), _ptr(idg), _ptr(iv), _ptr(idir), n, bits,
-                                                   _ptr(keys), _ptr(digests), _ptr(values), _ptr(va), m,
-                                                   nk.ctypes.data, nd.ctypes.data, nv.ctypes.data, ndir.ctypes.data,
-                                                   bits_new, _ptr(pos), _ptr(flags), ctypes.byref(counts)),
-                    "sdcas_chunk_holders_add")
-        e = int(counts.entries_new)
-        return (nk[:e].copy(), nd[:e].copy(), nv[:e].copy(), ndir, bits_new), pos, flags, counts.as_dict()
+        return self._index_add(self.L.sdcas_chunk_holders_add, "chunk_holders_add", index, keys, digests, values, valid,
+                               bits_new)
 
     def chunk_holders_remove(self, index, removed, bits_new=None):
         """sdcas_chunk_holders_remove over host arrays: the index's entries
@@ -1234,22 +1215,43 @@ class ChunkIndex:
         return (self._upload(keys, np.int64), self._upload(digests, np.uint8),
                 None if va is None else self._upload(va, np.uint8))
 
+    # what a subclass names: the kind in `load`'s messages, its check (no GPU)
+    # and the engine's device add
+    _noun = "chunk index"
+
+    @staticmethod
+    def _checker(keys, digests, values, dir, bits):
+        return Engine.chunk_index_check(keys, digests, dir, bits)
+
+    def _dev_add(self, *args, **kw):
+        return self.engine.dev_chunk_index_add(*args, **kw)
+
     # -- match ----------------------------------------------------------------------
-    def _match_dev(self, d_keys, d_digests, d_valid):
-        """device tensors in, device tensors out: (pos int64[m], value
-        int64[m]: the uint64's bits, counts dict — reading them is the wait)"""
+    def _match_call(self, d_keys, d_digests, d_valid, with_holders):
+        """the outputs allocated, the engine's device match for the kind of
+        index, the counts read -> (pos, value, holders int32[m] or None, counts)"""
         import torch
         m = d_keys.numel()
         p = lambda t: t.data_ptr() if t is not None and t.numel() else 0
         with torch.cuda.stream(self.stream):
             pos = torch.empty(m, dtype=torch.int64, device=self.device)
             value = torch.empty(m, dtype=torch.int64, device=self.device)
+            holders = torch.empty(m, dtype=torch.int32, device=self.device) if with_holders else None
             counts = torch.zeros(4, dtype=torch.int64, device=self.device)
-            self.engine.dev_chunk_index_match(p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n,
-                                              self.bits, p(d_keys), p(d_digests), p(d_valid), m, p(pos), p(value),
-                                              counts.data_ptr(), stream=self.stream.cuda_stream)
+            args = (p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n, self.bits, p(d_keys),
+                    p(d_digests), p(d_valid), m, p(pos), p(value))
+            if with_holders:
+                self.engine.dev_chunk_holders_match(*args, p(holders), counts.data_ptr(), stream=self.stream.cuda_stream)
+            else:
+                self.engine.dev_chunk_index_match(*args, counts.data_ptr(), stream=self.stream.cuda_stream)
             c = [int(v) for v in counts.cpu()]
-        return pos, value, dict(zip((name for name, _ in N.IndexMatchCounts._fields_), c))
+        return pos, value, holders, dict(zip((name for name, _ in N.IndexMatchCounts._fields_), c))
+
+    def _match_dev(self, d_keys, d_digests, d_valid):
+        """device tensors in, device tensors out: (pos int64[m], value
+        int64[m]: the uint64's bits, counts dict — reading them is the wait)"""
+        pos, value, _, counts = self._match_call(d_keys, d_digests, d_valid, False)
+        return pos, value, counts
 
     def match(self, keys, digests, valid=None):
         """only the batch goes up -> (pos int64[m], value uint64[m], counts),
@@ -1282,14 +1284,14 @@ class ChunkIndex:
             pos = torch.empty(m, dtype=torch.int64, device=self.device)
             flags = torch.empty(m, dtype=torch.uint8, device=self.device)
             counts = torch.zeros(6, dtype=torch.int64, device=self.device)
-            self.engine.dev_chunk_index_add(p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n,
-                                            self.bits, p(d_keys), p(d_digests), p(d_values), p(d_valid), m, p(keys),
-                                            p(digests), p(values), dir.data_ptr(), bits_new, p(pos), p(flags),
-                                            counts.data_ptr(), stream=self.stream.cuda_stream)
+            self._dev_add(p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n, self.bits, p(d_keys),
+                          p(d_digests), p(d_values), p(d_valid), m, p(keys), p(digests), p(values), dir.data_ptr(),
+                          bits_new, p(pos), p(flags), counts.data_ptr(), stream=self.stream.cuda_stream)
             c = [int(v) for v in counts.cpu()]
             n_new = c[5]
             if not self.n <= n_new <= cap:
-                raise N.SdcasError(N.SDCAS_E_HIP, f"ChunkIndex.add: {n_new} entries from {self.n} and a batch of {m}")
+                raise N.SdcasError(N.SDCAS_E_HIP,
+                                   f"{type(self).__name__}.add: {n_new} entries from {self.n} and a batch of {m}")
             self.keys, self.digests, self.values, self.dir = keys[:n_new], digests[:32 * n_new], values[:n_new], dir
             self.n, self.bits = n_new, bits_new
         return pos, flags, dict(zip((name for name, _ in N.IndexAddCounts._fields_), c))
@@ -1323,8 +1325,10 @@ class ChunkIndex:
 
     @classmethod
     def load(cls, engine, path, device=None):
-        """an index saved by `save`: checked (sdcas_chunk_index_check) before
-        anything goes to the device; ValueError when it is not an index"""
+        """an index saved by `save`: checked (the class's check:
+        sdcas_chunk_index_check, for ChunkHolders sdcas_chunk_holders_check)
+        before anything goes to the device; ValueError when it is not an index
+        of the class's kind"""
         import torch
         import zipfile
         try:  # the archive's own checksums catch a byte that changed on disk
@@ -1333,14 +1337,14 @@ class ChunkIndex:
                                                     z["values"].astype(np.uint64), z["dir"].astype(np.uint32),
                                                     int(z["bits"]))
         except (zipfile.BadZipFile, KeyError, EOFError, OSError, ValueError) as e:
-            raise ValueError(f"{path}: not a saved chunk index ({e})") from e
+            raise ValueError(f"{path}: not a saved {cls._noun} ({e})") from e
         n = keys.size
         if digests.size != 32 * n or values.size != n or not 0 <= bits <= N.SDCAS_INDEX_MAX_BITS or \
                 dir.size != (1 << bits) + 1:
             raise ValueError(f"{path}: the arrays' sizes do not make an index")
-        rc, bad = Engine.chunk_index_check(keys, digests, dir, bits)
+        rc, bad = cls._checker(keys, digests, values, dir, bits)
         if rc != N.SDCAS_OK:
-            raise ValueError(f"{path}: not a chunk index (sdcas error {rc}" +
+            raise ValueError(f"{path}: not a {cls._noun} (sdcas error {rc}" +
                              (f", first at entry or slot {bad})" if bad is not None else ")"))
         ix = cls(engine, device)
         with torch.cuda.stream(ix.stream):
@@ -1358,28 +1362,24 @@ class ChunkHolders(ChunkIndex):
     batch's unseen triples; `remove(file_ids)` streams the index through once
     and leaves, byte for byte, the index built from the files that remain.
 
-    The tensors, the stream and the `_upload` / `_match_dev` / `_add_dev`
-    contract are ChunkIndex's, so Engine.similar_files_indexed takes either
-    kind; with this one the origin of a stored chunk is its lowest holder."""
+    The tensors, the stream, `load` and the `_upload` / `_match_dev` /
+    `_add_dev` contract are ChunkIndex's (here `_add_dev` merges the batch's
+    unseen (key, digest, value) triples), so Engine.similar_files_indexed takes
+    either kind; with this one the origin of a stored chunk is its lowest
+    holder."""
+
+    _noun = "holders index"
+    _checker = staticmethod(Engine.chunk_holders_check)
+
+    def _dev_add(self, *args, **kw):
+        return self.engine.dev_chunk_holders_add(*args, **kw)
 
     # -- match ----------------------------------------------------------------------
     def _match_holders_dev(self, d_keys, d_digests, d_valid):
         """device tensors in, device tensors out: (pos int64[m], value
         int64[m]: the uint64's bits, holders int32[m], counts dict — reading
         them is the wait)"""
-        import torch
-        m = d_keys.numel()
-        p = lambda t: t.data_ptr() if t is not None and t.numel() else 0
-        with torch.cuda.stream(self.stream):
-            pos = torch.empty(m, dtype=torch.int64, device=self.device)
-            value = torch.empty(m, dtype=torch.int64, device=self.device)
-            holders = torch.empty(m, dtype=torch.int32, device=self.device)
-            counts = torch.zeros(4, dtype=torch.int64, device=self.device)
-            self.engine.dev_chunk_holders_match(p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n,
-                                                self.bits, p(d_keys), p(d_digests), p(d_valid), m, p(pos), p(value),
-                                                p(holders), counts.data_ptr(), stream=self.stream.cuda_stream)
-            c = [int(v) for v in counts.cpu()]
-        return pos, value, holders, dict(zip((name for name, _ in N.IndexMatchCounts._fields_), c))
+        return self._match_call(d_keys, d_digests, d_valid, True)
 
     def _match_dev(self, d_keys, d_digests, d_valid):
         """ChunkIndex._match_dev's triple: pos is the pair's first entry, value
@@ -1396,39 +1396,6 @@ class ChunkHolders(ChunkIndex):
             pos, value, holders, counts = self._match_holders_dev(d_keys, d_dig, d_valid)
             return (pos.cpu().numpy(), value.cpu().numpy().view(np.uint64), holders.cpu().numpy().view(np.uint32),
                     counts)
-
-    # -- add ------------------------------------------------------------------------
-    def _add_dev(self, d_keys, d_digests, d_values, d_valid):
-        """ChunkIndex._add_dev with the holders add: the batch's unseen
-        (key, digest, value) triples merged in"""
-        import torch
-        m = d_keys.numel()
-        p = lambda t: t.data_ptr() if t is not None and t.numel() else 0
-        bits_new = self.engine.chunk_index_dir_bits(self.n + m)
-        with torch.cuda.stream(self.stream):
-            if m == 0:  # nothing to merge: the index stays as it is
-                return (torch.empty(0, dtype=torch.int64, device=self.device),
-                        torch.empty(0, dtype=torch.uint8, device=self.device),
-                        dict(zip((name for name, _ in N.IndexAddCounts._fields_), (0, 0, 0, 0, self.n, self.n))))
-            cap = self.n + m
-            keys = torch.empty(cap, dtype=torch.int64, device=self.device)
-            digests = torch.empty(32 * cap, dtype=torch.uint8, device=self.device)
-            values = torch.empty(cap, dtype=torch.int64, device=self.device)
-            dir = torch.empty((1 << bits_new) + 1, dtype=torch.int32, device=self.device)
-            pos = torch.empty(m, dtype=torch.int64, device=self.device)
-            flags = torch.empty(m, dtype=torch.uint8, device=self.device)
-            counts = torch.zeros(6, dtype=torch.int64, device=self.device)
-            self.engine.dev_chunk_holders_add(p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n,
-                                              self.bits, p(d_keys), p(d_digests), p(d_values), p(d_valid), m, p(keys),
-                                              p(digests), p(values), dir.data_ptr(), bits_new, p(pos), p(flags),
-                                              counts.data_ptr(), stream=self.stream.cuda_stream)
-            c = [int(v) for v in counts.cpu()]
-            n_new = c[5]
-            if not self.n <= n_new <= cap:
-                raise N.SdcasError(N.SDCAS_E_HIP, f"ChunkHolders.add: {n_new} entries from {self.n} and a batch of {m}")
-            self.keys, self.digests, self.values, self.dir = keys[:n_new], digests[:32 * n_new], values[:n_new], dir
-            self.n, self.bits = n_new, bits_new
-        return pos, flags, dict(zip((name for name, _ in N.IndexAddCounts._fields_), c))
 
     # -- remove ---------------------------------------------------------------------
     def remove(self, file_ids, bits_new=None):
@@ -1478,35 +1445,6 @@ class ChunkHolders(ChunkIndex):
                                                                           chunk_index.values, chunk_index.dir))
         ix.stream.synchronize()
         ix.n, ix.bits = chunk_index.n, chunk_index.bits
-        return ix
-
-    @classmethod
-    def load(cls, engine, path, device=None):
-        """an index saved by `save`: checked (sdcas_chunk_holders_check)
-        before anything goes to the device; ValueError when it is not a
-        holders index"""
-        import torch
-        import zipfile
-        try:  # the archive's own checksums catch a byte that changed on disk
-            with np.load(path) as z:
-                keys, digests, values, dir, bits = (z["keys"].astype(np.uint64), z["digests"].astype(np.uint8),
-                                                    z["values"].astype(np.uint64), z["dir"].astype(np.uint32),
-                                                    int(z["bits"]))
-        except (zipfile.BadZipFile, KeyError, EOFError, OSError, ValueError) as e:
-            raise ValueError(f"{path}: not a saved holders index ({e})") from e
-        n = keys.size
-        if digests.size != 32 * n or values.size != n or not 0 <= bits <= N.SDCAS_INDEX_MAX_BITS or \
-                dir.size != (1 << bits) + 1:
-            raise ValueError(f"{path}: the arrays' sizes do not make an index")
-        rc, bad = Engine.chunk_holders_check(keys, digests, values, dir, bits)
-        if rc != N.SDCAS_OK:
-            raise ValueError(f"{path}: not a holders index (sdcas error {rc}" +
-                             (f", first at entry or slot {bad})" if bad is not None else ")"))
-        ix = cls(engine, device)
-        with torch.cuda.stream(ix.stream):
-            ix.keys, ix.digests = ix._upload(keys, np.int64), ix._upload(digests, np.uint8)
-            ix.values, ix.dir = ix._upload(values, np.int64), ix._upload(dir, np.int32)
-        ix.n, ix.bits = n, bits
         return ix
 
 

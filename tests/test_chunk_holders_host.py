@@ -59,7 +59,7 @@ def test_a_null_context_is_refused_without_a_device():
 
 def test_library_holds_the_kernels():
     out = subprocess.run(["nm", "-C", N.LIB_PATH], capture_output=True, text=True).stdout
-    for k in ("k_ch_match", "k_ch_merge", "k_ch_head", "k_ch_scan", "k_ch_place", "k_ch_place_old", "k_ch_dir",
+    for k in ("k_ch_match", "k_ch_merge", "k_ch_head", "k_ch_scan", "k_ch_place", "k_ix_place_old", "k_ix_dir",
               "k_ch_rm_mark", "k_ch_rm_scatter"):
         assert k in out, k
 

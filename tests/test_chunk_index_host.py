@@ -49,7 +49,7 @@ def test_a_null_context_is_refused_without_a_device():
 
 def test_library_holds_the_kernels():
     out = subprocess.run(["nm", "-C", N.LIB_PATH], capture_output=True, text=True).stdout
-    for k in ("k_ci_match", "k_ci_select", "k_ci_fix", "k_ci_place_new", "k_ci_place_old", "k_ci_add_out", "k_ci_dir"):
+    for k in ("k_ci_match", "k_ci_select", "k_ci_fix", "k_ci_place_new", "k_ix_place_old", "k_ci_add_out", "k_ix_dir"):
         assert k in out, k
 
 
