@@ -65,6 +65,10 @@ template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;  // elements
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   hipError_t ensure(size_t n) {
     if (n <= cap) return hipSuccess;
     if (p) (void)hipFree(p);
@@ -118,6 +122,10 @@ struct HostStage {
   hipEvent_t ev[kN] = {};
   bool recorded[kN] = {};
   int next = 0;
+  HostStage() = default;
+  HostStage(const HostStage&) = delete;
+  HostStage& operator=(const HostStage&) = delete;
+  ~HostStage() { release(); }
   // the next buffer, free and of at least `bytes` bytes, for a caller that
   // builds its array in place; send() uploads it
   hipError_t reserve(size_t bytes, uint8_t** out) {
@@ -193,46 +201,35 @@ struct sdcas_ctx {
   Slot slots[2];  // double-buffered pinned staging (host fills one, GPU hashes the other)
   DevBuf<uint8_t> id_scratch;  // sdcas_dev_identify / sdcas_identify_checksums: the dual plans and the gathered cas messages
 
-  // sdcas_dedup's device copies of the caller's host arrays
-  DevBuf<uint64_t> dd_keys, dd_ekeys, dd_ids;
-  DevBuf<uint8_t> dd_has;
-  DevBuf<int32_t> dd_status;
-  DevBuf<int64_t> dd_link;
-  DevBuf<unsigned long long> dd_counts;
+  // The device copies of the host arrays of every host-array entry point
+  // (sdcas_dedup_window ... sdcas_chunk_holders_remove; laid out by Parts).
+  // One buffer serves them all: each such call holds the context's mutex,
+  // runs on the context's own stream and returns only after waiting for that
+  // stream (after an error return the next call is still ordered behind it
+  // there), so no two of them ever use the buffer at once.
+  DevBuf<uint8_t> host_io;
 
-  // the (cas key, checksum) group-by (confirm.hip): its tables, slots and
-  // counters, and sdcas_confirm_duplicates' device copies of the host arrays
-  DevBuf<uint32_t> cf_ws;
-  DevBuf<uint64_t> cf_keys;
-  DevBuf<uint8_t> cf_digests, cf_valid, cf_flags;
-  DevBuf<int64_t> cf_rep;  // rep | key_rep
-  DevBuf<unsigned long long> cf_counts;
+  // the dedup's ordinals (sdcas_dedup_window, sdcas_dev_dedup)
+  DevBuf<uint64_t> dd_ids;
 
-  // duplicate sets (dupsets.hip): the workspace, and sdcas_duplicate_sets'
-  // device copies of the host arrays
-  DevBuf<uint32_t> ds_ws;
-  DevBuf<int64_t> ds_in;   // rep | sizes
-  DevBuf<int64_t> ds_out;  // set_rep | set_offsets | set_bytes | members
-  DevBuf<unsigned long long> ds_counts;
+  // the workspaces of the (cas key, checksum) group-by (confirm.hip) and of
+  // the duplicate sets (dupsets.hip)
+  DevBuf<uint32_t> cf_ws, ds_ws;
 
-  // directory digests and top-most duplicates (dirtree.hip): the workspaces,
-  // the shape's upload, and the host calls' device copies of their arrays
-  DevBuf<uint8_t> tr_ws, tr_io;
+  // directory digests and top-most duplicates (dirtree.hip): the workspaces
+  // and the shape's upload
+  DevBuf<uint8_t> tr_ws;
   HostStage tr_stage;
   DevBuf<uint32_t> tt_ws;
-  DevBuf<int64_t> tt_io;
 
   // content-defined chunks and their sharing (cdc.hip): the workspaces, the
-  // packed chunks of one hash batch, the packed offsets' upload, and the host
-  // calls' device copies of their arrays
-  DevBuf<uint8_t> cd_ws, cd_pack, cd_io, cs_ws, cs_io;
+  // packed chunks of one hash batch and the packed offsets' upload
+  DevBuf<uint8_t> cd_ws, cd_pack, cs_ws;
   HostStage cd_stage;
 
-  // the chunk index (chunk_index.hip): the add's workspace, and the host
-  // calls' device copies of their arrays
-  DevBuf<uint8_t> ci_ws, ci_io;
-  // the holders index (chunk_holders.hip): the add's and the remove's
-  // workspace (the host calls' device copies are ci_io)
+  // the chunk index (chunk_index.hip): the add's workspace
+  DevBuf<uint8_t> ci_ws;
+  // the holders index (chunk_holders.hip): the add's and the remove's workspace
   DevBuf<uint8_t> ch_ws;
 
   // multi-GPU dedup stages
@@ -362,6 +359,114 @@ int grow_synced(sdcas_ctx* c, DevBuf<T>& buf, size_t need, hipStream_t st, const
   if (!e) e = buf.ensure(need);
   return e ? c->hip_fail(e, what) : SDCAS_OK;
 }
+
+// a HIP error of entry point `who` at `step` ("", " H2D", ...)
+int hip_fail_at(sdcas_ctx* c, hipError_t e, const char* who, const char* step) {
+  return c->hip_fail(e, (std::string(who) + step).c_str());
+}
+
+// The arrays of one host-array call `who` on stream st. Each is declared once,
+// with its host pointer and its element count, and becomes a 16-byte aligned
+// part of the context's host_io; the part converts to its typed device
+// pointer there (from reserve() on). A part whose host pointer is null is
+// off: it takes no room, its device pointer is null and nothing is copied for
+// it. A part of no elements is copied neither.
+struct Parts {
+  struct Item {
+    const void* up;  // uploaded from here (null: not)
+    void* down;      // downloaded to here (null: not)
+    size_t off, bytes, down_bytes;
+    bool on;
+  };
+  template <class T>
+  struct Part {
+    Parts* p;
+    size_t i;
+    operator T*() const {
+      const Item& x = p->items[i];
+      return x.on ? reinterpret_cast<T*>(p->c->host_io.p + x.off) : nullptr;
+    }
+    template <class U>
+    U* as() const {
+      return reinterpret_cast<U*>(static_cast<T*>(*this));
+    }
+    // only the first k elements come down (k within the declared count: the caller checks)
+    void first(size_t k) const { p->items[i].down_bytes = k * sizeof(T); }
+  };
+  sdcas_ctx* c;
+  hipStream_t st;
+  const char* who;
+  std::vector<Item> items;
+  size_t o = 0;
+  Parts(sdcas_ctx* cc, hipStream_t s, const char* w) : c(cc), st(s), who(w) { items.reserve(16); }
+
+  template <class T>
+  Part<T> take(const void* up, void* down, size_t n, bool on) {
+    const size_t bytes = n * sizeof(T);
+    items.push_back(Item{on ? up : nullptr, on ? down : nullptr, o, bytes, bytes, on});
+    if (on) o += (bytes + 15) & ~(size_t)15;
+    return Part<T>{this, items.size() - 1};
+  }
+  template <class T>
+  Part<const T> in(const T* h, size_t n) {
+    return take<const T>(h, nullptr, n, h != nullptr);
+  }
+  // keep: the device array is there (the kernels write it) whether or not the caller asks for it
+  template <class T>
+  Part<T> out(T* h, size_t n, bool keep = false) {
+    return take<T>(nullptr, h, n, keep || h != nullptr);
+  }
+  template <class T>
+  Part<T> inout(T* h, size_t n) {
+    return take<T>(h, h, n, h != nullptr);
+  }
+  // a device array of the call that no host array stands behind
+  template <class T>
+  Part<T> room(size_t n) {
+    return take<T>(nullptr, nullptr, n, true);
+  }
+
+  // host_io grown to the sum of the parts (the host waits only when it must be reallocated)
+  int reserve() { return grow_synced(c, c->host_io, o, st, (std::string(who) + " buffers").c_str()); }
+  int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* step) {
+    if (!bytes) return SDCAS_OK;
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
+    return e ? hip_fail_at(c, e, who, step) : SDCAS_OK;
+  }
+  int sync(const char* step = " sync") {
+    const hipError_t e = hipStreamSynchronize(st);
+    return e ? hip_fail_at(c, e, who, step) : SDCAS_OK;
+  }
+  // every input up
+  int upload() {
+    for (const Item& x : items)
+      if (x.up)
+        if (int rc = copy(c->host_io.p + x.off, x.up, x.bytes, hipMemcpyHostToDevice, " H2D")) return rc;
+    return SDCAS_OK;
+  }
+  // The counts down on their own, and the wait for them: they say how many
+  // entries of the other outputs follow. The caller checks their range and
+  // names the prefixes (Part::first); download() fetches the rest.
+  template <class T>
+  int counts(const Part<T>& part) {
+    Item& x = items[part.i];
+    if (int rc = copy(x.down, c->host_io.p + x.off, x.down_bytes, hipMemcpyDeviceToHost, " counts")) return rc;
+    x.down = nullptr;
+    return sync(" counts");
+  }
+  // a device array that is no part of the call, down with the outputs
+  template <class T>
+  int fetch(T* dst, const void* d_src, size_t n) {
+    return copy(dst, d_src, n * sizeof(T), hipMemcpyDeviceToHost, " D2H");
+  }
+  // every output down, and the call's final wait
+  int download() {
+    for (const Item& x : items)
+      if (x.down)
+        if (int rc = copy(x.down, c->host_io.p + x.off, x.down_bytes, hipMemcpyDeviceToHost, " D2H")) return rc;
+    return sync();
+  }
+};
 
 int reserve_ws(sdcas_ctx* c, size_t max_msgs, uint64_t max_chunks) {
   hipError_t e;
@@ -503,9 +608,6 @@ void slot_release(Slot& s) {
   if (s.hm) (void)hipHostFree(s.hm);
   s.hm = nullptr;
   s.cap_n = 0;
-  s.d_blob.release();
-  s.d_meta.release();
-  s.d_res.release();
   if (s.ev) (void)hipEventDestroy(s.ev);
   if (s.h2d) (void)hipEventDestroy(s.h2d);
   s.ev = s.h2d = nullptr;
@@ -856,47 +958,18 @@ void sdcas_destroy(sdcas_ctx* c) {
   // caller's stream may be gone by now: wait for the whole device instead
   if (!c->scratch_recorded) (void)hipDeviceSynchronize();
   else (void)c->scratch_sync();
-  for (auto* b : {&c->ws_S, &c->ws_total, &c->ws_soffs, &c->ws_slens, &c->dd_keys, &c->dd_ekeys, &c->dd_ids})
-    b->release();
-  for (auto* b : {&c->ws_tile_first, &c->ws_nodes, &c->ws_perm, &c->ws_sort_keys, &c->d_file_nodes, &c->piece_ctr, &c->piece_l4})
-    b->release();
-  for (auto* b : {&c->ws_scan, &c->d_out32, &c->dd_has, &c->id_scratch}) b->release();
-  c->d_files.release();
-  c->dd_status.release();
-  c->dd_link.release();
-  c->dd_counts.release();
-  c->cf_ws.release();
-  c->cf_keys.release();
-  for (auto* b : {&c->cf_digests, &c->cf_valid, &c->cf_flags}) b->release();
-  c->cf_rep.release();
-  c->cf_counts.release();
-  c->ds_ws.release();
-  for (auto* b : {&c->ds_in, &c->ds_out}) b->release();
-  c->ds_counts.release();
-  c->tr_ws.release();
-  c->tr_io.release();
-  c->tr_stage.release();
-  c->tt_ws.release();
-  c->tt_io.release();
-  for (auto* b : {&c->cd_ws, &c->cd_pack, &c->cd_io, &c->cs_ws, &c->cs_io}) b->release();
-  c->cd_stage.release();
-  c->ci_ws.release();
-  c->ci_io.release();
-  c->ch_ws.release();
+  // (the context's DevBufs and HostStages release themselves in `delete c`,
+  // after the waits above and before the streams go)
   c->dist.release();
-  c->sm_d_files.release();
-  c->sm_nodes.release();
-  c->sm_pieces.release();
-  c->sm_segs.release();
-  c->sm_stage.release();
   for (Slot& s : c->slots) slot_release(s);
   for (auto e : c->ev_free) (void)hipEventDestroy(e);
   for (auto& p : c->ev_leaf) (void)hipEventDestroy(p.first), (void)hipEventDestroy(p.second);
   for (auto& p : c->ev_all) (void)hipEventDestroy(p.first), (void)hipEventDestroy(p.second);
   if (c->scratch_ev) (void)hipEventDestroy(c->scratch_ev);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+  const hipStream_t stream = c->stream, copy_stream = c->copy_stream;
   delete c;
+  if (stream) (void)hipStreamDestroy(stream);
+  if (copy_stream) (void)hipStreamDestroy(copy_stream);
 }
 
 const char* sdcas_last_error(const sdcas_ctx* c) { return c ? c->err.c_str() : "no context"; }
@@ -1909,21 +1982,23 @@ int sdcas_dedup_window(sdcas_ctx* c, const uint64_t* keys, const uint8_t* has_ke
   if (!c || (n && (!keys || !has_key || !out_link)) || (n_existing && !existing_keys)) return SDCAS_E_INVALID;
   if (!dedup_fits(n, n_existing))
     return c->fail(SDCAS_E_CAPACITY, "dedup of %zu files + %zu Objects exceeds 2^30", n, n_existing);
-  PathCall call(c);
+  DevCall call(c, nullptr);
   if (call.rc) return call.rc;
   if (chunk_size == 0) chunk_size = SDCAS_IDENTIFIER_CHUNK_SIZE;
   hipError_t e;
-  hipStream_t st = c->stream;
-  if ((e = c->dd_keys.ensure(n)) || (e = c->dd_has.ensure(n)) || (e = c->dd_link.ensure(n)) ||
-      (status && (e = c->dd_status.ensure(n))) || (e = c->dd_ekeys.ensure(n_existing + 1)) ||
-      (e = c->dd_counts.ensure(2)))
-    return c->hip_fail(e, "dedup buffers");
-  if ((e = hipMemcpyAsync(c->dd_keys.p, keys, 8 * n, hipMemcpyHostToDevice, st)) ||
-      (e = hipMemcpyAsync(c->dd_has.p, has_key, n, hipMemcpyHostToDevice, st)) ||
-      (status && (e = hipMemcpyAsync(c->dd_status.p, status, 4 * n, hipMemcpyHostToDevice, st))) ||
-      (n_existing && (e = hipMemcpyAsync(c->dd_ekeys.p, existing_keys, 8 * n_existing, hipMemcpyHostToDevice, st))) ||
-      (e = hipMemsetAsync(c->dd_counts.p, 0, 2 * sizeof(unsigned long long), st)))
-    return c->hip_fail(e, "dedup H2D");
+  hipStream_t st = call.st;
+  unsigned long long cnt[2] = {0, 0};
+  uint64_t hdr[kPlanHeader] = {};
+  Parts p(c, st, "dedup");
+  const auto d_keys = p.in(keys, n);
+  const auto d_has = p.in(has_key, n);
+  const auto d_status = p.in(status, n);
+  const auto d_ekeys = p.in(existing_keys, n_existing);
+  const auto d_link = p.out(out_link, n);
+  const auto d_cnt = p.out(cnt, 2);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = p.upload()) return rc;
+  if ((e = hipMemsetAsync(d_cnt, 0, sizeof cnt, st))) return c->hip_fail(e, "dedup counts");
   // files are ordinals 0..n-1 in orphan order, existing Objects 0..ne-1 in DB
   // order: one iota serves both (ids of the first min(n, ne) coincide)
   if ((e = iota(c->dd_ids, std::max(n, n_existing), st))) return c->hip_fail(e, "dedup ids");
@@ -1931,17 +2006,11 @@ int sdcas_dedup_window(sdcas_ctx* c, const uint64_t* keys, const uint8_t* has_ke
   sw.n_total = n;
   sw.max_steps = win ? win->max_steps : 0;
   sw.more = win ? win->more : 0;
-  if ((e = dd_local(c->dist, c->dd_keys.p, c->dd_has.p, status ? c->dd_status.p : nullptr, c->dd_ids.p, (uint32_t)n,
-                    c->dd_ekeys.p, c->dd_ids.p, (uint32_t)n_existing, chunk_size, sw, c->dd_link.p, c->dd_counts.p,
-                    st)))
+  if ((e = dd_local(c->dist, d_keys, d_has, d_status, c->dd_ids.p, (uint32_t)n, d_ekeys, c->dd_ids.p,
+                    (uint32_t)n_existing, chunk_size, sw, d_link, d_cnt, st)))
     return c->hip_fail(e, "dedup");
-  unsigned long long cnt[2] = {0, 0};
-  uint64_t hdr[kPlanHeader] = {};
-  if ((n && (e = hipMemcpyAsync(out_link, c->dd_link.p, 8 * n, hipMemcpyDeviceToHost, st))) ||
-      (e = hipMemcpyAsync(cnt, c->dd_counts.p, sizeof cnt, hipMemcpyDeviceToHost, st)) ||
-      (e = hipMemcpyAsync(hdr, c->dist.plan.p, sizeof hdr, hipMemcpyDeviceToHost, st)))
-    return c->hip_fail(e, "dedup D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "dedup sync");
+  if (int rc = p.fetch(hdr, c->dist.plan.p, kPlanHeader)) return rc;
+  if (int rc = p.download()) return rc;
   if (out_created) *out_created = (int64_t)cnt[0];
   if (out_linked) *out_linked = (int64_t)cnt[1];
   if (win) {
@@ -2012,31 +2081,24 @@ int sdcas_confirm_duplicates(sdcas_ctx* c, const uint64_t* keys, const uint8_t* 
   if (n && (!keys || !digests32)) return c->fail(SDCAS_E_INVALID, "confirm_duplicates: null keys or digests");
   if (out_counts) memset(out_counts, 0, sizeof *out_counts);
   if (n == 0) return SDCAS_OK;
-  PathCall call(c);
+  DevCall call(c, nullptr);
   if (call.rc) return call.rc;
-  hipError_t e;
-  hipStream_t st = c->stream;
-  if ((e = c->cf_keys.ensure(n)) || (e = c->cf_digests.ensure(32 * n)) || (valid && (e = c->cf_valid.ensure(n))) ||
-      (e = c->cf_rep.ensure(2 * n)) || (e = c->cf_flags.ensure(n)) || (e = c->cf_counts.ensure(kConfirmCounts)))
-    return c->hip_fail(e, "confirm buffers");
+  hipStream_t st = call.st;
+  Parts p(c, st, "confirm_duplicates");
+  const auto d_keys = p.in(keys, n);
+  const auto d_digests = p.in(digests32, 32 * n);
+  const auto d_valid = p.in(valid, n);
+  const auto d_rep = p.out(out_rep, n);
+  const auto d_krep = p.out(out_key_rep, n);
+  const auto d_flags = p.out(out_flags, n);
+  const auto d_cts = p.out(out_counts, 1);
+  if (int rc = p.reserve()) return rc;
   if (int rc = confirm_ws(c, n, st)) return rc;
-  if ((e = hipMemcpyAsync(c->cf_keys.p, keys, 8 * n, hipMemcpyHostToDevice, st)) ||
-      (e = hipMemcpyAsync(c->cf_digests.p, digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
-      (valid && (e = hipMemcpyAsync(c->cf_valid.p, valid, n, hipMemcpyHostToDevice, st))))
-    return c->hip_fail(e, "confirm H2D");
-  int64_t* d_rep = out_rep ? c->cf_rep.p : nullptr;
-  int64_t* d_krep = out_key_rep ? c->cf_rep.p + n : nullptr;
-  if ((e = confirm_duplicates(c->cf_ws.p, c->cf_keys.p, c->cf_digests.p, valid ? c->cf_valid.p : nullptr, (uint32_t)n,
-                              d_rep, d_krep, out_flags ? c->cf_flags.p : nullptr,
-                              out_counts ? c->cf_counts.p : nullptr, st)))
+  if (int rc = p.upload()) return rc;
+  if (hipError_t e = confirm_duplicates(c->cf_ws.p, d_keys, d_digests, d_valid, (uint32_t)n, d_rep, d_krep, d_flags,
+                                        d_cts.as<unsigned long long>(), st))
     return c->hip_fail(e, "confirm_duplicates");
-  if ((out_rep && (e = hipMemcpyAsync(out_rep, d_rep, 8 * n, hipMemcpyDeviceToHost, st))) ||
-      (out_key_rep && (e = hipMemcpyAsync(out_key_rep, d_krep, 8 * n, hipMemcpyDeviceToHost, st))) ||
-      (out_flags && (e = hipMemcpyAsync(out_flags, c->cf_flags.p, n, hipMemcpyDeviceToHost, st))) ||
-      (out_counts && (e = hipMemcpyAsync(out_counts, c->cf_counts.p, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, "confirm D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "confirm sync");
-  return SDCAS_OK;
+  return p.download();
 }
 
 // ---- duplicate sets (dupsets.hip) ----------------------------------------------
@@ -2092,43 +2154,30 @@ int sdcas_duplicate_sets(sdcas_ctx* c, const int64_t* rep, const uint64_t* sizes
     if (out_set_offsets) out_set_offsets[0] = 0;
     return SDCAS_OK;
   }
-  PathCall call(c);
+  DevCall call(c, nullptr);
   if (call.rc) return call.rc;
-  hipError_t e;
-  hipStream_t st = c->stream;
-  const size_t h = n / 2;
-  if ((e = c->ds_in.ensure(2 * n)) || (e = c->ds_out.ensure(3 * h + 1 + n)) ||
-      (e = c->ds_counts.ensure(kDupsetsCounts)))
-    return c->hip_fail(e, "duplicate sets buffers");
-  if (int rc = dupsets_ws(c, n, st)) return rc;
-  int64_t* d_rep = c->ds_in.p;
-  uint64_t* d_sizes = sizes ? reinterpret_cast<uint64_t*>(c->ds_in.p + n) : nullptr;
-  if ((e = hipMemcpyAsync(d_rep, rep, 8 * n, hipMemcpyHostToDevice, st)) ||
-      (sizes && (e = hipMemcpyAsync(d_sizes, sizes, 8 * n, hipMemcpyHostToDevice, st))))
-    return c->hip_fail(e, "duplicate sets H2D");
-  int64_t* d_set_rep = c->ds_out.p;
-  uint64_t* d_set_offsets = reinterpret_cast<uint64_t*>(c->ds_out.p + h);
-  uint64_t* d_set_bytes = reinterpret_cast<uint64_t*>(c->ds_out.p + 2 * h + 1);
-  int64_t* d_members = c->ds_out.p + 3 * h + 1;
-  if ((e = duplicate_sets(c->ds_ws.p, d_rep, d_sizes, (uint32_t)n, order, out_set_rep ? d_set_rep : nullptr,
-                          out_set_offsets ? d_set_offsets : nullptr, out_set_bytes ? d_set_bytes : nullptr,
-                          out_members ? d_members : nullptr, c->ds_counts.p, st)))
-    return c->hip_fail(e, "duplicate_sets");
-  // the counts down first: they say how many entries of each array follow
+  hipStream_t st = call.st;
+  const size_t h = n / 2;  // no more sets than that
   sdcas_sets_counts cts;
-  if ((e = hipMemcpyAsync(&cts, c->ds_counts.p, sizeof cts, hipMemcpyDeviceToHost, st)) ||
-      (e = hipStreamSynchronize(st)))
-    return c->hip_fail(e, "duplicate sets counts");
+  Parts p(c, st, "duplicate_sets");
+  const auto d_rep = p.in(rep, n);
+  const auto d_sizes = p.in(sizes, n);
+  const auto d_set_rep = p.out(out_set_rep, h);
+  const auto d_set_offsets = p.out(out_set_offsets, h + 1);
+  const auto d_set_bytes = p.out(out_set_bytes, h);
+  const auto d_members = p.out(out_members, n);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = dupsets_ws(c, n, st)) return rc;
+  if (int rc = p.upload()) return rc;
+  if (hipError_t e = duplicate_sets(c->ds_ws.p, d_rep, d_sizes, (uint32_t)n, order, d_set_rep, d_set_offsets,
+                                    d_set_bytes, d_members, d_cts.as<unsigned long long>(), st))
+    return c->hip_fail(e, "duplicate_sets");
+  if (int rc = p.counts(d_cts)) return rc;
   if (cts.sets > h || cts.members > n) return c->fail(SDCAS_E_HIP, "duplicate_sets: counts out of range");
-  if ((out_set_rep && cts.sets && (e = hipMemcpyAsync(out_set_rep, d_set_rep, 8 * cts.sets, hipMemcpyDeviceToHost, st))) ||
-      (out_set_offsets &&
-       (e = hipMemcpyAsync(out_set_offsets, d_set_offsets, 8 * (cts.sets + 1), hipMemcpyDeviceToHost, st))) ||
-      (out_set_bytes && cts.sets &&
-       (e = hipMemcpyAsync(out_set_bytes, d_set_bytes, 8 * cts.sets, hipMemcpyDeviceToHost, st))) ||
-      (out_members && cts.members &&
-       (e = hipMemcpyAsync(out_members, d_members, 8 * cts.members, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, "duplicate sets D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "duplicate sets sync");
+  d_set_rep.first(cts.sets), d_set_offsets.first(cts.sets + 1), d_set_bytes.first(cts.sets);
+  d_members.first(cts.members);
+  if (int rc = p.download()) return rc;
   if (out_counts) *out_counts = cts;
   return SDCAS_OK;
 }
@@ -2240,43 +2289,23 @@ int sdcas_tree_digests(sdcas_ctx* c, const int64_t* parent, const uint8_t* is_di
   if (n == 0) return SDCAS_OK;
   DevCall call(c, nullptr);
   if (call.rc) return call.rc;
-  hipError_t e;
   hipStream_t st = call.st;
-  // name32 | digests32 | sizes | keys | tree_bytes | tree_files | counts | valid | flags
-  const size_t o_dig = 32 * n, o_sizes = 64 * n, o_keys = 72 * n, o_tb = 80 * n, o_tf = 88 * n, o_cts = 96 * n,
-               o_valid = o_cts + 64, o_flags = o_valid + n;
-  if (o_flags + n > c->tr_io.cap) {
-    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->tr_io.ensure(o_flags + n)))
-      return c->hip_fail(e, "tree_digests buffers");
-  }
-  uint8_t* io = c->tr_io.p;
-  if ((e = hipMemcpyAsync(io, name32, 32 * n, hipMemcpyHostToDevice, st)) ||
-      (e = hipMemcpyAsync(io + o_dig, digests32, 32 * n, hipMemcpyHostToDevice, st)) ||
-      (sizes && (e = hipMemcpyAsync(io + o_sizes, sizes, 8 * n, hipMemcpyHostToDevice, st))) ||
-      (keys && (e = hipMemcpyAsync(io + o_keys, keys, 8 * n, hipMemcpyHostToDevice, st))) ||
-      (valid && (e = hipMemcpyAsync(io + o_valid, valid, n, hipMemcpyHostToDevice, st))))
-    return c->hip_fail(e, "tree_digests H2D");
-  TreeArgs a{nullptr,
-             io,
-             sizes ? reinterpret_cast<const uint64_t*>(io + o_sizes) : nullptr,
-             keys ? reinterpret_cast<uint64_t*>(io + o_keys) : nullptr,
-             io + o_dig,
-             valid ? io + o_valid : nullptr,
-             out_tree_bytes ? reinterpret_cast<uint64_t*>(io + o_tb) : nullptr,
-             out_tree_files ? reinterpret_cast<uint64_t*>(io + o_tf) : nullptr,
-             out_flags ? io + o_flags : nullptr};
-  if (int rc = tree_enqueue(c, "tree_digests", s, is_dir, a, reinterpret_cast<uint64_t*>(io + o_cts), st)) return rc;
-  // (the file entries' slots come back as they went up)
-  if ((e = hipMemcpyAsync(digests32, io + o_dig, 32 * n, hipMemcpyDeviceToHost, st)) ||
-      (keys && (e = hipMemcpyAsync(keys, io + o_keys, 8 * n, hipMemcpyDeviceToHost, st))) ||
-      (valid && (e = hipMemcpyAsync(valid, io + o_valid, n, hipMemcpyDeviceToHost, st))) ||
-      (out_tree_bytes && (e = hipMemcpyAsync(out_tree_bytes, io + o_tb, 8 * n, hipMemcpyDeviceToHost, st))) ||
-      (out_tree_files && (e = hipMemcpyAsync(out_tree_files, io + o_tf, 8 * n, hipMemcpyDeviceToHost, st))) ||
-      (out_flags && (e = hipMemcpyAsync(out_flags, io + o_flags, n, hipMemcpyDeviceToHost, st))) ||
-      (out_counts && (e = hipMemcpyAsync(out_counts, io + o_cts, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, "tree_digests D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "tree_digests sync");
-  return SDCAS_OK;
+  Parts p(c, st, "tree_digests");
+  const auto d_name = p.in(name32, 32 * n);
+  const auto d_sizes = p.in(sizes, n);
+  // (the file entries' slots of these three come back as they went up)
+  const auto d_keys = p.inout(keys, n);
+  const auto d_digests = p.inout(digests32, 32 * n);
+  const auto d_valid = p.inout(valid, n);
+  const auto d_tb = p.out(out_tree_bytes, n);
+  const auto d_tf = p.out(out_tree_files, n);
+  const auto d_flags = p.out(out_flags, n);
+  const auto d_cts = p.out(out_counts, 1, true);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = p.upload()) return rc;
+  const TreeArgs a{nullptr, d_name, d_sizes, d_keys, d_digests, d_valid, d_tb, d_tf, d_flags};
+  if (int rc = tree_enqueue(c, "tree_digests", s, is_dir, a, d_cts.as<uint64_t>(), st)) return rc;
+  return p.download();
 }
 
 // the workspace grown to n entries
@@ -2317,29 +2346,20 @@ int sdcas_tree_top(sdcas_ctx* c, const int64_t* parent, const int64_t* rep, size
   if (n == 0) return SDCAS_OK;
   DevCall call(c, nullptr);
   if (call.rc) return call.rc;
-  hipError_t e;
   hipStream_t st = call.st;
-  // parent | rep | top_rep | counts (8 words) | flags
-  const size_t words = 3 * n + 8 + (n + 7) / 8;
-  if (words > c->tt_io.cap) {
-    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->tt_io.ensure(words)))
-      return c->hip_fail(e, "tree_top buffers");
-  }
+  Parts p(c, st, "tree_top");
+  const auto d_parent = p.in(parent, n);
+  const auto d_rep = p.in(rep, n);
+  const auto d_top = p.out(out_top_rep, n);
+  const auto d_flags = p.out(out_flags, n);
+  const auto d_cts = p.out(out_counts, 1, true);
+  if (int rc = p.reserve()) return rc;
   if (int rc = tree_top_ws(c, n, st)) return rc;
-  int64_t* io = c->tt_io.p;
-  uint8_t* d_flags = reinterpret_cast<uint8_t*>(io + 3 * n + 8);
-  if ((e = hipMemcpyAsync(io, parent, 8 * n, hipMemcpyHostToDevice, st)) ||
-      (e = hipMemcpyAsync(io + n, rep, 8 * n, hipMemcpyHostToDevice, st)))
-    return c->hip_fail(e, "tree_top H2D");
-  if ((e = tree_top(c->tt_ws.p, io, io + n, (uint32_t)n, out_top_rep ? io + 2 * n : nullptr,
-                    out_flags ? d_flags : nullptr, reinterpret_cast<unsigned long long*>(io + 3 * n), st)))
+  if (int rc = p.upload()) return rc;
+  if (hipError_t e = tree_top(c->tt_ws.p, d_parent, d_rep, (uint32_t)n, d_top, d_flags,
+                              d_cts.as<unsigned long long>(), st))
     return c->hip_fail(e, "tree_top");
-  if ((out_top_rep && (e = hipMemcpyAsync(out_top_rep, io + 2 * n, 8 * n, hipMemcpyDeviceToHost, st))) ||
-      (out_flags && (e = hipMemcpyAsync(out_flags, d_flags, n, hipMemcpyDeviceToHost, st))) ||
-      (out_counts && (e = hipMemcpyAsync(out_counts, io + 3 * n, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, "tree_top D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "tree_top sync");
-  return SDCAS_OK;
+  return p.download();
 }
 
 // ---- content-defined chunks and their sharing (cdc.hip) ---------------------------
@@ -2531,64 +2551,42 @@ static int chunk_host(sdcas_ctx* c, const char* who, bool windows, const uint8_t
   if (call.rc) return call.rc;
   hipError_t e;
   hipStream_t st = call.st;
-  // blob | offs | lens | file_chunks | chunk_off | chunk_len | keys | counts | digests | chunk_file
   const uint64_t mc = max_chunks;
-  const uint64_t o_offs = bytes, o_lens = o_offs + 8 * n, o_fc = o_lens + 8 * n, o_off = o_fc + 8 * (n + 1),
-                 o_len = o_off + 8 * mc, o_keys = o_len + 8 * mc, o_cts = o_keys + 8 * mc, o_dig = o_cts + 64,
-                 o_file = o_dig + 32 * mc, o_cons = (o_file + 4 * mc + 7) & ~7ull, o_fin = o_cons + 8 * n,
-                 total = windows ? o_fin + n : o_file + 4 * mc;  // windows: | consumed | final
-  if (total > c->cd_io.cap) {
-    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->cd_io.ensure(total)))
-      return c->hip_fail(e, who);
-  }
-  uint8_t* io = c->cd_io.p;
+  sdcas_chunk_counts cts;
+  Parts pt(c, st, who);
+  const auto d_blob = pt.room<uint8_t>(bytes);
+  const auto d_offs = pt.in(at.data(), n);
+  const auto d_lens = pt.in(lens, n);
+  const auto d_final = pt.in(final, n);
+  const auto d_fc = pt.out(out_file_chunks, n + 1, true);
+  const auto d_off = pt.out(out_chunk_off, mc, true);
+  const auto d_len = pt.out(out_chunk_len, mc, true);
+  const auto d_file = pt.out(out_chunk_file, mc, true);
+  const auto d_keys = pt.out(out_keys, mc);
+  const auto d_digests = pt.out(out_digests32, 32 * mc);
+  const auto d_consumed = pt.out(out_consumed, n, windows);
+  const auto d_cts = pt.out(&cts, 1);
+  if (int rc = pt.reserve()) return rc;
   {
     // the files, packed on the host, in one upload
-    std::vector<uint8_t> img(bytes + 16 * n, 0);
-    uint64_t* hoffs = reinterpret_cast<uint64_t*>(img.data() + bytes);
-    for (size_t i = 0; i < n; ++i) {
+    std::vector<uint8_t> img(bytes, 0);
+    for (size_t i = 0; i < n; ++i)
       if (lens[i]) memcpy(img.data() + at[i], blob + offsets[i], lens[i]);
-      hoffs[i] = at[i], hoffs[n + i] = lens[i];
-    }
-    if ((e = hipMemcpyAsync(io, img.data(), img.size(), hipMemcpyHostToDevice, st)) ||
-        (final && (e = hipMemcpyAsync(io + o_fin, final, n, hipMemcpyHostToDevice, st))) ||
-        (e = hipStreamSynchronize(st)))
-      return c->hip_fail(e, who);
+    if ((e = hipMemcpyAsync(d_blob, img.data(), bytes, hipMemcpyHostToDevice, st))) return hip_fail_at(c, e, who, " H2D");
+    if (int rc = pt.upload()) return rc;
+    if (int rc = pt.sync(" H2D")) return rc;
   }
-  const CdcWinArgs win{final ? io + o_fin : nullptr, reinterpret_cast<uint64_t*>(io + o_cons), windows ? chunk_seg(p) : 0};
-  CdcArgs a{nullptr,
-            io,
-            reinterpret_cast<const uint64_t*>(io + o_offs),
-            reinterpret_cast<const uint64_t*>(io + o_lens),
-            (uint32_t)n,
-            p,
-            max_chunks,
-            slots,
-            reinterpret_cast<uint64_t*>(io + o_fc),
-            reinterpret_cast<uint64_t*>(io + o_off),
-            reinterpret_cast<uint64_t*>(io + o_len),
-            reinterpret_cast<uint32_t*>(io + o_file)};
-  if (int rc = chunk_enqueue(c, who, a, out_keys ? reinterpret_cast<uint64_t*>(io + o_keys) : nullptr,
-                             out_digests32 ? io + o_dig : nullptr, reinterpret_cast<uint64_t*>(io + o_cts), st,
-                             windows ? &win : nullptr))
+  const CdcWinArgs win{d_final, d_consumed, windows ? chunk_seg(p) : 0};
+  const CdcArgs a{nullptr, d_blob, d_offs, d_lens, (uint32_t)n, p, max_chunks, slots, d_fc, d_off, d_len, d_file};
+  if (int rc = chunk_enqueue(c, who, a, d_keys, d_digests, d_cts.as<uint64_t>(), st, windows ? &win : nullptr))
     return rc;
-  // the counts down first: they say how many entries of each array follow
-  sdcas_chunk_counts cts;
-  if ((e = hipMemcpyAsync(&cts, io + o_cts, sizeof cts, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
-    return c->hip_fail(e, who);
+  if (int rc = pt.counts(d_cts)) return rc;
   const uint64_t m = cts.chunks;
   if (m > mc) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
+  d_off.first(m), d_len.first(m), d_file.first(m), d_keys.first(m), d_digests.first(32 * m);
   std::vector<uint32_t> file(out_chunk_off ? m : 0);
-  if ((out_file_chunks && (e = hipMemcpyAsync(out_file_chunks, io + o_fc, 8 * (n + 1), hipMemcpyDeviceToHost, st))) ||
-      (out_consumed && (e = hipMemcpyAsync(out_consumed, io + o_cons, 8 * n, hipMemcpyDeviceToHost, st))) ||
-      (m && out_chunk_off && ((e = hipMemcpyAsync(out_chunk_off, io + o_off, 8 * m, hipMemcpyDeviceToHost, st)) ||
-                              (e = hipMemcpyAsync(file.data(), io + o_file, 4 * m, hipMemcpyDeviceToHost, st)))) ||
-      (m && out_chunk_len && (e = hipMemcpyAsync(out_chunk_len, io + o_len, 8 * m, hipMemcpyDeviceToHost, st))) ||
-      (m && out_chunk_file && (e = hipMemcpyAsync(out_chunk_file, io + o_file, 4 * m, hipMemcpyDeviceToHost, st))) ||
-      (m && out_keys && (e = hipMemcpyAsync(out_keys, io + o_keys, 8 * m, hipMemcpyDeviceToHost, st))) ||
-      (m && out_digests32 && (e = hipMemcpyAsync(out_digests32, io + o_dig, 32 * m, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, who);
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, who);
+  if (int rc = pt.fetch(file.data(), d_file, file.size())) return rc;
+  if (int rc = pt.download()) return rc;
   // offsets in the caller's blob, not in the device copy
   if (out_chunk_off)
     for (uint64_t k = 0; k < m; ++k)
@@ -2686,38 +2684,25 @@ int sdcas_chunk_sharing(sdcas_ctx* c, const uint32_t* chunk_file, const uint64_t
   if (out_counts) memset(out_counts, 0, sizeof *out_counts);
   DevCall call(c, nullptr);
   if (call.rc) return call.rc;
-  hipError_t e;
   hipStream_t st = call.st;
-  // chunk_len | rep | new | self | other | peer | peer_bytes | counts | chunk_file
   const size_t nf = n_files;
-  const size_t o_rep = 8 * m, o_new = 16 * m, o_self = o_new + 8 * nf, o_other = o_self + 8 * nf,
-               o_peer = o_other + 8 * nf, o_pb = o_peer + 8 * nf, o_cts = o_pb + 8 * nf, o_file = o_cts + 64,
-               total = o_file + 4 * m;
-  if (total > c->cs_io.cap) {
-    if ((e = c->scratch_sync()) || (e = hipStreamSynchronize(st)) || (e = c->cs_io.ensure(total)))
-      return c->hip_fail(e, "chunk_sharing buffers");
-  }
+  Parts p(c, st, "chunk_sharing");
+  const auto d_file = p.in(chunk_file, m);
+  const auto d_len = p.in(chunk_len, m);
+  const auto d_rep = p.in(rep, m);
+  const auto d_new = p.out(out_new_bytes, nf, true);
+  const auto d_self = p.out(out_self_bytes, nf, true);
+  const auto d_other = p.out(out_other_bytes, nf, true);
+  const auto d_peer = p.out(out_peer, nf, true);
+  const auto d_pb = p.out(out_peer_bytes, nf, true);
+  const auto d_cts = p.out(out_counts, 1, true);
+  if (int rc = p.reserve()) return rc;
   if (int rc = sharing_ws(c, m, n_files, st)) return rc;
-  uint8_t* io = c->cs_io.p;
-  if (m && ((e = hipMemcpyAsync(io, chunk_len, 8 * m, hipMemcpyHostToDevice, st)) ||
-            (e = hipMemcpyAsync(io + o_rep, rep, 8 * m, hipMemcpyHostToDevice, st)) ||
-            (e = hipMemcpyAsync(io + o_file, chunk_file, 4 * m, hipMemcpyHostToDevice, st))))
-    return c->hip_fail(e, "chunk_sharing H2D");
-  if ((e = cdc_sharing(c->cs_ws.p, reinterpret_cast<const uint32_t*>(io + o_file), reinterpret_cast<const uint64_t*>(io),
-                       reinterpret_cast<const int64_t*>(io + o_rep), (uint32_t)m, (uint32_t)n_files,
-                       reinterpret_cast<uint64_t*>(io + o_new), reinterpret_cast<uint64_t*>(io + o_self),
-                       reinterpret_cast<uint64_t*>(io + o_other), reinterpret_cast<int64_t*>(io + o_peer),
-                       reinterpret_cast<uint64_t*>(io + o_pb), reinterpret_cast<unsigned long long*>(io + o_cts), st)))
+  if (int rc = p.upload()) return rc;
+  if (hipError_t e = cdc_sharing(c->cs_ws.p, d_file, d_len, d_rep, (uint32_t)m, (uint32_t)n_files, d_new, d_self,
+                                 d_other, d_peer, d_pb, d_cts.as<unsigned long long>(), st))
     return c->hip_fail(e, "chunk_sharing");
-  if ((nf && out_new_bytes && (e = hipMemcpyAsync(out_new_bytes, io + o_new, 8 * nf, hipMemcpyDeviceToHost, st))) ||
-      (nf && out_self_bytes && (e = hipMemcpyAsync(out_self_bytes, io + o_self, 8 * nf, hipMemcpyDeviceToHost, st))) ||
-      (nf && out_other_bytes && (e = hipMemcpyAsync(out_other_bytes, io + o_other, 8 * nf, hipMemcpyDeviceToHost, st))) ||
-      (nf && out_peer && (e = hipMemcpyAsync(out_peer, io + o_peer, 8 * nf, hipMemcpyDeviceToHost, st))) ||
-      (nf && out_peer_bytes && (e = hipMemcpyAsync(out_peer_bytes, io + o_pb, 8 * nf, hipMemcpyDeviceToHost, st))) ||
-      (out_counts && (e = hipMemcpyAsync(out_counts, io + o_cts, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
-    return c->hip_fail(e, "chunk_sharing D2H");
-  if ((e = hipStreamSynchronize(st))) return c->hip_fail(e, "chunk_sharing sync");
-  return SDCAS_OK;
+  return p.download();
 }
 
 // ---- the chunk index (chunk_index.hip) ----------------------------------------------
@@ -2782,9 +2767,6 @@ static int index_add_args(sdcas_ctx* c, const char* who, const void* old_keys, c
 // every add and match entry point of the two is one body, told which by this.
 enum IndexKind { kPairs, kTriples };
 
-static int index_io(sdcas_ctx* c, size_t bytes, hipStream_t st) {
-  return grow_synced(c, c->ci_io, bytes, st, "chunk index buffers");
-}
 static int holders_ws(sdcas_ctx* c, size_t need, hipStream_t st) {
   return grow_synced(c, c->ch_ws, need, st, "chunk holders workspace");
 }
@@ -2809,11 +2791,6 @@ static hipError_t index_match_kind(IndexKind kind, const IndexView& v, const uin
   return index_match(v, keys, digests, valid, m, pos, value, counts, st);
 }
 
-// a HIP error of entry point `who` at `step` ("", " H2D", ...)
-static int index_hip_fail(sdcas_ctx* c, hipError_t e, const char* who, const char* step) {
-  return c->hip_fail(e, (std::string(who) + step).c_str());
-}
-
 // a pointer of the first group off 16 bytes, of the second off 8, of the third
 // off 4 (a null pointer passes)
 static bool index_misaligned(std::initializer_list<const void*> p16, std::initializer_list<const void*> p8,
@@ -2826,65 +2803,38 @@ static bool index_misaligned(std::initializer_list<const void*> p16, std::initia
 }
 
 namespace {
-// byte offsets of consecutive 16-byte aligned parts of one buffer
-struct Parts {
-  size_t o = 0;
-  size_t take(size_t bytes) {
-    const size_t at = o;
-    o += (bytes + 15) & ~(size_t)15;
-    return at;
-  }
+// a host index a call reads, among the call's parts
+struct IndexIn {
+  Parts::Part<const uint64_t> k;
+  Parts::Part<const uint8_t> d;
+  Parts::Part<const uint64_t> v;
+  Parts::Part<const uint32_t> dir;
+  uint32_t n, bits;
+  IndexView view() const { return IndexView{k, d, v, dir, n, bits}; }
 };
-// an index's four arrays among the parts of ci_io
-struct IndexParts {
-  size_t k, d, v, dir, dir_bytes;
+// the index of up to `cap` entries a call writes
+struct IndexNew {
+  Parts::Part<uint64_t> k;
+  Parts::Part<uint8_t> d;
+  Parts::Part<uint64_t> v;
+  Parts::Part<uint32_t> dir;
+  uint32_t bits;
+  IndexOut out() const { return IndexOut{k, d, v, dir, bits}; }
+  // nn entries come down (the directory whole)
+  void first(size_t nn) const { k.first(nn), d.first(32 * nn), v.first(nn); }
 };
 }  // namespace
 
-static IndexParts index_parts(Parts& p, size_t entries, size_t dir_bytes) {
-  IndexParts x{};
-  x.k = p.take(8 * entries), x.d = p.take(32 * entries), x.v = p.take(8 * entries), x.dir = p.take(dir_bytes);
-  x.dir_bytes = dir_bytes;
-  return x;
+// (an index of no entries is read without its directory)
+static IndexIn index_in(Parts& p, const uint64_t* keys, const uint8_t* digests, const uint64_t* values,
+                        const uint32_t* dir, size_t n, uint32_t bits) {
+  return IndexIn{p.in(keys, n), p.in(digests, 32 * n), p.in(values, n),
+                 p.in(dir, n ? (size_t)index_dir_slots(bits) : 0), (uint32_t)n, bits};
 }
-// the directory bytes an index of n entries is read with
-static size_t index_old_dir_bytes(uint64_t n, uint32_t bits) { return n ? 4 * (size_t)index_dir_slots(bits) : 0; }
-
-// a host index's arrays up into their parts of ci_io; *v <- its view there
-static hipError_t index_stage(uint8_t* io, const IndexParts& x, const uint64_t* keys, const uint8_t* digests,
-                              const uint64_t* values, const uint32_t* dir, size_t n, uint32_t bits, hipStream_t st,
-                              IndexView* v) {
-  hipError_t e;
-  if (n && ((e = hipMemcpyAsync(io + x.k, keys, 8 * n, hipMemcpyHostToDevice, st)) ||
-            (e = hipMemcpyAsync(io + x.d, digests, 32 * n, hipMemcpyHostToDevice, st)) ||
-            (values && (e = hipMemcpyAsync(io + x.v, values, 8 * n, hipMemcpyHostToDevice, st))) ||
-            (e = hipMemcpyAsync(io + x.dir, dir, x.dir_bytes, hipMemcpyHostToDevice, st))))
-    return e;
-  *v = IndexView{reinterpret_cast<const uint64_t*>(io + x.k), io + x.d,
-                 values ? reinterpret_cast<const uint64_t*>(io + x.v) : nullptr,
-                 reinterpret_cast<const uint32_t*>(io + x.dir), (uint32_t)n, bits};
-  return hipSuccess;
-}
-static IndexOut index_out_parts(uint8_t* io, const IndexParts& x, uint32_t bits) {
-  return IndexOut{reinterpret_cast<uint64_t*>(io + x.k), io + x.d, reinterpret_cast<uint64_t*>(io + x.v),
-                  reinterpret_cast<uint32_t*>(io + x.dir), bits};
-}
-// A new index down from its parts, the counts first: they say how many entries
-// of the new arrays follow. Waits for the counts, enqueues the rest.
-static int index_fetch(sdcas_ctx* c, const char* who, const uint8_t* io, const IndexParts& x, size_t o_cts, void* cts,
-                       size_t cts_bytes, const uint64_t* entries_new, size_t cap, uint64_t* new_keys,
-                       uint8_t* new_digests, uint64_t* new_values, uint32_t* new_dir, hipStream_t st) {
-  hipError_t e;
-  if ((e = hipMemcpyAsync(cts, io + o_cts, cts_bytes, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
-    return index_hip_fail(c, e, who, " counts");
-  const size_t nn = (size_t)*entries_new;
-  if (nn > cap) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
-  if ((nn && ((e = hipMemcpyAsync(new_keys, io + x.k, 8 * nn, hipMemcpyDeviceToHost, st)) ||
-              (e = hipMemcpyAsync(new_digests, io + x.d, 32 * nn, hipMemcpyDeviceToHost, st)) ||
-              (e = hipMemcpyAsync(new_values, io + x.v, 8 * nn, hipMemcpyDeviceToHost, st)))) ||
-      (e = hipMemcpyAsync(new_dir, io + x.dir, x.dir_bytes, hipMemcpyDeviceToHost, st)))
-    return index_hip_fail(c, e, who, " D2H");
-  return SDCAS_OK;
+static IndexNew index_new(Parts& p, uint64_t* keys, uint8_t* digests, uint64_t* values, uint32_t* dir, size_t cap,
+                          uint32_t bits) {
+  return IndexNew{p.out(keys, cap), p.out(digests, 32 * cap), p.out(values, cap),
+                  p.out(dir, (size_t)index_dir_slots(bits)), bits};
 }
 
 static int index_dev_match(sdcas_ctx* c, IndexKind kind, const char* who, const uint64_t* d_idx_keys,
@@ -2911,7 +2861,7 @@ static int index_dev_match(sdcas_ctx* c, IndexKind kind, const char* who, const 
   const IndexView v{d_idx_keys, d_idx_digests32, d_idx_values, d_idx_dir, (uint32_t)n, bits};
   e = index_match_kind(kind, v, d_keys, d_digests32, d_valid, (uint32_t)m, d_out_pos, d_out_value, d_out_holders,
                        (unsigned long long*)d_counts, call.st);
-  return e ? index_hip_fail(c, e, who, "") : SDCAS_OK;
+  return e ? hip_fail_at(c, e, who, "") : SDCAS_OK;
 }
 
 static int index_host_match(sdcas_ctx* c, IndexKind kind, const char* who, const uint64_t* idx_keys,
@@ -2927,34 +2877,22 @@ static int index_host_match(sdcas_ctx* c, IndexKind kind, const char* who, const
   if (m == 0) return SDCAS_OK;
   DevCall call(c, nullptr);
   if (call.rc) return call.rc;
-  hipError_t e;
   hipStream_t st = call.st;
-  Parts p;
-  const IndexParts ip = index_parts(p, n, index_old_dir_bytes(n, bits));
-  const size_t o_k = p.take(8 * m), o_d = p.take(32 * m), o_v = p.take(m), o_pos = p.take(8 * m),
-               o_val = p.take(8 * m), o_h = p.take(kind == kTriples ? 4 * m : 0),
-               o_cts = p.take(8 * kIndexMatchCounts);
-  if (int rc = index_io(c, p.o, st)) return rc;
-  uint8_t* io = c->ci_io.p;
-  IndexView v{};
-  if ((e = index_stage(io, ip, idx_keys, idx_digests32, idx_values, idx_dir, n, bits, st, &v)) ||
-      (e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
-      (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
-      (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))
-    return index_hip_fail(c, e, who, " H2D");
-  if ((e = index_match_kind(kind, v, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d, valid ? io + o_v : nullptr,
-                            (uint32_t)m, out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr,
-                            out_value ? reinterpret_cast<uint64_t*>(io + o_val) : nullptr,
-                            out_holders ? reinterpret_cast<uint32_t*>(io + o_h) : nullptr,
-                            out_counts ? reinterpret_cast<unsigned long long*>(io + o_cts) : nullptr, st)))
-    return index_hip_fail(c, e, who, "");
-  if ((out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
-      (out_value && (e = hipMemcpyAsync(out_value, io + o_val, 8 * m, hipMemcpyDeviceToHost, st))) ||
-      (out_holders && (e = hipMemcpyAsync(out_holders, io + o_h, 4 * m, hipMemcpyDeviceToHost, st))) ||
-      (out_counts && (e = hipMemcpyAsync(out_counts, io + o_cts, sizeof *out_counts, hipMemcpyDeviceToHost, st))))
-    return index_hip_fail(c, e, who, " D2H");
-  if ((e = hipStreamSynchronize(st))) return index_hip_fail(c, e, who, " sync");
-  return SDCAS_OK;
+  Parts p(c, st, who);
+  const IndexIn idx = index_in(p, idx_keys, idx_digests32, idx_values, idx_dir, n, bits);
+  const auto d_keys = p.in(keys, m);
+  const auto d_digests = p.in(digests32, 32 * m);
+  const auto d_valid = p.in(valid, m);
+  const auto d_pos = p.out(out_pos, m);
+  const auto d_value = p.out(out_value, m);
+  const auto d_holders = p.out(out_holders, m);
+  const auto d_cts = p.out(out_counts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = p.upload()) return rc;
+  if (hipError_t e = index_match_kind(kind, idx.view(), d_keys, d_digests, d_valid, (uint32_t)m, d_pos, d_value,
+                                      d_holders, d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  return p.download();
 }
 
 static int index_dev_add(sdcas_ctx* c, IndexKind kind, const char* who, const uint64_t* d_old_keys,
@@ -2978,7 +2916,7 @@ static int index_dev_add(sdcas_ctx* c, IndexKind kind, const char* who, const ui
   const IndexOut out{d_new_keys, d_new_digests32, d_new_values, d_new_dir, bits_new};
   hipError_t e = index_add_kind(c, kind, old, d_keys, d_digests32, d_values, d_valid, (uint32_t)m, out, d_out_pos,
                                 d_out_flags, (unsigned long long*)d_counts, call.st);
-  return e ? index_hip_fail(c, e, who, "") : SDCAS_OK;
+  return e ? hip_fail_at(c, e, who, "") : SDCAS_OK;
 }
 
 static int index_host_add(sdcas_ctx* c, IndexKind kind, const char* who, const uint64_t* old_keys,
@@ -2995,38 +2933,29 @@ static int index_host_add(sdcas_ctx* c, IndexKind kind, const char* who, const u
   if (out_counts) memset(out_counts, 0, sizeof *out_counts);
   DevCall call(c, nullptr);
   if (call.rc) return call.rc;
-  hipError_t e;
   hipStream_t st = call.st;
-  const size_t n = n_old, cap = n_old + m;
-  Parts p;
-  const IndexParts op = index_parts(p, n, index_old_dir_bytes(n, bits_old));
-  const size_t o_k = p.take(8 * m), o_d = p.take(32 * m), o_val = p.take(8 * m), o_v = p.take(m);
-  const IndexParts np = index_parts(p, cap, 4 * (size_t)index_dir_slots(bits_new));
-  const size_t o_pos = p.take(8 * m), o_fl = p.take(m), o_cts = p.take(8 * kIndexAddCounts);
-  if (int rc = index_io(c, p.o, st)) return rc;
-  if (int rc = index_add_ws(c, kind, m, st)) return rc;
-  uint8_t* io = c->ci_io.p;
-  IndexView old{};
-  if ((e = index_stage(io, op, old_keys, old_digests32, old_values, old_dir, n, bits_old, st, &old)) ||
-      (m && ((e = hipMemcpyAsync(io + o_k, keys, 8 * m, hipMemcpyHostToDevice, st)) ||
-             (e = hipMemcpyAsync(io + o_d, digests32, 32 * m, hipMemcpyHostToDevice, st)) ||
-             (values && (e = hipMemcpyAsync(io + o_val, values, 8 * m, hipMemcpyHostToDevice, st))) ||
-             (valid && (e = hipMemcpyAsync(io + o_v, valid, m, hipMemcpyHostToDevice, st))))))
-    return index_hip_fail(c, e, who, " H2D");
-  if ((e = index_add_kind(c, kind, old, reinterpret_cast<const uint64_t*>(io + o_k), io + o_d,
-                          values ? reinterpret_cast<const uint64_t*>(io + o_val) : nullptr,
-                          valid ? io + o_v : nullptr, (uint32_t)m, index_out_parts(io, np, bits_new),
-                          out_pos ? reinterpret_cast<int64_t*>(io + o_pos) : nullptr, out_flags ? io + o_fl : nullptr,
-                          reinterpret_cast<unsigned long long*>(io + o_cts), st)))
-    return index_hip_fail(c, e, who, "");
+  const size_t cap = n_old + m;
   sdcas_index_add_counts cts;
-  if (int rc = index_fetch(c, who, io, np, o_cts, &cts, sizeof cts, &cts.entries_new, cap, new_keys, new_digests32,
-                           new_values, new_dir, st))
-    return rc;
-  if ((m && out_pos && (e = hipMemcpyAsync(out_pos, io + o_pos, 8 * m, hipMemcpyDeviceToHost, st))) ||
-      (m && out_flags && (e = hipMemcpyAsync(out_flags, io + o_fl, m, hipMemcpyDeviceToHost, st))))
-    return index_hip_fail(c, e, who, " D2H");
-  if ((e = hipStreamSynchronize(st))) return index_hip_fail(c, e, who, " sync");
+  Parts p(c, st, who);
+  const IndexIn old = index_in(p, old_keys, old_digests32, old_values, old_dir, n_old, bits_old);
+  const auto d_keys = p.in(keys, m);
+  const auto d_digests = p.in(digests32, 32 * m);
+  const auto d_values = p.in(values, m);
+  const auto d_valid = p.in(valid, m);
+  const IndexNew nw = index_new(p, new_keys, new_digests32, new_values, new_dir, cap, bits_new);
+  const auto d_pos = p.out(out_pos, m);
+  const auto d_flags = p.out(out_flags, m);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = index_add_ws(c, kind, m, st)) return rc;
+  if (int rc = p.upload()) return rc;
+  if (hipError_t e = index_add_kind(c, kind, old.view(), d_keys, d_digests, d_values, d_valid, (uint32_t)m, nw.out(),
+                                    d_pos, d_flags, d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  if (int rc = p.counts(d_cts)) return rc;
+  if (cts.entries_new > cap) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
+  nw.first((size_t)cts.entries_new);
+  if (int rc = p.download()) return rc;
   if (out_counts) *out_counts = cts;
   return SDCAS_OK;
 }
@@ -3188,29 +3117,24 @@ int sdcas_chunk_holders_remove(sdcas_ctx* c, const uint64_t* old_keys, const uin
   if (out_counts) memset(out_counts, 0, sizeof *out_counts);
   DevCall call(c, nullptr);
   if (call.rc) return call.rc;
-  hipError_t e;
   hipStream_t st = call.st;
   const size_t n = n_old;
-  Parts p;
-  const IndexParts op = index_parts(p, n, index_old_dir_bytes(n, bits_old));
-  const size_t o_r = p.take(8 * r);
-  const IndexParts np = index_parts(p, n, 4 * (size_t)index_dir_slots(bits_new));
-  const size_t o_cts = p.take(8 * kHoldersRemoveCounts);
-  if (int rc = index_io(c, p.o, st)) return rc;
-  if (int rc = holders_ws(c, (size_t)holders_remove_layout(n).bytes, st)) return rc;
-  uint8_t* io = c->ci_io.p;
-  IndexView old{};
-  if ((e = index_stage(io, op, old_keys, old_digests32, old_values, old_dir, n, bits_old, st, &old)) ||
-      (r && (e = hipMemcpyAsync(io + o_r, removed, 8 * r, hipMemcpyHostToDevice, st))))
-    return index_hip_fail(c, e, who, " H2D");
-  if ((e = holders_remove(c->ch_ws.p, old, reinterpret_cast<const uint64_t*>(io + o_r), (uint32_t)r,
-                          index_out_parts(io, np, bits_new), reinterpret_cast<unsigned long long*>(io + o_cts), st)))
-    return index_hip_fail(c, e, who, "");
   sdcas_holders_remove_counts cts;
-  if (int rc = index_fetch(c, who, io, np, o_cts, &cts, sizeof cts, &cts.entries_new, n, new_keys, new_digests32,
-                           new_values, new_dir, st))
-    return rc;
-  if ((e = hipStreamSynchronize(st))) return index_hip_fail(c, e, who, " sync");
+  Parts p(c, st, who);
+  const IndexIn old = index_in(p, old_keys, old_digests32, old_values, old_dir, n, bits_old);
+  const auto d_removed = p.in(removed, r);
+  const IndexNew nw = index_new(p, new_keys, new_digests32, new_values, new_dir, n, bits_new);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = holders_ws(c, (size_t)holders_remove_layout(n).bytes, st)) return rc;
+  if (int rc = p.upload()) return rc;
+  if (hipError_t e = holders_remove(c->ch_ws.p, old.view(), d_removed, (uint32_t)r, nw.out(),
+                                    d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  if (int rc = p.counts(d_cts)) return rc;
+  if (cts.entries_new > n) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
+  nw.first((size_t)cts.entries_new);
+  if (int rc = p.download()) return rc;
   if (out_counts) *out_counts = cts;
   return SDCAS_OK;
 }
