@@ -37,9 +37,9 @@ int sdcas_dev_profile(sdcas_ctx *ctx, int enable);
 int sdcas_dev_last_kernel_ms(sdcas_ctx *ctx, float *leaf_ms, float *total_ms);
 
 /* Tuning: select the leaf/tree kernel variant (-1 = default). Returns
- * SDCAS_OK, or SDCAS_E_INVALID (selection unchanged) for a variant this
- * build does not hold: libsdcas.so holds only the bit-exact product kernels;
- * the ablation build (libsdcas_ablate.so, tools only) holds all of them. */
+ * SDCAS_OK, or SDCAS_E_INVALID (selection unchanged) for a number that
+ * names no kernel: the library holds the leaf kernels 52, 67, 71, 73 and 84
+ * (the retired numbers of earlier A/B runs are listed in DESIGN.md). */
 int sdcas_dev_set_leaf_variant(sdcas_ctx *ctx, int variant);
 /* Tuning: select the 1 MiB-piece kernel variant of the checksum path (-1 =
  * default); same return convention. */

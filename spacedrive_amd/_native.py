@@ -3,17 +3,12 @@
 The library is the product: every hash and every dedup result comes from its
 HIP kernels. Importing this module without the built library, or calling it
 without a GPU, raises — there is no CPU fallback.
-
-`use_ablation_library()` (tools/ab_leaf.py only) binds libsdcas_ablate.so
-instead: the same sources built with every A/B kernel variant, including
-diagnostic ones that produce wrong digests. Nothing in the package calls it.
 """
 import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsdcas.so")
-ABLATION_LIB_PATH = os.path.join(_HERE, "libsdcas_ablate.so")
 
 SDCAS_OK = 0
 SDCAS_E_NO_DEVICE = -1
@@ -219,14 +214,6 @@ class HoldersRemoveCounts(ctypes.Structure):
 _lib = None
 _lib_path = LIB_PATH
 
-
-def use_ablation_library():
-    """Bind libsdcas_ablate.so (A/B tools only; see the module docstring).
-    Must be called before the first load()."""
-    global _lib_path
-    if _lib is not None and _lib_path != ABLATION_LIB_PATH:
-        raise RuntimeError("libsdcas.so is already loaded in this process")
-    _lib_path = ABLATION_LIB_PATH
 
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t

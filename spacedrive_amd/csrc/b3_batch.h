@@ -30,14 +30,14 @@ inline size_t sort_key_words(size_t max_msgs) { return kSortTotalsWords + 256 * 
 struct BatchWorkspace {
   uint64_t* S = nullptr;           // [cap_msgs] first slot of each message
   uint32_t* tile_first = nullptr;  // [cap_tiles] message owning each tile's first slot
-  uint64_t* total = nullptr;       // [4] total slots, error word, leaf tile counter
+  uint64_t* total = nullptr;       // [4] total slots, error word, 0 (once a leaf tile counter), 0
   uint32_t* nodes = nullptr;       // [cap_chunks * 8] maximal in-tile node CVs, by first slot
   void* scan_tmp = nullptr;
   size_t scan_tmp_bytes = 0;
   uint32_t cap_msgs = 0;
   uint64_t cap_chunks = 0;  // chunks a batch of up to cap_msgs messages may hold
-  uint64_t cap_slots = 0;   // slots the workspace holds (chunks + the quad layout's padding)
-  int variant = -1;  // leaf kernel variant (-1: default / SDCAS_LEAF_VARIANT; unavailable ones: default)
+  uint64_t cap_slots = 0;   // slots the workspace holds (chunks + padding)
+  int variant = -1;  // leaf kernel variant (-1: default / SDCAS_LEAF_VARIANT; a number naming no kernel: default)
   uint64_t small_slots = kSmallSlots;  // default variant: batches up to this many slots take the small kernel (0: never)
   int small_variant = kSmallVariant;   // which small-tile variant (A/B runs)
   uint64_t cap_small_tiles = 0;        // tile_first entries (the small kernel's tiles need kTile / kSmallTile times more)
@@ -53,15 +53,14 @@ struct BatchWorkspace {
 
 size_t batch_scan_temp_bytes(uint32_t max_msgs);
 int leaf_variant();
-int leaf_variant_count();
-bool leaf_variant_available(int v);  // compiled into this build (the diagnostic ones never are in libsdcas.so)
+bool leaf_variant_available(int v);  // names a leaf kernel (52, 67, 71, 73, 84)
 bool leaf_variant_forced();          // SDCAS_LEAF_VARIANT names an available variant
-bool piece_variant_available(int v);
+bool piece_variant_available(int v);  // names a piece kernel (17, 19)
 
 // A small batch's slot plan, computed by a caller that has the lengths on the
-// host (the staging path) and uploaded with them: what the scan and
-// k_tile_first would write for tiles of `tile` slots, so that batch_hash
-// launches neither; `crossing` = some message spans a tile boundary (else
+// host (the staging path) and uploaded with them: what the plan kernels
+// (k_plan_*) would write for tiles of `tile` slots, so that batch_hash
+// launches none of them; `crossing` = some message spans a tile boundary (else
 // k_finish_t has nothing to do and is not launched either). Used only for a
 // batch the kernel takes in caller order (fewer than kSortMinMsgs messages)
 // with that tile size; any other batch plans on the device.
@@ -69,12 +68,12 @@ constexpr uint32_t kSortMinMsgs = 128;  // smaller batches keep the caller's ord
 struct BatchPlan {
   const uint64_t* S = nullptr;           // device: first slot of each message
   const uint32_t* tile_first = nullptr;  // device: message owning each tile's first slot
-  uint64_t* total = nullptr;             // device: [4] total slots, 0, 0 (leaf tile counter), 0
+  uint64_t* total = nullptr;             // device: [4] total slots, 0, 0, 0
   uint32_t tile = 0;
   bool crossing = true;
 };
 // Host side of BatchPlan: S[n], tile_first[tiles] and total[4] for tiles of
-// `tile` slots (tile_first entries below cap_slots only, as k_tile_first);
+// `tile` slots (tile_first entries below cap_slots only, as k_plan_write);
 // returns the tile count and sets *crossing.
 uint64_t batch_plan_host(const uint64_t* lens, uint32_t n, uint32_t tile, uint64_t cap_slots, uint64_t* S,
                          uint32_t* tile_first, uint64_t* total, bool* crossing);
@@ -163,7 +162,8 @@ inline uint64_t bigfile_node_count(uint64_t C) {
 constexpr uint32_t kPieceDeferLevel = 4;
 // device scratch of piece_hash's l4 argument: u32 words per piece
 constexpr uint64_t kPieceL4Words = 8ull * (kTile >> kPieceDeferLevel);
-// ctr: one u32 of device scratch (the persistent variants' piece counter);
+// ctr: one u32 of device scratch, unused (the retired persistent variants'
+// piece counter; kept so that no caller changes what it allocates);
 // l4: kPieceL4Words * npieces u32 of device scratch (variant 19);
 // variant: piece kernel variant (-1: default / SDCAS_PIECE_VARIANT)
 hipError_t piece_hash(const uint8_t* blob, const PieceDesc* pieces, uint32_t npieces, uint32_t* file_nodes,

@@ -46,7 +46,7 @@ __device__ __forceinline__ uint32_t rotr(uint32_t x, uint32_t n) {
 // profiles/gsched_compress.txt, 8 waves per SIMD): the compiler's schedule of
 // B3_G (the four G's of a half-round interleaved) sustains 58 G
 // compressions/s, the block without nops 57 G/s, with a nop after each
-// v_alignbit_b32 only (B3_G_ASM_R, the block of rounds 2-6) 67 G/s, this
+// v_alignbit_b32 only (the block of rounds 2-6) 67 G/s, this
 // block 70.6 G/s. tools/ubench_isa.hip (profiles/gsched_isa.txt) shows the
 // rule behind it: in a mix of half-rate and full-rate instructions every
 // instruction costs about a half-rate issue slot unless the wave steps aside
@@ -78,117 +78,6 @@ __device__ __forceinline__ uint32_t rotr(uint32_t x, uint32_t n) {
       : "+v"(a), "+v"(b), "=&v"(c), "=&v"(d)                                                 \
       : "s"(cin), "v"(din), "v"(x), "v"(y))
 
-// The block of rounds 2-6, a nop after each v_alignbit_b32 only, kept for the
-// ablation library's A/B (compress<6>, leaf variant 95, piece variant 31).
-#define B3_G_ASM_R(a, b, c, d, x, y)                                                         \
-  asm volatile(                                                                              \
-      "v_add3_u32 %0, %0, %1, %4\n v_xor_b32 %3, %3, %0\n v_alignbit_b32 %3, %3, %3, 16\n"   \
-      " s_nop 0\n v_add_u32 %2, %2, %3\n v_xor_b32 %1, %1, %2\n"                             \
-      " v_alignbit_b32 %1, %1, %1, 12\n s_nop 0\n v_add3_u32 %0, %0, %1, %5\n"               \
-      " v_xor_b32 %3, %3, %0\n v_alignbit_b32 %3, %3, %3, 8\n s_nop 0\n"                     \
-      " v_add_u32 %2, %2, %3\n v_xor_b32 %1, %1, %2\n v_alignbit_b32 %1, %1, %1, 7\n"        \
-      " s_nop 0\n"                                                                          \
-      : "+v"(a), "+v"(b), "+v"(c), "+v"(d)                                                   \
-      : "v"(x), "v"(y))
-#define B3_G_ASM_FIRST_R(a, b, c, d, cin, din, x, y)                                         \
-  asm volatile(                                                                              \
-      "v_add3_u32 %0, %0, %1, %6\n v_xor_b32 %3, %5, %0\n v_alignbit_b32 %3, %3, %3, 16\n"   \
-      " s_nop 0\n v_add_u32 %2, %4, %3\n v_xor_b32 %1, %1, %2\n"                             \
-      " v_alignbit_b32 %1, %1, %1, 12\n s_nop 0\n v_add3_u32 %0, %0, %1, %7\n"               \
-      " v_xor_b32 %3, %3, %0\n v_alignbit_b32 %3, %3, %3, 8\n s_nop 0\n"                     \
-      " v_add_u32 %2, %2, %3\n v_xor_b32 %1, %1, %2\n v_alignbit_b32 %1, %1, %1, 7\n"        \
-      " s_nop 0\n"                                                                          \
-      : "+v"(a), "+v"(b), "=&v"(c), "=&v"(d)                                                 \
-      : "s"(cin), "v"(din), "v"(x), "v"(y))
-
-// ---- several G steps in one asm block ----------------------------------------
-//
-// The four column steps of a round are independent of one another, and so are
-// the four diagonal steps, so one block can issue the same instruction of two
-// or four G's next to each other: no instruction then reads the result of the
-// one just before it. The twelve instructions of a G as text, operands given
-// as strings ("%3"): B3_ST0 .. B3_ST11; B3_ST1F / B3_ST3F are the first column
-// step's forms, which read d and c from inputs (DIN a VGPR, CIN an SGPR or a
-// literal) and write fresh d, c.
-#define B3_ST0(A, B, C, D, X, Y) "v_add3_u32 " A ", " A ", " B ", " X "\n"
-#define B3_ST1(A, B, C, D, X, Y) "v_xor_b32 " D ", " D ", " A "\n"
-#define B3_ST2(A, B, C, D, X, Y) "v_alignbit_b32 " D ", " D ", " D ", 16\n"
-#define B3_ST3(A, B, C, D, X, Y) "v_add_u32 " C ", " C ", " D "\n"
-#define B3_ST4(A, B, C, D, X, Y) "v_xor_b32 " B ", " B ", " C "\n"
-#define B3_ST5(A, B, C, D, X, Y) "v_alignbit_b32 " B ", " B ", " B ", 12\n"
-#define B3_ST6(A, B, C, D, X, Y) "v_add3_u32 " A ", " A ", " B ", " Y "\n"
-#define B3_ST7(A, B, C, D, X, Y) B3_ST1(A, B, C, D, X, Y)
-#define B3_ST8(A, B, C, D, X, Y) "v_alignbit_b32 " D ", " D ", " D ", 8\n"
-#define B3_ST9(A, B, C, D, X, Y) B3_ST3(A, B, C, D, X, Y)
-#define B3_ST10(A, B, C, D, X, Y) B3_ST4(A, B, C, D, X, Y)
-#define B3_ST11(A, B, C, D, X, Y) "v_alignbit_b32 " B ", " B ", " B ", 7\n"
-#define B3_ST1F(A, B, C, D, X, Y, CIN, DIN) "v_xor_b32 " D ", " DIN ", " A "\n"
-#define B3_ST3F(A, B, C, D, X, Y, CIN, DIN) "v_add_u32 " C ", " CIN ", " D "\n"
-#define B3_CALL(M, ...) M(__VA_ARGS__)
-#define B3_NOP "s_nop 0\n"
-
-// Two G's: operands %0 %1 = a, %2 %3 = b, %4 %5 = c, %6 %7 = d, %8 %9 = the
-// first G's message words, %10 %11 = the second's. NI follows every
-// instruction of a pair, NP the pair.
-#define B3_G2_0 "%0", "%2", "%4", "%6", "%8", "%9"
-#define B3_G2_1 "%1", "%3", "%5", "%7", "%10", "%11"
-#define B3_P2(S, NI, NP) B3_CALL(S, B3_G2_0) NI B3_CALL(S, B3_G2_1) NI NP
-// NH: after each pair of v_add3_u32; NR: after each pair of v_alignbit_b32;
-// NRI: after each single v_alignbit_b32; NHI: after each single v_add3_u32
-#define B3_G2_TEXT(NH, NR, NRI, NHI)                                                                        \
-  B3_P2(B3_ST0, NHI, NH) B3_P2(B3_ST1, "", "") B3_P2(B3_ST2, NRI, NR) B3_P2(B3_ST3, "", "")            \
-  B3_P2(B3_ST4, "", "") B3_P2(B3_ST5, NRI, NR) B3_P2(B3_ST6, NHI, NH) B3_P2(B3_ST7, "", "")            \
-  B3_P2(B3_ST8, NRI, NR) B3_P2(B3_ST9, "", "") B3_P2(B3_ST10, "", "") B3_P2(B3_ST11, NRI, NR)
-#define B3_G2_OPS(a0, a1, b0, b1, c0, c1, d0, d1, x0, y0, x1, y1)                                      \
-  : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1), "+v"(c0), "+v"(c1), "+v"(d0), "+v"(d1)                     \
-  : "v"(x0), "v"(y0), "v"(x1), "v"(y1)
-// the first column steps: %12 %13 = c inputs (SGPRs), %14 %15 = d inputs
-#define B3_G2F_0 "%0", "%2", "%4", "%6", "%8", "%9", "%12", "%14"
-#define B3_G2F_1 "%1", "%3", "%5", "%7", "%10", "%11", "%13", "%15"
-#define B3_P2F(S, NI, NP) B3_CALL(S, B3_G2F_0) NI B3_CALL(S, B3_G2F_1) NI NP
-#define B3_G2F_TEXT(NH, NR, NRI, NHI)                                                                       \
-  B3_P2(B3_ST0, NHI, NH) B3_P2F(B3_ST1F, "", "") B3_P2(B3_ST2, NRI, NR) B3_P2F(B3_ST3F, "", "")        \
-  B3_P2(B3_ST4, "", "") B3_P2(B3_ST5, NRI, NR) B3_P2(B3_ST6, NHI, NH) B3_P2(B3_ST7, "", "")            \
-  B3_P2(B3_ST8, NRI, NR) B3_P2(B3_ST9, "", "") B3_P2(B3_ST10, "", "") B3_P2(B3_ST11, NRI, NR)
-#define B3_G2F_OPS(a0, a1, b0, b1, c0, c1, d0, d1, x0, y0, x1, y1, ci0, ci1, di0, di1)                 \
-  : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1), "=&v"(c0), "=&v"(c1), "=&v"(d0), "=&v"(d1)                 \
-  : "v"(x0), "v"(y0), "v"(x1), "v"(y1), "s"(ci0), "s"(ci1), "v"(di0), "v"(di1)
-
-// Four G's (a half-round): %0-%3 = a, %4-%7 = b, %8-%11 = c, %12-%15 = d,
-// %16 .. %23 = the message words x0 y0 x1 y1 x2 y2 x3 y3.
-#define B3_G4_0 "%0", "%4", "%8", "%12", "%16", "%17"
-#define B3_G4_1 "%1", "%5", "%9", "%13", "%18", "%19"
-#define B3_G4_2 "%2", "%6", "%10", "%14", "%20", "%21"
-#define B3_G4_3 "%3", "%7", "%11", "%15", "%22", "%23"
-#define B3_P4(S, NI, NP) \
-  B3_CALL(S, B3_G4_0) NI B3_CALL(S, B3_G4_1) NI B3_CALL(S, B3_G4_2) NI B3_CALL(S, B3_G4_3) NI NP
-#define B3_G4_TEXT(NH, NR, NRI, NHI)                                                                        \
-  B3_P4(B3_ST0, NHI, NH) B3_P4(B3_ST1, "", "") B3_P4(B3_ST2, NRI, NR) B3_P4(B3_ST3, "", "")            \
-  B3_P4(B3_ST4, "", "") B3_P4(B3_ST5, NRI, NR) B3_P4(B3_ST6, NHI, NH) B3_P4(B3_ST7, "", "")            \
-  B3_P4(B3_ST8, NRI, NR) B3_P4(B3_ST9, "", "") B3_P4(B3_ST10, "", "") B3_P4(B3_ST11, NRI, NR)
-#define B3_G4_OPS(a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3, d0, d1, d2, d3, x0, y0, x1, y1, x2, y2, x3, y3) \
-  : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(c0), "+v"(c1),         \
-    "+v"(c2), "+v"(c3), "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3)                                                  \
-  : "v"(x0), "v"(y0), "v"(x1), "v"(y1), "v"(x2), "v"(y2), "v"(x3), "v"(y3)
-// the first column steps: c from the IV words as literals (an asm statement
-// takes 30 operands at most), d from %24-%27
-#define B3_G4F_0 "%0", "%4", "%8", "%12", "%16", "%17", "0x6A09E667", "%24"
-#define B3_G4F_1 "%1", "%5", "%9", "%13", "%18", "%19", "0xBB67AE85", "%25"
-#define B3_G4F_2 "%2", "%6", "%10", "%14", "%20", "%21", "0x3C6EF372", "%26"
-#define B3_G4F_3 "%3", "%7", "%11", "%15", "%22", "%23", "0xA54FF53A", "%27"
-#define B3_P4F(S, NI, NP) \
-  B3_CALL(S, B3_G4F_0) NI B3_CALL(S, B3_G4F_1) NI B3_CALL(S, B3_G4F_2) NI B3_CALL(S, B3_G4F_3) NI NP
-#define B3_G4F_TEXT(NH, NR, NRI, NHI)                                                                       \
-  B3_P4(B3_ST0, NHI, NH) B3_P4F(B3_ST1F, "", "") B3_P4(B3_ST2, NRI, NR) B3_P4F(B3_ST3F, "", "")        \
-  B3_P4(B3_ST4, "", "") B3_P4(B3_ST5, NRI, NR) B3_P4(B3_ST6, NHI, NH) B3_P4(B3_ST7, "", "")            \
-  B3_P4(B3_ST8, NRI, NR) B3_P4(B3_ST9, "", "") B3_P4(B3_ST10, "", "") B3_P4(B3_ST11, NRI, NR)
-#define B3_G4F_OPS(a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3, d0, d1, d2, d3, x0, y0, x1, y1, x2, y2, x3, y3, \
-                   di0, di1, di2, di3)                                                                           \
-  : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "=&v"(c0), "=&v"(c1),        \
-    "=&v"(c2), "=&v"(c3), "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3)                                             \
-  : "v"(x0), "v"(y0), "v"(x1), "v"(y1), "v"(x2), "v"(y2), "v"(x3), "v"(y3), "v"(di0), "v"(di1), "v"(di2),        \
-    "v"(di3)
-
 // one round; s0..s15 = this round's message schedule (compile-time); G = the
 // G step (B3_G or B3_G_ASM)
 #define B3_ROUND_G(G, s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15) \
@@ -212,114 +101,24 @@ __device__ __forceinline__ uint32_t rotr(uint32_t x, uint32_t n) {
   B3_ROUND_G(G, 9, 14, 11, 5, 8, 12, 15, 1, 13, 3, 0, 10, 2, 6, 4, 7);    \
   B3_ROUND_G(G, 11, 15, 5, 0, 1, 9, 8, 6, 14, 10, 2, 12, 3, 4, 7, 13)
 
+#define B3_ROUND0(G) B3_ROUND_G(G, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
+
+// How a compression's G steps are scheduled: by the compiler (B3_G; a lone
+// wave issues the four independent G chains of a half-round together), or as
+// B3_G_ASM blocks with the first round's column steps as B3_G_ASM_FIRST
+// (kernels whose SIMDs hold several waves).
+enum class GSched { kCompiler, kAsmBlocks };
+
 // cv <- first 8 words of compress(cv, m, counter, block_len, flags).
 // For a ROOT compression these 8 words are the 32 digest bytes (LE words),
 // because the root's output-block counter is 0 and every root on this path
 // (a single chunk, or a parent) has counter 0 as well.
-// GA = 0: compiler-scheduled G steps; GA = 1: B3_G_ASM blocks; GA = 2:
-// B3_G_ASM with the first column steps as B3_G_ASM_FIRST.
-#define B3_ROUND0(G) B3_ROUND_G(G, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
-
-// A block of two or four G's with "s_nop 0" placed by NM: 0 nowhere, 1 after
-// each group of v_add3_u32 and of v_alignbit_b32, 2 after each group of
-// v_alignbit_b32, 3 after each single v_alignbit_b32, 4 after each single
-// v_alignbit_b32 and v_add3_u32 (every half-rate instruction).
-#define B3_NM_ASM(NM, TEXT, OPS)                                                      \
-  do {                                                                                \
-    if constexpr ((NM) == 0) asm volatile(TEXT("", "", "", "") OPS);                  \
-    else if constexpr ((NM) == 1) asm volatile(TEXT(B3_NOP, B3_NOP, "", "") OPS);     \
-    else if constexpr ((NM) == 2) asm volatile(TEXT("", B3_NOP, "", "") OPS);         \
-    else if constexpr ((NM) == 3) asm volatile(TEXT("", "", B3_NOP, "") OPS);         \
-    else asm volatile(TEXT("", "", B3_NOP, B3_NOP) OPS);                              \
-  } while (0)
-// a round as four blocks of two G's (columns 0 1, 2 3, diagonals 0 1, 2 3)
-#define B3_ROUND_G2(NM, s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15)                       \
-  do {                                                                                                             \
-    B3_NM_ASM(NM, B3_G2_TEXT, B3_G2_OPS(v0, v1, v4, v5, v8, v9, v12, v13, m[s0], m[s1], m[s2], m[s3]));            \
-    B3_NM_ASM(NM, B3_G2_TEXT, B3_G2_OPS(v2, v3, v6, v7, v10, v11, v14, v15, m[s4], m[s5], m[s6], m[s7]));          \
-    B3_NM_ASM(NM, B3_G2_TEXT, B3_G2_OPS(v0, v1, v5, v6, v10, v11, v15, v12, m[s8], m[s9], m[s10], m[s11]));        \
-    B3_NM_ASM(NM, B3_G2_TEXT, B3_G2_OPS(v2, v3, v7, v4, v8, v9, v13, v14, m[s12], m[s13], m[s14], m[s15]));        \
-  } while (0)
-// a round as two blocks of four G's (the column step, the diagonal step)
-#define B3_DIAG_G4(NM, s8, s9, s10, s11, s12, s13, s14, s15)                                                       \
-  B3_NM_ASM(NM, B3_G4_TEXT,                                                                                        \
-            B3_G4_OPS(v0, v1, v2, v3, v5, v6, v7, v4, v10, v11, v8, v9, v15, v12, v13, v14, m[s8], m[s9], m[s10],  \
-                      m[s11], m[s12], m[s13], m[s14], m[s15]))
-#define B3_ROUND_G4(NM, s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15)                       \
-  do {                                                                                                             \
-    B3_NM_ASM(NM, B3_G4_TEXT,                                                                                      \
-              B3_G4_OPS(v0, v1, v2, v3, v4, v5, v6, v7, v8, v9, v10, v11, v12, v13, v14, v15, m[s0], m[s1], m[s2], \
-                        m[s3], m[s4], m[s5], m[s6], m[s7]));                                                       \
-    B3_DIAG_G4(NM, s8, s9, s10, s11, s12, s13, s14, s15);                                                          \
-  } while (0)
-#define B3_SIX_ROUNDS_N(R, NM)                                             \
-  R(NM, 2, 6, 3, 10, 7, 0, 4, 13, 1, 11, 12, 5, 9, 14, 15, 8);            \
-  R(NM, 3, 4, 10, 12, 13, 2, 7, 14, 6, 5, 9, 0, 11, 15, 8, 1);            \
-  R(NM, 10, 7, 12, 9, 14, 3, 13, 15, 4, 0, 11, 2, 5, 8, 1, 6);            \
-  R(NM, 12, 13, 9, 11, 15, 10, 14, 8, 7, 2, 5, 3, 0, 1, 6, 4);            \
-  R(NM, 9, 14, 11, 5, 8, 12, 15, 1, 13, 3, 0, 10, 2, 6, 4, 7);            \
-  R(NM, 11, 15, 5, 0, 1, 9, 8, 6, 14, 10, 2, 12, 3, 4, 7, 13)
-
-// GA % 10 = 3: every round as blocks of two G's, 4: of four G's, the first
-// column steps copy-free as in GA 2; GA / 10 = the blocks' nop placement NM.
-// GA = 6: GA 2 with B3_G_ASM_R. GA 3, 4 and 6 are the ablation library's.
-template <int GA = 0>
+template <GSched GS = GSched::kCompiler>
 __device__ __forceinline__ void compress(uint32_t (&cv)[8], const uint32_t (&m)[16], uint64_t counter,
                                          uint32_t block_len, uint32_t flags) {
   uint32_t v0 = cv[0], v1 = cv[1], v2 = cv[2], v3 = cv[3];
   uint32_t v4 = cv[4], v5 = cv[5], v6 = cv[6], v7 = cv[7];
-  if constexpr (GA % 10 == 3 || GA % 10 == 4) {
-    constexpr int NM = GA / 10;
-    uint32_t v8, v9, v10, v11, v12, v13, v14, v15;
-    const uint32_t c_lo = (uint32_t)counter, c_hi = (uint32_t)(counter >> 32);
-    if constexpr (GA % 10 == 3) {
-      B3_NM_ASM(NM, B3_G2F_TEXT,
-                B3_G2F_OPS(v0, v1, v4, v5, v8, v9, v12, v13, m[0], m[1], m[2], m[3], IV0, IV1, c_lo, c_hi));
-      B3_NM_ASM(NM, B3_G2F_TEXT,
-                B3_G2F_OPS(v2, v3, v6, v7, v10, v11, v14, v15, m[4], m[5], m[6], m[7], IV2, IV3, block_len, flags));
-      B3_NM_ASM(NM, B3_G2_TEXT, B3_G2_OPS(v0, v1, v5, v6, v10, v11, v15, v12, m[8], m[9], m[10], m[11]));
-      B3_NM_ASM(NM, B3_G2_TEXT, B3_G2_OPS(v2, v3, v7, v4, v8, v9, v13, v14, m[12], m[13], m[14], m[15]));
-      B3_SIX_ROUNDS_N(B3_ROUND_G2, NM);
-    } else {
-      B3_NM_ASM(NM, B3_G4F_TEXT,
-                B3_G4F_OPS(v0, v1, v2, v3, v4, v5, v6, v7, v8, v9, v10, v11, v12, v13, v14, v15, m[0], m[1], m[2],
-                           m[3], m[4], m[5], m[6], m[7], c_lo, c_hi, block_len, flags));
-      B3_DIAG_G4(NM, 8, 9, 10, 11, 12, 13, 14, 15);
-      B3_SIX_ROUNDS_N(B3_ROUND_G4, NM);
-    }
-    cv[0] = v0 ^ v8;
-    cv[1] = v1 ^ v9;
-    cv[2] = v2 ^ v10;
-    cv[3] = v3 ^ v11;
-    cv[4] = v4 ^ v12;
-    cv[5] = v5 ^ v13;
-    cv[6] = v6 ^ v14;
-    cv[7] = v7 ^ v15;
-    return;
-  }
-  if constexpr (GA == 6) {  // GA 2 with the blocks of rounds 2-6 (ablation A/B)
-    uint32_t v8, v9, v10, v11, v12, v13, v14, v15;
-    const uint32_t c_lo = (uint32_t)counter, c_hi = (uint32_t)(counter >> 32);
-    B3_G_ASM_FIRST_R(v0, v4, v8, v12, IV0, c_lo, m[0], m[1]);
-    B3_G_ASM_FIRST_R(v1, v5, v9, v13, IV1, c_hi, m[2], m[3]);
-    B3_G_ASM_FIRST_R(v2, v6, v10, v14, IV2, block_len, m[4], m[5]);
-    B3_G_ASM_FIRST_R(v3, v7, v11, v15, IV3, flags, m[6], m[7]);
-    B3_G_ASM_R(v0, v5, v10, v15, m[8], m[9]);
-    B3_G_ASM_R(v1, v6, v11, v12, m[10], m[11]);
-    B3_G_ASM_R(v2, v7, v8, v13, m[12], m[13]);
-    B3_G_ASM_R(v3, v4, v9, v14, m[14], m[15]);
-    B3_SIX_ROUNDS(B3_G_ASM_R);
-    cv[0] = v0 ^ v8;
-    cv[1] = v1 ^ v9;
-    cv[2] = v2 ^ v10;
-    cv[3] = v3 ^ v11;
-    cv[4] = v4 ^ v12;
-    cv[5] = v5 ^ v13;
-    cv[6] = v6 ^ v14;
-    cv[7] = v7 ^ v15;
-    return;
-  }
-  if constexpr (GA == 2) {
+  if constexpr (GS == GSched::kAsmBlocks) {
     uint32_t v8, v9, v10, v11, v12, v13, v14, v15;
     const uint32_t c_lo = (uint32_t)counter, c_hi = (uint32_t)(counter >> 32);
     B3_G_ASM_FIRST(v0, v4, v8, v12, IV0, c_lo, m[0], m[1]);
@@ -343,13 +142,8 @@ __device__ __forceinline__ void compress(uint32_t (&cv)[8], const uint32_t (&m)[
   }
   uint32_t v8 = IV0, v9 = IV1, v10 = IV2, v11 = IV3;
   uint32_t v12 = (uint32_t)counter, v13 = (uint32_t)(counter >> 32), v14 = block_len, v15 = flags;
-  if constexpr (GA) {
-    B3_ROUND0(B3_G_ASM);
-    B3_SIX_ROUNDS(B3_G_ASM);
-  } else {
-    B3_ROUND0(B3_G);
-    B3_SIX_ROUNDS(B3_G);
-  }
+  B3_ROUND0(B3_G);
+  B3_SIX_ROUNDS(B3_G);
   cv[0] = v0 ^ v8;
   cv[1] = v1 ^ v9;
   cv[2] = v2 ^ v10;
@@ -366,7 +160,7 @@ __device__ __forceinline__ void set_iv(uint32_t (&cv)[8]) {
 }
 
 // parent node: message = left CV || right CV, counter 0, 64-byte block
-template <int GA = 0>
+template <GSched GS = GSched::kCompiler>
 __device__ __forceinline__ void parent(const uint32_t (&l)[8], const uint32_t (&r)[8], bool root,
                                        uint32_t (&out)[8]) {
   uint32_t m[16];
@@ -376,7 +170,7 @@ __device__ __forceinline__ void parent(const uint32_t (&l)[8], const uint32_t (&
     m[8 + i] = r[i];
   }
   set_iv(out);
-  compress<GA>(out, m, 0, BLOCK_LEN, PARENT | (root ? ROOT : 0u));
+  compress<GS>(out, m, 0, BLOCK_LEN, PARENT | (root ? ROOT : 0u));
 }
 
 // ---- quad-cooperative compression, for chains that wait on each compression --
@@ -532,18 +326,6 @@ __device__ __forceinline__ void parent_quad(const uint32_t (&l)[8], const uint32
 __device__ __forceinline__ void load_full_block(const uint8_t* p, uint32_t (&m)[16]) {
   const uint4* q = reinterpret_cast<const uint4*>(p);
   uint4 a = q[0], b = q[1], c = q[2], d = q[3];
-  m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w;
-  m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
-  m[8] = c.x; m[9] = c.y; m[10] = c.z; m[11] = c.w;
-  m[12] = d.x; m[13] = d.y; m[14] = d.z; m[15] = d.w;
-}
-
-// the same with non-temporal (streaming) loads: message bytes are read once
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void load_full_block_nt(const uint8_t* p, uint32_t (&m)[16]) {
-  const u32x4* q = reinterpret_cast<const u32x4*>(p);
-  u32x4 a = __builtin_nontemporal_load(q), b = __builtin_nontemporal_load(q + 1);
-  u32x4 c = __builtin_nontemporal_load(q + 2), d = __builtin_nontemporal_load(q + 3);
   m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w;
   m[4] = b.x; m[5] = b.y; m[6] = b.z; m[7] = b.w;
   m[8] = c.x; m[9] = c.y; m[10] = c.z; m[11] = c.w;

@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(256) k_dual_prep(const uint64_t* __restrict__ 
 #pragma unroll
     for (int w = 0; w < 16; ++w) m[w] = 0;
     set_iv(cv);
-    compress<0>(cv, m, 0, 0, CHUNK_START | CHUNK_END | ROOT);
+    compress<GSched::kCompiler>(cv, m, 0, 0, CHUNK_START | CHUNK_END | ROOT);
     store_digest(i, cv, out32, nullptr);
   }
   if (len > kWholeMax) {
@@ -192,7 +192,7 @@ __global__ void __launch_bounds__(kDualWG, 5)
         load_full_block(p + b * BLOCK_LEN, w);
         const uint32_t vb = clenB - b * BLOCK_LEN;  // content bytes of this block that the file holds
         if (vb < BLOCK_LEN) mask_tail_table(w, vb);
-        compress<2>(cvB, w, c, min(BLOCK_LEN, vb),
+        compress<GSched::kAsmBlocks>(cvB, w, c, min(BLOCK_LEN, vb),
                     (b == 0 ? CHUNK_START : 0u) | (b + 1 == nbB ? CHUNK_END | (rootB ? ROOT : 0u) : 0u));
       } else {
         // the cas chain's extra block: only the carried words
@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(kDualWG, 5)
         for (int i = 0; i < 16; ++i) w[i] = 0;
       }
       const uint32_t mA[16] = {k0, k1, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12], w[13]};
-      compress<2>(cvA, mA, c, min(BLOCK_LEN, clenA - b * BLOCK_LEN),
+      compress<GSched::kAsmBlocks>(cvA, mA, c, min(BLOCK_LEN, clenA - b * BLOCK_LEN),
                   (b == 0 ? CHUNK_START : 0u) | (b + 1 == nbA ? CHUNK_END | (rootA ? ROOT : 0u) : 0u));
       k0 = w[14];
       k1 = w[15];
@@ -311,7 +311,7 @@ __global__ void __launch_bounds__(kTreeWG) k_dual_tree(const uint64_t* __restric
         a[q] = cvs[l][q];
         b[q] = cvs[r][q];
       }
-      parent<2>(a, b, root, o);
+      parent<GSched::kAsmBlocks>(a, b, root, o);
       if (root) {
         store_digest(m0 + ((e >> 20) & 2047u), o, out32, out_keys);
       } else {

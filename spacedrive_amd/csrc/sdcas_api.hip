@@ -470,11 +470,12 @@ struct Parts {
 
 int reserve_ws(sdcas_ctx* c, size_t max_msgs, uint64_t max_chunks) {
   hipError_t e;
-  // the chunk scan takes an int count (hipcub)
+  // a batch's message count is an int all the way down
   if (max_msgs > SDCAS_MAX_BATCH) return c->fail(SDCAS_E_CAPACITY, "batch of %zu messages exceeds 2^31 - 1", max_msgs);
   if ((e = c->ws_S.ensure(max_msgs + 1))) return c->hip_fail(e, "workspace S");
-  // room for the quad layout's padding too: < 4 dead slots per message (of
-  // as many messages as the workspace takes)
+  // 3 slots per message (of as many as the workspace takes) and 8 more are
+  // padding no kernel fills since the quad slot layout went; they stay,
+  // because the capacities callers see derive from them
   // (rounded up, +3: cap_chunks below comes out >= max_chunks, so that
   // slots_prepare's check holds on the next call instead of re-reserving)
   const uint64_t tiles = (max_chunks + 3 * (uint64_t)(c->ws_S.cap - 1) + 8 + kTile - 1) / kTile + 3;
@@ -670,7 +671,7 @@ int slot_submit(sdcas_ctx* c, Slot& s, bool res32) {
   const bool packed = 2 * s.n <= s.cap_n;
   if (packed) memcpy(s.hm + s.n, s.lens(), 8 * s.n);
   // A batch for the small kernel in caller order is planned here and its
-  // plan goes up behind the lengths in the same copy: the scan, k_tile_first
+  // plan goes up behind the lengths in the same copy: the plan kernels
   // and (when no message crosses a tile) k_finish_t are not launched.
   uint64_t meta_words = packed ? 2 * s.n : s.n;
   const uint64_t plan_tiles = s.chunks / kSmallTile + 2;

@@ -83,39 +83,50 @@ def test_product_library_holds_only_product_kernels():
     and the small-batch kernels 84 (default since round 6, a quad of lanes
     per slot with four blocks in flight staged in LDS), 73 (a quad of lanes
     per slot) and 71, piece 19 (default: k_piece_l4 + k_piece_top) and 17, all bit-exact
-    and GPU-tested — and no ablation or DIAGNOSTIC variant (those produce
-    wrong digests and live only in libsdcas_ablate.so)"""
+    and GPU-tested — and nothing else. k_leaf_tree's arguments: threads, tile
+    slots, BlockLoop (0 computed tail mask, 1 mask table), GSched (0 compiler,
+    1 asm blocks), leaf order, first chunk kept, SlotBy (0 lane, 1 quad,
+    2 quad staged in LDS)"""
     stubs = _kernel_stubs(N.LIB_PATH)
     leaf = [s for s in stubs if s.startswith("k_leaf")]
-    assert leaf == ["k_leaf_tree<128, 79, 1, 1, 2, 2, 0, 128u, 0, 0>",
-                    "k_leaf_tree<512, 209, 1, 1, 2, 2, 0, 1024u, 0, 0>",
-                    "k_leaf_tree<512, 279, 1, 1, 2, 2, 0, 1024u, 0, 0>",
-                    "k_leaf_tree<512, 79, 1, 0, 2, 0, 0, 128u, 1, 0>",
-                    "k_leaf_tree<512, 79, 1, 0, 2, 0, 0, 128u, 3, 0>"], leaf
+    assert leaf == [
+        "k_leaf_tree<128, 128u, (sdcas::BlockLoop)1, (b3d::GSched)0, true, true, (sdcas::SlotBy)0>",     # 71
+        "k_leaf_tree<512, 1024u, (sdcas::BlockLoop)0, (b3d::GSched)1, true, true, (sdcas::SlotBy)0>",    # 52
+        "k_leaf_tree<512, 1024u, (sdcas::BlockLoop)1, (b3d::GSched)1, true, true, (sdcas::SlotBy)0>",    # 67
+        "k_leaf_tree<512, 128u, (sdcas::BlockLoop)1, (b3d::GSched)0, false, false, (sdcas::SlotBy)1>",   # 73
+        "k_leaf_tree<512, 128u, (sdcas::BlockLoop)1, (b3d::GSched)0, false, false, (sdcas::SlotBy)2>",   # 84
+    ], leaf
     finish = [s for s in stubs if s.startswith("k_finish")]
     assert finish == ["k_finish_q<1024u>", "k_finish_q<128u>", "k_finish_t<1024u>", "k_finish_t<128u>"], finish
     assert not [s for s in stubs if "slim" in s or "quad" in s]
     pieces = [s for s in stubs if s.startswith("k_piece")]
-    assert sorted(pieces) == ["k_piece_l4<259, 6>", "k_piece_top<259>", "k_piece_tree<259, 6, 1, 0, 10>"], pieces
+    assert sorted(pieces) == ["k_piece_l4", "k_piece_top", "k_piece_tree"], pieces
 
 
 def test_product_library_has_no_cub():
     """round 5: the last hipCUB / rocPRIM uses left the product library — the
     exact combine goes through the compact table (two emit passes), the
     gathered stays list is sorted by one workgroup or read back from a
-    bitmap (dist_dedup.hip); only the ablation library's quad-layout scan
-    keeps hipCUB"""
+    bitmap (dist_dedup.hip)"""
     out = subprocess.run(["nm", "-C", N.LIB_PATH], capture_output=True, text=True).stdout
     assert out and not re.search(r"hipcub|rocprim|\bcub::", out)
 
 
 def test_ablation_build_is_separate():
-    """the A/B library is a different file that no product module names"""
-    assert N.ABLATION_LIB_PATH != N.LIB_PATH
+    """there is no ablation build: no module of the package, the loader
+    included, and no source under csrc/ names one"""
+    assert not hasattr(N, "ABLATION_LIB_PATH")
     pkg = os.path.join(ROOT, "spacedrive_amd")
     for f in os.listdir(pkg):
-        if f.endswith(".py") and f != "_native.py":
+        if f.endswith(".py"):
             assert "ablat" not in open(os.path.join(pkg, f)).read(), f
+    csrc = os.path.join(pkg, "csrc")
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".o", ".so")):
+                continue
+            text = open(os.path.join(d, f), errors="replace").read()
+            assert "ablat" not in text and "SDCAS_ABLATIONS" not in text, os.path.join(d, f)
 
 
 def test_quad_message_schedules_are_blake3s():

@@ -338,31 +338,45 @@ def test_many_short_multichunk_messages(oracle, variant):
 
 
 def test_diagnostic_variants_unreachable(eng, oracle):
-    """the DIAGNOSTIC leaf variants (no memory reads / no compression / no
-    tree: wrong digests) are not in the product library: selecting one is
-    refused through the API, and the SDCAS_LEAF_VARIANT / SDCAS_PIECE_VARIANT
+    """the retired variant numbers (rounds 1-6's losing and DIAGNOSTIC
+    kernels: no memory reads / no compression / no tree, wrong digests) name
+    no kernel: selecting one is refused through the API, and the
+    SDCAS_LEAF_VARIANT / SDCAS_PIECE_VARIANT / SDCAS_SMALL_VARIANT
     environment overrides fall back to the default kernels — digests stay
     bit-exact"""
     import subprocess
     import sys
-    for v in (4, 5, 6, 7, 26, 27, 28, 39, 40, 41, 1, 25, 29, 36, 43, 46, 47, 48, 49, 50, 51, 64, 65, 66, 68):
-        assert not eng.dev_set_leaf_variant(v), v
-    for v in (4, 6, 7, 11, 14, 15, 16, 18):
-        assert not eng.dev_set_piece_variant(v), v
+    for v in range(-1 + 1, 128):
+        if v not in (52, 67, 71, 73, 84):
+            assert not eng.dev_set_leaf_variant(v), v
+    for v in range(0, 48):
+        if v not in (17, 19):
+            assert not eng.dev_set_piece_variant(v), v
     code = (
-        "import numpy as np, sys; sys.path.insert(0, %r)\n"
+        "import numpy as np, os, sys; sys.path.insert(0, %r)\n"
         "from spacedrive_amd import Engine\n"
         "from tests._oracle import load_oracle\n"
         "o = load_oracle(); rng = np.random.default_rng(3)\n"
-        "msgs = [rng.integers(0, 256, int(L), dtype=np.uint8).tobytes() for L in "
-        "list(rng.integers(0, 300000, 200)) + [3 << 20, (1 << 20) + 1]]\n"
-        "e = Engine(staging_bytes=16 << 20)\n"
-        "out = e.hash_messages(*e.pack(msgs))\n"
-        "bad = sum(bytes(d).hex() != o.hash(m) for m, d in zip(msgs, out))\n"
-        "print('bad', bad); sys.exit(1 if bad else 0)\n") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for env in ({"SDCAS_LEAF_VARIANT": "4"}, {"SDCAS_LEAF_VARIANT": "40", "SDCAS_PIECE_VARIANT": "7"}):
-        r = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, capture_output=True, text=True,
-                           timeout=100)
+        "msgs = [rng.integers(0, 256, int(L), dtype=np.uint8).tobytes() for L in %s]\n"
+        "bad = 0\n"
+        "for small in %r:\n"  # an Engine reads SDCAS_SMALL_VARIANT when it is made
+        "    if small: os.environ['SDCAS_SMALL_VARIANT'] = small\n"
+        "    e = Engine(staging_bytes=16 << 20)\n"
+        "    out = e.hash_messages(*e.pack(msgs))\n"
+        "    bad += sum(bytes(d).hex() != o.hash(m) for m, d in zip(msgs, out))\n"
+        "    e.close()\n"
+        "print('bad', bad); sys.exit(1 if bad else 0)\n")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    many = "list(rng.integers(0, 300000, 200)) + [3 << 20, (1 << 20) + 1]"
+    # eight files: below kSortMinMsgs and inside small_slots, so the
+    # small-batch rule runs — 83 and 72 are retired small-tile numbers, 67 has
+    # the big tile: each falls back to 84
+    eight = "[0, 1, 63, 64, 1024, 1025, 2049, 4096]"
+    for env, lens, smalls in (({"SDCAS_LEAF_VARIANT": "4"}, many, [None]),
+                              ({"SDCAS_LEAF_VARIANT": "40", "SDCAS_PIECE_VARIANT": "7"}, many, [None]),
+                              ({}, eight, ["83", "72", "67"])):
+        r = subprocess.run([sys.executable, "-c", code % (root, lens, smalls)], env={**os.environ, **env},
+                           capture_output=True, text=True, timeout=100)
         assert r.returncode == 0, (env, r.stdout[-500:], r.stderr[-2000:])
 
 

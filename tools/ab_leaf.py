@@ -3,9 +3,8 @@
 ONE process (cdna_hip_programming.md §5.4 rule 24). Prints per-variant median
 and min leaf-kernel ms (HIP events) and checks all variants agree bit-exactly.
 
-Binds the ablation library (libsdcas_ablate.so: `make -C spacedrive_amd/csrc
-ablate`), which holds every variant of round 1's A/B runs, the DIAGNOSTIC ones
-(wrong digests) included; --product binds libsdcas.so (product variants only)."""
+The variants are libsdcas.so's leaf kernels (52, 67, 71, 73, 84); the retired
+numbers of rounds 1-6 are listed in DESIGN.md §3."""
 import argparse
 import os
 import sys
@@ -26,13 +25,10 @@ def main():
     ap.add_argument("--align", type=int, default=128, help="message start alignment in HBM")
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c5"])
     ap.add_argument("--sorts", default="1", help="comma list of slot orders to try: 1 length-sorted, 0 caller order")
-    ap.add_argument("--product", action="store_true", help="bind libsdcas.so instead of the ablation library")
     a = ap.parse_args()
     import torch
     from spacedrive_amd import Engine
     from spacedrive_amd import _native as N
-    if not a.product:
-        N.use_ablation_library()
     dev = torch.device("cuda", 0)
     n = a.files
     sizes, keys, _ = bench.files_of(a.workload, 0, n)
@@ -41,7 +37,7 @@ def main():
     padded = (lens + A - np.uint64(1)) // A * A
     offs = np.zeros(n, np.uint64)
     offs[1:] = np.cumsum(padded[:-1])
-    total = int(offs[-1] + padded[-1]) + 64 + (1 << 17)  # + 128 KiB: diagnostic 57 reads 64 KiB past a wave base
+    total = int(offs[-1] + padded[-1]) + 64
     chunks = int(np.maximum(np.uint64(1), (lens + np.uint64(1023)) // np.uint64(1024)).sum())
     eng = Engine()
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.int64)).to(dev)
@@ -50,9 +46,9 @@ def main():
     eng.dev_reserve(n, chunks)
     sp = torch.cuda.current_stream().cuda_stream
     eng.dev_synth_cas_messages(dk.data_ptr(), ds.data_ptr(), do.data_ptr(), n, d_blob.data_ptr(), sp)
-    vl = [int(v) for v in a.variants.split(",")] if a.variants else [v for v in range(64) if eng.dev_set_leaf_variant(v)]
+    vl = [int(v) for v in a.variants.split(",")] if a.variants else [v for v in range(128) if eng.dev_set_leaf_variant(v)]
     for v in vl:
-        assert eng.dev_set_leaf_variant(v), f"variant {v} is not in {N.ABLATION_LIB_PATH if not a.product else N.LIB_PATH}"
+        assert eng.dev_set_leaf_variant(v), f"variant {v} is not in {N.LIB_PATH}"
     # an arm is (variant, sort, position): a variant named twice gives two
     # arms of identical code (A/A), whose spread is the noise of the A/B
     vs = [(v, int(so), i) for i, v in enumerate(vl) for so in a.sorts.split(",")]

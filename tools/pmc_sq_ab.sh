@@ -1,14 +1,14 @@
 #!/bin/bash
-# SQ instruction / wave-state counters of leaf variants of the ABLATION
-# library, per workload, two counter groups per run (the VALU mix; cycles,
-# LDS, SALU): tools/pmc_sq_ab.sh OUTDIR "67 78" "c2:1000000 c5:6250000"
+# SQ instruction / wave-state counters of leaf kernel variants, per
+# workload, two counter groups per run (the VALU mix; cycles,
+# LDS, SALU): tools/pmc_sq_ab.sh OUTDIR "52 67" "c2:1000000 c5:6250000"
 # Summarise with tools/pmc_sq_ab_summary.py OUTDIR.
 set -u
 OUT=${1:-gpurun_out/pmc_sq_ab}
 R=$(pwd)
 mkdir -p $OUT
 export TMPDIR=/tmp
-for V in ${2:-67 78}; do
+for V in ${2:-52 67}; do
   for WN in ${3:-c2:1000000 c5:6250000}; do
     W=${WN%%:*}; N=${WN##*:}
     PROG="python $R/tools/ab_leaf.py --rounds 1 --reps 2 --variants $V --workload $W --files $N"

@@ -24,7 +24,7 @@ N = {"c2": 1_000_000, "c3": 1_250_000, "c5": 6_250_000}
 
 def main():
     src = sys.argv[1]
-    out = {"source": f"rocprofv3 --pmc passes (tools/pmc_sq_ab.sh) over tools/ab_leaf.py (ablation library), {src}",
+    out = {"source": f"rocprofv3 --pmc passes (tools/pmc_sq_ab.sh) over tools/ab_leaf.py, {src}",
            "runs": {}}
     keys = sorted({tuple(os.path.basename(d).split("_")[1:]) for d in glob.glob(os.path.join(src, "s_*"))})
     for w, v in keys:

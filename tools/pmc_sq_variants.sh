@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ wave-state counters (one pass per leaf variant) over C2:
-# tools/pmc_sq_variants.sh OUTDIR "1 4 6 14"
+# tools/pmc_sq_variants.sh OUTDIR "52 67"
 set -u
 OUT=${1:-gpurun_out/pmc_sq}
 R=$(pwd)

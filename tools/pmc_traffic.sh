@@ -7,7 +7,7 @@ set -u
 OUT=${1:-gpurun_out/pmc_traffic}
 shift || true
 R=$(pwd)
-if [ "${1:-}" = "--" ]; then shift; PROG="$*"; else PROG="python $R/tools/ab_leaf.py --product --rounds 1 --reps 2 --variants 67"; fi
+if [ "${1:-}" = "--" ]; then shift; PROG="$*"; else PROG="python $R/tools/ab_leaf.py --rounds 1 --reps 2 --variants 67"; fi
 mkdir -p $OUT
 export TMPDIR=/tmp
 pass() {

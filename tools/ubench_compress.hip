@@ -190,8 +190,96 @@ __device__ __forceinline__ void G(uint32_t& a, uint32_t& b, uint32_t& c, uint32_
     RND(V, __VA_ARGS__) \
   }
 
-// ---- candidate schedules with several G's per asm block (b3_device.h:
-// B3_G2_TEXT, B3_G4_TEXT and their first-column forms) -----------------------
+// ---- several G steps in one asm block ----------------------------------------
+//
+// The four column steps of a round are independent of one another, and so are
+// the four diagonal steps, so one block can issue the same instruction of two
+// or four G's next to each other: no instruction then reads the result of the
+// one just before it. The twelve instructions of a G as text, operands given
+// as strings ("%3"): B3_ST0 .. B3_ST11; B3_ST1F / B3_ST3F are the first column
+// step's forms, which read d and c from inputs (DIN a VGPR, CIN an SGPR or a
+// literal) and write fresh d, c.
+#define B3_ST0(A, B, C, D, X, Y) "v_add3_u32 " A ", " A ", " B ", " X "\n"
+#define B3_ST1(A, B, C, D, X, Y) "v_xor_b32 " D ", " D ", " A "\n"
+#define B3_ST2(A, B, C, D, X, Y) "v_alignbit_b32 " D ", " D ", " D ", 16\n"
+#define B3_ST3(A, B, C, D, X, Y) "v_add_u32 " C ", " C ", " D "\n"
+#define B3_ST4(A, B, C, D, X, Y) "v_xor_b32 " B ", " B ", " C "\n"
+#define B3_ST5(A, B, C, D, X, Y) "v_alignbit_b32 " B ", " B ", " B ", 12\n"
+#define B3_ST6(A, B, C, D, X, Y) "v_add3_u32 " A ", " A ", " B ", " Y "\n"
+#define B3_ST7(A, B, C, D, X, Y) B3_ST1(A, B, C, D, X, Y)
+#define B3_ST8(A, B, C, D, X, Y) "v_alignbit_b32 " D ", " D ", " D ", 8\n"
+#define B3_ST9(A, B, C, D, X, Y) B3_ST3(A, B, C, D, X, Y)
+#define B3_ST10(A, B, C, D, X, Y) B3_ST4(A, B, C, D, X, Y)
+#define B3_ST11(A, B, C, D, X, Y) "v_alignbit_b32 " B ", " B ", " B ", 7\n"
+#define B3_ST1F(A, B, C, D, X, Y, CIN, DIN) "v_xor_b32 " D ", " DIN ", " A "\n"
+#define B3_ST3F(A, B, C, D, X, Y, CIN, DIN) "v_add_u32 " C ", " CIN ", " D "\n"
+#define B3_CALL(M, ...) M(__VA_ARGS__)
+#define B3_NOP "s_nop 0\n"
+
+// Two G's: operands %0 %1 = a, %2 %3 = b, %4 %5 = c, %6 %7 = d, %8 %9 = the
+// first G's message words, %10 %11 = the second's. NI follows every
+// instruction of a pair, NP the pair.
+#define B3_G2_0 "%0", "%2", "%4", "%6", "%8", "%9"
+#define B3_G2_1 "%1", "%3", "%5", "%7", "%10", "%11"
+#define B3_P2(S, NI, NP) B3_CALL(S, B3_G2_0) NI B3_CALL(S, B3_G2_1) NI NP
+// NH: after each pair of v_add3_u32; NR: after each pair of v_alignbit_b32;
+// NRI: after each single v_alignbit_b32; NHI: after each single v_add3_u32
+#define B3_G2_TEXT(NH, NR, NRI, NHI)                                                                        \
+  B3_P2(B3_ST0, NHI, NH) B3_P2(B3_ST1, "", "") B3_P2(B3_ST2, NRI, NR) B3_P2(B3_ST3, "", "")            \
+  B3_P2(B3_ST4, "", "") B3_P2(B3_ST5, NRI, NR) B3_P2(B3_ST6, NHI, NH) B3_P2(B3_ST7, "", "")            \
+  B3_P2(B3_ST8, NRI, NR) B3_P2(B3_ST9, "", "") B3_P2(B3_ST10, "", "") B3_P2(B3_ST11, NRI, NR)
+#define B3_G2_OPS(a0, a1, b0, b1, c0, c1, d0, d1, x0, y0, x1, y1)                                      \
+  : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1), "+v"(c0), "+v"(c1), "+v"(d0), "+v"(d1)                     \
+  : "v"(x0), "v"(y0), "v"(x1), "v"(y1)
+// the first column steps: %12 %13 = c inputs (SGPRs), %14 %15 = d inputs
+#define B3_G2F_0 "%0", "%2", "%4", "%6", "%8", "%9", "%12", "%14"
+#define B3_G2F_1 "%1", "%3", "%5", "%7", "%10", "%11", "%13", "%15"
+#define B3_P2F(S, NI, NP) B3_CALL(S, B3_G2F_0) NI B3_CALL(S, B3_G2F_1) NI NP
+#define B3_G2F_TEXT(NH, NR, NRI, NHI)                                                                       \
+  B3_P2(B3_ST0, NHI, NH) B3_P2F(B3_ST1F, "", "") B3_P2(B3_ST2, NRI, NR) B3_P2F(B3_ST3F, "", "")        \
+  B3_P2(B3_ST4, "", "") B3_P2(B3_ST5, NRI, NR) B3_P2(B3_ST6, NHI, NH) B3_P2(B3_ST7, "", "")            \
+  B3_P2(B3_ST8, NRI, NR) B3_P2(B3_ST9, "", "") B3_P2(B3_ST10, "", "") B3_P2(B3_ST11, NRI, NR)
+#define B3_G2F_OPS(a0, a1, b0, b1, c0, c1, d0, d1, x0, y0, x1, y1, ci0, ci1, di0, di1)                 \
+  : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1), "=&v"(c0), "=&v"(c1), "=&v"(d0), "=&v"(d1)                 \
+  : "v"(x0), "v"(y0), "v"(x1), "v"(y1), "s"(ci0), "s"(ci1), "v"(di0), "v"(di1)
+
+// Four G's (a half-round): %0-%3 = a, %4-%7 = b, %8-%11 = c, %12-%15 = d,
+// %16 .. %23 = the message words x0 y0 x1 y1 x2 y2 x3 y3.
+#define B3_G4_0 "%0", "%4", "%8", "%12", "%16", "%17"
+#define B3_G4_1 "%1", "%5", "%9", "%13", "%18", "%19"
+#define B3_G4_2 "%2", "%6", "%10", "%14", "%20", "%21"
+#define B3_G4_3 "%3", "%7", "%11", "%15", "%22", "%23"
+#define B3_P4(S, NI, NP) \
+  B3_CALL(S, B3_G4_0) NI B3_CALL(S, B3_G4_1) NI B3_CALL(S, B3_G4_2) NI B3_CALL(S, B3_G4_3) NI NP
+#define B3_G4_TEXT(NH, NR, NRI, NHI)                                                                        \
+  B3_P4(B3_ST0, NHI, NH) B3_P4(B3_ST1, "", "") B3_P4(B3_ST2, NRI, NR) B3_P4(B3_ST3, "", "")            \
+  B3_P4(B3_ST4, "", "") B3_P4(B3_ST5, NRI, NR) B3_P4(B3_ST6, NHI, NH) B3_P4(B3_ST7, "", "")            \
+  B3_P4(B3_ST8, NRI, NR) B3_P4(B3_ST9, "", "") B3_P4(B3_ST10, "", "") B3_P4(B3_ST11, NRI, NR)
+#define B3_G4_OPS(a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3, d0, d1, d2, d3, x0, y0, x1, y1, x2, y2, x3, y3) \
+  : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(c0), "+v"(c1),         \
+    "+v"(c2), "+v"(c3), "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3)                                                  \
+  : "v"(x0), "v"(y0), "v"(x1), "v"(y1), "v"(x2), "v"(y2), "v"(x3), "v"(y3)
+// the first column steps: c from the IV words as literals (an asm statement
+// takes 30 operands at most), d from %24-%27
+#define B3_G4F_0 "%0", "%4", "%8", "%12", "%16", "%17", "0x6A09E667", "%24"
+#define B3_G4F_1 "%1", "%5", "%9", "%13", "%18", "%19", "0xBB67AE85", "%25"
+#define B3_G4F_2 "%2", "%6", "%10", "%14", "%20", "%21", "0x3C6EF372", "%26"
+#define B3_G4F_3 "%3", "%7", "%11", "%15", "%22", "%23", "0xA54FF53A", "%27"
+#define B3_P4F(S, NI, NP) \
+  B3_CALL(S, B3_G4F_0) NI B3_CALL(S, B3_G4F_1) NI B3_CALL(S, B3_G4F_2) NI B3_CALL(S, B3_G4F_3) NI NP
+#define B3_G4F_TEXT(NH, NR, NRI, NHI)                                                                       \
+  B3_P4(B3_ST0, NHI, NH) B3_P4F(B3_ST1F, "", "") B3_P4(B3_ST2, NRI, NR) B3_P4F(B3_ST3F, "", "")        \
+  B3_P4(B3_ST4, "", "") B3_P4(B3_ST5, NRI, NR) B3_P4(B3_ST6, NHI, NH) B3_P4(B3_ST7, "", "")            \
+  B3_P4(B3_ST8, NRI, NR) B3_P4(B3_ST9, "", "") B3_P4(B3_ST10, "", "") B3_P4(B3_ST11, NRI, NR)
+#define B3_G4F_OPS(a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3, d0, d1, d2, d3, x0, y0, x1, y1, x2, y2, x3, y3, \
+                   di0, di1, di2, di3)                                                                           \
+  : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "=&v"(c0), "=&v"(c1),        \
+    "=&v"(c2), "=&v"(c3), "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3)                                             \
+  : "v"(x0), "v"(y0), "v"(x1), "v"(y1), "v"(x2), "v"(y2), "v"(x3), "v"(y3), "v"(di0), "v"(di1), "v"(di2),        \
+    "v"(di3)
+
+// ---- candidate schedules with several G's per asm block (B3_G2_TEXT,
+// B3_G4_TEXT and their first-column forms, above) -----------------------------
 // MODE 0: no nop; 1: s_nop 0 after each pair (group) of half-rate ops, add3
 // and rotate; 2: after each pair (group) of rotates only; 3: after each single
 // rotate; 4: after each single rotate and each single add3 (every half-rate

@@ -107,16 +107,16 @@ __global__ void __launch_bounds__(WG, 6) k_stream(const uint8_t* __restrict__ bu
         for (int k = 0; k < 4; ++k)
           __builtin_amdgcn_global_load_lds((const void*)(wbase + (size_t)(16 * k + c16) * 1024 + b * 64 + 64 + piece * 16),
                                            (__attribute__((address_space(3))) void*)(wl + k * 1024), 16, 0, 0);
-        compress<2>(cv, m0, chunk, 64, b == 0 ? CHUNK_START : 0u);
+        compress<GSched::kAsmBlocks>(cv, m0, chunk, 64, b == 0 ? CHUNK_START : 0u);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
         for (int k = 0; k < 4; ++k) put(m1, k, myl[k]);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        compress<2>(cv, m1, chunk, 64, b + 2 == 16 ? CHUNK_END : 0u);
+        compress<GSched::kAsmBlocks>(cv, m1, chunk, 64, b + 2 == 16 ? CHUNK_END : 0u);
         continue;
       }
-      compress<2>(cv, m0, chunk, 64, b == 0 ? CHUNK_START : 0u);
-      compress<2>(cv, m1, chunk, 64, b + 2 == 16 ? CHUNK_END : 0u);
+      compress<GSched::kAsmBlocks>(cv, m0, chunk, 64, b == 0 ? CHUNK_START : 0u);
+      compress<GSched::kAsmBlocks>(cv, m1, chunk, 64, b + 2 == 16 ? CHUNK_END : 0u);
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc ^= cv[i] * (i + 1);
