@@ -1027,6 +1027,111 @@ int sdcas_dev_chunk_holders_remove(sdcas_ctx *ctx, const uint64_t *d_old_keys, c
                                    uint8_t *d_new_digests32, uint64_t *d_new_values, uint32_t *d_new_dir,
                                    uint32_t bits_new, uint64_t *d_counts, void *stream);
 
+/* ---- chunk peers: the files that hold most of a file's bytes --------------------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * sdcas_chunk_sharing credits each shared chunk to ONE file, its origin (the
+ * lowest holder), which was all a chunk index could say. A holders index keeps
+ * every holder, and this call reads them: for a batch's chunks it computes,
+ * per batch file, the bytes it shares with EVERY file that holds any of them,
+ * and returns the top k files per file. Of three versions of a log with ids
+ * 1 < 2 < 3, v1 = A, v2 = A B, v3 = A B C, sharing reports v1 (|A| bytes) for
+ * v3; here v3's first peer is v2 with |A| + |B|. The call sits beside
+ * sdcas_chunk_sharing (the new / self / other byte split is still that call's)
+ * and changes no index.
+ *   inputs   a holders index (idx_keys, idx_digests32, idx_values, idx_dir, n,
+ *            bits: its limits, alignments and directory clamping); a batch of m
+ *            chunks (keys, digests32, valid: NULL means all valid,
+ *            chunk_file[m] u32, chunk_len[m] u64); file_ids[n_files] u64, the id
+ *            each batch file has in the index; k in [1, 64]; max_holders H in
+ *            [1, 2^20]; mode; max_pairs. A chunk takes no part when it is not
+ *            valid or chunk_file[c] >= n_files.
+ *   modes    SDCAS_PEERS_EARLIER: the COUNTED holders of chunk c of file i are
+ *            the entries of c's pair whose value is BELOW file_ids[i];
+ *            SDCAS_PEERS_ALL: the entries whose value is NOT EQUAL to it. Both
+ *            are contiguous pieces of the pair's run: its two ends and the
+ *            place of (key, digest, file_ids[i]) in it are found by halving, so
+ *            cnt(c), their number, costs three halvings and no thread walks a
+ *            run.
+ *   common   a chunk with cnt(c) > H is COMMON (the zero chunk of sparse files,
+ *            a template header): it scores for nobody and its length goes to
+ *            out_common_bytes[i]. A definition, not a fallback: it bounds the
+ *            expansion and keeps ubiquitous content from deciding the nearest
+ *            file. In EARLIER mode cnt looks only at ids below the file's own,
+ *            so a file's result does not depend on which later files the index
+ *            already holds.
+ *   score    S(i, f) = the sum, modulo 2^64, of chunk_len[c] over i's
+ *            participating chunks that are not common and of which f is a
+ *            counted holder; a chunk that occurs twice in i counts twice. The
+ *            PEERS of i are the f with at least one such chunk, ordered by (S
+ *            descending, f ascending as u64); the first k are returned.
+ *   outputs  out_peer_count[n_files] u32: min(k, the number of peers);
+ *            out_peers[n_files * k] and out_peer_bytes[n_files * k] u64: row i
+ *            in peer order, slots past the count 0; out_shared_bytes[i]: the
+ *            bytes of i's chunks with 1 <= cnt <= H, out_unique_bytes[i]: of
+ *            those with cnt == 0, out_common_bytes[i]: of the common ones.
+ *            shared + unique + common is the sum of i's participating chunk
+ *            lengths modulo 2^64. Any output may be NULL; every slot of a given
+ *            array is written, so two calls give the same bytes.
+ *   capacity the expansion holds max_pairs (chunk, holder) pairs. With P, the
+ *            sum of cnt over the chunks that are not common, above max_pairs
+ *            the device form sets overflow, writes every peer_count as 0 and
+ *            zeroes the peer rows; the three byte arrays and the counts other
+ *            than edges and files_with_peer are still exact. The host form then
+ *            returns SDCAS_E_CAPACITY (its outputs written as the device
+ *            form's).
+ * SDCAS_E_INVALID for k, H or mode out of range, a needed NULL array or a
+ * misalignment; SDCAS_E_CAPACITY for m > 2^30, n > 2^30, bits > 28, n_files >
+ * 2^32 - 2 or max_pairs > 2^30: all before anything is enqueued. Results are
+ * exact and do not depend on scheduling. */
+#define SDCAS_PEERS_EARLIER 0u
+#define SDCAS_PEERS_ALL 1u
+#define SDCAS_PEERS_MAX_K 64u
+#define SDCAS_PEERS_MAX_HOLDERS (1u << 20)
+#define SDCAS_PEERS_MAX_PAIRS (1ull << 30)
+typedef struct sdcas_peers_counts {
+  uint64_t files;           /* n_files */
+  uint64_t chunks;          /* participating chunks */
+  uint64_t common_chunks;
+  uint64_t pairs;           /* P */
+  uint64_t edges;           /* distinct (i, f) with a scoring chunk; 0 on overflow */
+  uint64_t files_with_peer; /* 0 on overflow */
+  uint64_t overflow;        /* 1: P > max_pairs */
+} sdcas_peers_counts;
+/* GPU-free, like sdcas_chunk_plan: the range checks above (k, H; m, n_files),
+ * *out_max_pairs = min(m * H, 2^30), the bound that can never overflow, and
+ * *out_workspace_bytes = what the device call takes for that many pairs (16
+ * bytes per chunk, 57 per pair). Either output may be NULL. */
+int sdcas_chunk_peers_plan(uint64_t m, uint64_t n_files, uint32_t k, uint32_t max_holders, uint64_t *out_max_pairs,
+                           uint64_t *out_workspace_bytes);
+/* Host arrays; max_pairs == 0 means the plan's bound. One upload of the index
+ * and the batch, the device call, one download. */
+int sdcas_chunk_peers(sdcas_ctx *ctx, const uint64_t *idx_keys, const uint8_t *idx_digests32,
+                      const uint64_t *idx_values, const uint32_t *idx_dir, uint64_t n, uint32_t bits,
+                      const uint64_t *keys, const uint8_t *digests32, const uint8_t *valid,
+                      const uint32_t *chunk_file, const uint64_t *chunk_len, size_t m, const uint64_t *file_ids,
+                      size_t n_files, uint32_t k, uint32_t max_holders, uint32_t mode, uint64_t max_pairs,
+                      uint32_t *out_peer_count, uint64_t *out_peers, uint64_t *out_peer_bytes,
+                      uint64_t *out_shared_bytes, uint64_t *out_unique_bytes, uint64_t *out_common_bytes,
+                      sdcas_peers_counts *out_counts);
+/* Device arrays under sdcas_dev_chunk_holders_match's stream and alignment
+ * rules; d_chunk_file and d_out_peer_count 4-byte aligned, d_file_ids,
+ * d_chunk_len and the u64 outputs 8-byte. max_pairs is taken as given (0 holds
+ * no pair). d_counts: seven u64 in sdcas_peers_counts' order, overwritten. The
+ * workspace for (m, max_pairs) is allocated by the first call that needs it,
+ * which waits for the stream; after that the call never waits for the device.
+ * Every grid is sized from m, n_files and max_pairs: P and the edges stay on
+ * the device, the two orders take ceil_log2(max_pairs) merge passes each. */
+int sdcas_dev_chunk_peers(sdcas_ctx *ctx, const uint64_t *d_idx_keys, const uint8_t *d_idx_digests32,
+                          const uint64_t *d_idx_values, const uint32_t *d_idx_dir, uint64_t n, uint32_t bits,
+                          const uint64_t *d_keys, const uint8_t *d_digests32, const uint8_t *d_valid,
+                          const uint32_t *d_chunk_file, const uint64_t *d_chunk_len, size_t m,
+                          const uint64_t *d_file_ids, size_t n_files, uint32_t k, uint32_t max_holders,
+                          uint32_t mode, uint64_t max_pairs, uint32_t *d_out_peer_count, uint64_t *d_out_peers,
+                          uint64_t *d_out_peer_bytes, uint64_t *d_out_shared_bytes, uint64_t *d_out_unique_bytes,
+                          uint64_t *d_out_common_bytes, uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

@@ -48,6 +48,11 @@ SDCAS_INDEX_MAX_BITS = 28
 SDCAS_INDEX_HIT = 1
 SDCAS_INDEX_ADDED = 2
 SDCAS_INDEX_SKIPPED = 4
+SDCAS_PEERS_EARLIER = 0
+SDCAS_PEERS_ALL = 1
+SDCAS_PEERS_MAX_K = 64
+SDCAS_PEERS_MAX_HOLDERS = 1 << 20
+SDCAS_PEERS_MAX_PAIRS = 1 << 30
 
 # every entry point include/sdcas.h and include/sdcas_bench.h declare
 ABI_SYMBOLS = [
@@ -67,6 +72,7 @@ ABI_SYMBOLS = [
     "sdcas_chunk_holders_check", "sdcas_chunk_holders_match", "sdcas_dev_chunk_holders_match",
     "sdcas_chunk_holders_add", "sdcas_dev_chunk_holders_add", "sdcas_chunk_holders_remove",
     "sdcas_dev_chunk_holders_remove",  # added after ABI 7
+    "sdcas_chunk_peers_plan", "sdcas_chunk_peers", "sdcas_dev_chunk_peers",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -211,6 +217,16 @@ class HoldersRemoveCounts(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class PeersCounts(ctypes.Structure):
+    """sdcas_peers_counts"""
+    _fields_ = [("files", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("common_chunks", ctypes.c_uint64),
+                ("pairs", ctypes.c_uint64), ("edges", ctypes.c_uint64), ("files_with_peer", ctypes.c_uint64),
+                ("overflow", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _lib_path = LIB_PATH
 
@@ -309,6 +325,11 @@ def load():
                                              ctypes.POINTER(HoldersRemoveCounts)]
     L.sdcas_dev_chunk_holders_remove.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _sz, _vp, _vp, _vp, _vp,
                                                  _u32, _vp, _vp]
+    L.sdcas_chunk_peers_plan.argtypes = [_u64, _u64, _u32, _u32, _vp, _vp]
+    L.sdcas_chunk_peers.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _u32,
+                                    _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(PeersCounts)]
+    L.sdcas_dev_chunk_peers.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz,
+                                        _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

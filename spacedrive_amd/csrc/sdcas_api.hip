@@ -35,6 +35,7 @@
 #include "dirtree.h"
 #include "cdc.h"
 #include "chunk_holders.h"
+#include "chunk_peers.h"
 #include "chunk_index.h"
 #include "dist_dedup.h"
 #include "synth.h"
@@ -231,6 +232,8 @@ struct sdcas_ctx {
   DevBuf<uint8_t> ci_ws;
   // the holders index (chunk_holders.hip): the add's and the remove's workspace
   DevBuf<uint8_t> ch_ws;
+  // the chunk peers (chunk_peers.hip): the runs, the expansion and the edges
+  DevBuf<uint8_t> cp_ws;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -3137,6 +3140,133 @@ int sdcas_chunk_holders_remove(sdcas_ctx* c, const uint64_t* old_keys, const uin
   nw.first((size_t)cts.entries_new);
   if (int rc = p.download()) return rc;
   if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+// ---- the chunk peers (chunk_peers.hip) ------------------------------------------------
+
+// the request's ranges, GPU-free: SDCAS_OK, or the code with *why set
+static int peers_range(uint64_t m, uint64_t n_files, uint32_t k, uint32_t max_holders, uint64_t max_pairs,
+                       const char** why) {
+  static_assert(SDCAS_PEERS_MAX_K == kPeersMaxK && SDCAS_PEERS_MAX_HOLDERS == kPeersMaxHolders &&
+                    SDCAS_PEERS_MAX_PAIRS == kPeersMaxPairs && SDCAS_PEERS_EARLIER == kPeersEarlier &&
+                    SDCAS_PEERS_ALL == kPeersAll,
+                "peers limits");
+  if (k < 1 || k > kPeersMaxK) return *why = "k is not in [1, 64]", SDCAS_E_INVALID;
+  if (max_holders < 1 || max_holders > kPeersMaxHolders) return *why = "max_holders is not in [1, 2^20]", SDCAS_E_INVALID;
+  if (m > kIndexMaxEntries) return *why = "a batch of more than 2^30 chunks", SDCAS_E_CAPACITY;
+  if (n_files >= 0xFFFFFFFFull) return *why = "more than 2^32 - 2 files", SDCAS_E_CAPACITY;
+  if (max_pairs > kPeersMaxPairs) return *why = "max_pairs exceeds 2^30", SDCAS_E_CAPACITY;
+  return SDCAS_OK;
+}
+
+int sdcas_chunk_peers_plan(uint64_t m, uint64_t n_files, uint32_t k, uint32_t max_holders, uint64_t* out_max_pairs,
+                           uint64_t* out_workspace_bytes) {
+  const char* why = nullptr;
+  if (int rc = peers_range(m, n_files, k, max_holders, 0, &why)) return rc;
+  const uint64_t q = peers_pair_bound(m, max_holders);
+  if (out_max_pairs) *out_max_pairs = q;
+  if (out_workspace_bytes) *out_workspace_bytes = peers_layout(m, q).bytes;
+  return SDCAS_OK;
+}
+
+// a call's arguments (host or device arrays): the ranges, then the arrays it needs
+static int peers_args(sdcas_ctx* c, const char* who, const void* idx_keys, const void* idx_digests, const void* idx_dir,
+                      uint64_t n, uint32_t bits, const void* keys, const void* digests, const void* chunk_file,
+                      const void* chunk_len, size_t m, const void* file_ids, size_t n_files, uint32_t k,
+                      uint32_t max_holders, uint32_t mode, uint64_t max_pairs) {
+  const char* why = nullptr;
+  if (mode != kPeersEarlier && mode != kPeersAll) return c->fail(SDCAS_E_INVALID, "%s: unknown mode %u", who, mode);
+  if (int rc = peers_range(m, n_files, k, max_holders, max_pairs, &why)) return c->fail(rc, "%s: %s", who, why);
+  if (int rc = index_view_args(c, who, idx_keys, idx_digests, idx_dir, n, bits)) return rc;
+  if (int rc = index_batch_args(c, who, keys, digests, m)) return rc;
+  if (m && (!chunk_file || !chunk_len)) return c->fail(SDCAS_E_INVALID, "%s: null chunk_file or chunk_len", who);
+  if (m && n_files && !file_ids) return c->fail(SDCAS_E_INVALID, "%s: null file_ids", who);
+  return SDCAS_OK;
+}
+
+int sdcas_dev_chunk_peers(sdcas_ctx* c, const uint64_t* d_idx_keys, const uint8_t* d_idx_digests32,
+                          const uint64_t* d_idx_values, const uint32_t* d_idx_dir, uint64_t n, uint32_t bits,
+                          const uint64_t* d_keys, const uint8_t* d_digests32, const uint8_t* d_valid,
+                          const uint32_t* d_chunk_file, const uint64_t* d_chunk_len, size_t m,
+                          const uint64_t* d_file_ids, size_t n_files, uint32_t k, uint32_t max_holders, uint32_t mode,
+                          uint64_t max_pairs, uint32_t* d_out_peer_count, uint64_t* d_out_peers,
+                          uint64_t* d_out_peer_bytes, uint64_t* d_out_shared_bytes, uint64_t* d_out_unique_bytes,
+                          uint64_t* d_out_common_bytes, uint64_t* d_counts, void* stream) {
+  const char* who = "dev_chunk_peers";
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = peers_args(c, who, d_idx_keys, d_idx_digests32, d_idx_dir, n, bits, d_keys, d_digests32, d_chunk_file,
+                          d_chunk_len, m, d_file_ids, n_files, k, max_holders, mode, max_pairs))
+    return rc;
+  if (index_misaligned({d_idx_digests32, d_digests32},
+                       {d_idx_keys, d_idx_values, d_keys, d_chunk_len, d_file_ids, d_out_peers, d_out_peer_bytes,
+                        d_out_shared_bytes, d_out_unique_bytes, d_out_common_bytes, d_counts},
+                       {d_idx_dir, d_chunk_file, d_out_peer_count}))
+    return c->fail(SDCAS_E_INVALID,
+                   "%s: an array is misaligned (digests 16 B, directory, chunk_file and peer_count 4 B, others 8 B)", who);
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = grow_synced(c, c->cp_ws, (size_t)peers_layout(m, max_pairs).bytes, call.st, "chunk peers workspace"))
+    return rc;
+  const IndexView v{d_idx_keys, d_idx_digests32, d_idx_values, d_idx_dir, (uint32_t)n, bits};
+  const PeersIn in{d_keys, d_digests32, d_valid, d_chunk_file, d_chunk_len, d_file_ids, (uint32_t)m,
+                   (uint32_t)n_files, k, max_holders, mode};
+  const PeersOut out{d_out_peer_count, d_out_peers, d_out_peer_bytes, d_out_shared_bytes, d_out_unique_bytes,
+                     d_out_common_bytes};
+  hipError_t e = chunk_peers(c->cp_ws.p, v, in, (uint32_t)max_pairs, out, (unsigned long long*)d_counts, call.st);
+  return e ? hip_fail_at(c, e, who, "") : SDCAS_OK;
+}
+
+int sdcas_chunk_peers(sdcas_ctx* c, const uint64_t* idx_keys, const uint8_t* idx_digests32, const uint64_t* idx_values,
+                      const uint32_t* idx_dir, uint64_t n, uint32_t bits, const uint64_t* keys,
+                      const uint8_t* digests32, const uint8_t* valid, const uint32_t* chunk_file,
+                      const uint64_t* chunk_len, size_t m, const uint64_t* file_ids, size_t n_files, uint32_t k,
+                      uint32_t max_holders, uint32_t mode, uint64_t max_pairs, uint32_t* out_peer_count,
+                      uint64_t* out_peers, uint64_t* out_peer_bytes, uint64_t* out_shared_bytes,
+                      uint64_t* out_unique_bytes, uint64_t* out_common_bytes, sdcas_peers_counts* out_counts) {
+  static_assert(sizeof(sdcas_peers_counts) == kPeersCounts * sizeof(uint64_t), "seven u64 counts");
+  const char* who = "chunk_peers";
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = peers_args(c, who, idx_keys, idx_digests32, idx_dir, n, bits, keys, digests32, chunk_file, chunk_len, m,
+                          file_ids, n_files, k, max_holders, mode, max_pairs))
+    return rc;
+  if (!max_pairs) max_pairs = peers_pair_bound(m, max_holders);
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  const size_t nf = n_files;
+  sdcas_peers_counts cts;
+  Parts p(c, st, who);
+  const IndexIn idx = index_in(p, idx_keys, idx_digests32, idx_values, idx_dir, n, bits);
+  const auto d_keys = p.in(keys, m);
+  const auto d_digests = p.in(digests32, 32 * m);
+  const auto d_valid = p.in(valid, m);
+  const auto d_file = p.in(chunk_file, m);
+  const auto d_len = p.in(chunk_len, m);
+  const auto d_ids = p.in(file_ids, nf);
+  const auto d_pc = p.out(out_peer_count, nf);
+  const auto d_peers = p.out(out_peers, nf * k);
+  const auto d_pb = p.out(out_peer_bytes, nf * k);
+  const auto d_shared = p.out(out_shared_bytes, nf);
+  const auto d_unique = p.out(out_unique_bytes, nf);
+  const auto d_common = p.out(out_common_bytes, nf);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = grow_synced(c, c->cp_ws, (size_t)peers_layout(m, max_pairs).bytes, st, "chunk peers workspace"))
+    return rc;
+  if (int rc = p.upload()) return rc;
+  const PeersIn in{d_keys, d_digests, d_valid, d_file, d_len, d_ids, (uint32_t)m, (uint32_t)n_files, k, max_holders,
+                   mode};
+  const PeersOut out{d_pc, d_peers, d_pb, d_shared, d_unique, d_common};
+  if (hipError_t e = chunk_peers(c->cp_ws.p, idx.view(), in, (uint32_t)max_pairs, out,
+                                 d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  if (int rc = p.download()) return rc;
+  if (out_counts) *out_counts = cts;
+  if (cts.overflow)
+    return c->fail(SDCAS_E_CAPACITY, "%s: %llu (chunk, holder) pairs exceed max_pairs %llu", who,
+                   (unsigned long long)cts.pairs, (unsigned long long)max_pairs);
   return SDCAS_OK;
 }
 

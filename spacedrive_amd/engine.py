@@ -876,7 +876,62 @@ class Engine:
         e = int(counts.entries_new)
         return (nk[:e].copy(), nd[:e].copy(), nv[:e].copy(), ndir, bits_new), counts.as_dict()
 
-    def similar_files_indexed(self, paths, file_ids, index, params=None, window_bytes=256 << 20):
+    # -- chunk peers: per file, the top-k files by shared bytes over every holder ------
+    @staticmethod
+    def _peers_mode(mode):
+        try:
+            return {"earlier": N.SDCAS_PEERS_EARLIER, "all": N.SDCAS_PEERS_ALL}[mode]
+        except (KeyError, TypeError):
+            return int(mode)
+
+    @staticmethod
+    def chunk_peers_plan(m, n_files, k, max_holders):
+        """sdcas_chunk_peers_plan (no GPU) -> (max_pairs: min(m * max_holders,
+        2^30), the bound that cannot overflow, workspace_bytes: what the device
+        call takes for that many pairs); SdcasError beyond the ranges"""
+        pairs, ws = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = N.load().sdcas_chunk_peers_plan(int(m), int(n_files), int(k), int(max_holders), ctypes.byref(pairs),
+                                             ctypes.byref(ws))
+        if rc != N.SDCAS_OK:
+            raise N.SdcasError(rc, f"chunk_peers_plan({m}, {n_files}, k={k}, max_holders={max_holders})")
+        return int(pairs.value), int(ws.value)
+
+    def chunk_peers(self, index, keys, digests, chunk_file, chunk_len, file_ids, k=4, max_holders=64, mode="earlier",
+                    valid=None, max_pairs=0):
+        """sdcas_chunk_peers over host arrays; index as for chunk_holders_match,
+        the batch as for chunk_sharing plus its keys and digests, file_ids
+        uint64[n_files]: the id each batch file has in the index. mode
+        "earlier": a chunk's counted holders are the index's entries below the
+        file's own id, "all": every entry but the file's own; a chunk with more
+        than max_holders of them is common and scores for nobody. max_pairs 0:
+        the plan's bound. -> dict: "peer_count" uint32[n], "peers" uint64[n, k]
+        (by bytes descending, then id ascending; unused slots 0), "peers_bytes"
+        uint64[n, k], "shared_bytes", "unique_bytes", "common_bytes" uint64[n],
+        "counts": sdcas_peers_counts' seven fields. SdcasError
+        (SDCAS_E_CAPACITY) when the pairs exceed max_pairs."""
+        ik, idg, iv, idir, bits = self._index_arrays(index, "chunk_peers")
+        keys, digests, va = self._index_batch(keys, digests, valid, "chunk_peers")
+        m = keys.size
+        fl, ln, ids = _arr(chunk_file, np.uint32), _arr(chunk_len, np.uint64), _arr(file_ids, np.uint64)
+        if fl.size != m or ln.size != m:
+            raise ValueError(f"chunk_peers: {m} keys, {fl.size} chunk files, {ln.size} chunk lengths")
+        n, k = ids.size, int(k)
+        if not 1 <= k <= N.SDCAS_PEERS_MAX_K:
+            raise N.SdcasError(N.SDCAS_E_INVALID, f"chunk_peers: k = {k}")
+        cnt, peers, pb = np.zeros(n, np.uint32), np.zeros((n, k), np.uint64), np.zeros((n, k), np.uint64)
+        shared, unique, common = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        counts = N.PeersCounts()
+        self._check(self.L.sdcas_chunk_peers(self.ctx, _ptr(ik), _ptr(idg), _ptr(iv), _ptr(idir), ik.size, bits,
+                                             _ptr(keys), _ptr(digests), _ptr(va), _ptr(fl), _ptr(ln), m, _ptr(ids), n,
+                                             k, int(max_holders), self._peers_mode(mode), int(max_pairs),
+                                             cnt.ctypes.data, peers.ctypes.data, pb.ctypes.data, shared.ctypes.data,
+                                             unique.ctypes.data, common.ctypes.data, ctypes.byref(counts)),
+                    "sdcas_chunk_peers")
+        return {"peer_count": cnt, "peers": peers, "peers_bytes": pb, "shared_bytes": shared, "unique_bytes": unique,
+                "common_bytes": common, "counts": counts.as_dict()}
+
+    def similar_files_indexed(self, paths, file_ids, index, params=None, window_bytes=256 << 20, peers=0,
+                              max_holders=64):
         """similar_files_streamed against what earlier calls stored: the files
         are chunked through chunk_stream, their chunks confirmed within the
         batch, matched against `index` (a ChunkIndex or a ChunkHolders) and
@@ -892,8 +947,31 @@ class Engine:
         For ids ascending in scan order and any split of the files into
         consecutive calls on one index that started empty, the per-file
         results are similar_files_streamed's over all the files at once, with
-        its peer mapped through the ids."""
+        its peer mapped through the ids.
+
+        peers=k > 0 (a ChunkHolders only; ValueError with a ChunkIndex) adds,
+        after the add and still on the index's stream, ChunkHolders.peers in
+        "earlier" mode over the batch's device arrays: "peers" uint64[n, k]
+        (the k files below the file's own id that hold most of its bytes,
+        counting EVERY holder of a chunk, not only its origin; by bytes
+        descending, then id ascending; unused slots 0), "peers_bytes"
+        uint64[n, k], "peer_count" uint32[n], "shared_bytes", "common_bytes"
+        (chunks with more than max_holders counted holders score for nobody)
+        and "peers_counts". `peer` answers "the lowest holder of most of my
+        chunks", peers[:, 0] "the file that holds most of my bytes": of three
+        versions of a growing log the third's peer is the first, its first
+        peer the second. The same law holds for these keys (but
+        "peers_counts", which is per call): for ids ascending in scan order
+        and any split of the files into consecutive calls on a holders index
+        that started empty, every file's rows equal those of one call over all
+        the files — in "earlier" mode a file's result does not depend on which
+        later files the index holds — and after remove(R) the rows of the later
+        batches equal those of one run over the survivors and those batches.
+        With peers=0 the calls and the dict are what they were."""
         import torch
+
+        if peers and not isinstance(index, ChunkHolders):
+            raise ValueError("similar_files_indexed: peers needs a ChunkHolders (ChunkHolders.from_index converts)")
 
         paths = [os.fspath(p) for p in paths]
         n = len(paths)
@@ -926,6 +1004,9 @@ class Engine:
             d_pos, d_val, mcounts = index._match_dev(d_keys, d_dig, None)
             rep, hit, val = d_rep.cpu().numpy(), d_pos.cpu().numpy() >= 0, d_val.cpu().numpy().view(np.uint64)
             acounts = index._add_dev(d_keys, d_dig, index._upload(ids[fl], np.int64), None)[2]
+            near = index._peers_dev(d_keys, d_dig, None, index._upload(fl, np.int32), index._upload(ln, np.int64),
+                                    index._upload(ids, np.int64), n, int(peers), int(max_holders),
+                                    N.SDCAS_PEERS_EARLIER) if peers else None
         # One pseudo-chunk of length 0 per chunk that is its pair's lowest in
         # the batch and hits the index, in front of the batch's chunks, owned
         # by a pseudo file that stands for the stored owner: a batch chunk with
@@ -945,10 +1026,15 @@ class Engine:
         indexed = np.zeros(n, np.uint64)
         np.add.at(indexed, fl[hit], ln[hit])
         peer = peer[ordinal]
-        return {"sizes": sizes, "new_bytes": new[ordinal], "self_bytes": own[ordinal], "other_bytes": other[ordinal],
-                "indexed_bytes": indexed, "peer": np.where(peer >= 0, all_ids[np.maximum(peer, 0)].astype(np.int64), -1),
-                "peer_bytes": peer_bytes[ordinal], "chunk_counts": ccounts, "match_counts": mcounts,
-                "add_counts": acounts}
+        out = {"sizes": sizes, "new_bytes": new[ordinal], "self_bytes": own[ordinal], "other_bytes": other[ordinal],
+               "indexed_bytes": indexed, "peer": np.where(peer >= 0, all_ids[np.maximum(peer, 0)].astype(np.int64), -1),
+               "peer_bytes": peer_bytes[ordinal], "chunk_counts": ccounts, "match_counts": mcounts,
+               "add_counts": acounts}
+        if near is not None:
+            out.update({"peers": near["peers"], "peers_bytes": near["peers_bytes"], "peer_count": near["peer_count"],
+                        "shared_bytes": near["shared_bytes"], "common_bytes": near["common_bytes"],
+                        "peers_counts": near["counts"]})
+        return out
 
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
     def dev_chunk_index_match(self, idx_keys, idx_digests, idx_values, idx_dir, n, bits, keys, digests, valid, m,
@@ -1014,6 +1100,24 @@ class Engine:
                                                           new_digests or None, new_values or None, new_dir or None,
                                                           int(bits_new), counts or None, stream or None),
                     "dev_chunk_holders_remove")
+
+    def dev_chunk_peers(self, idx_keys, idx_digests, idx_values, idx_dir, n, bits, keys, digests, valid, chunk_file,
+                        chunk_len, m, file_ids, n_files, k, max_holders, mode, max_pairs, peer_count=0, peers=0,
+                        peer_bytes=0, shared_bytes=0, unique_bytes=0, common_bytes=0, counts=0, stream=0):
+        """chunk_peers over device arrays (sdcas_dev_chunk_peers); idx_values,
+        valid and any output may be 0; chunk_file uint32[m], peer_count
+        uint32[n_files], peers and peer_bytes uint64[n_files * k], counts seven
+        uint64. max_pairs is taken as given: beyond it the counts' overflow is
+        1 and the peer rows are zero. Nothing waits for the device once the
+        workspace for (m, max_pairs) exists"""
+        self._check(self.L.sdcas_dev_chunk_peers(self.ctx, idx_keys or None, idx_digests or None, idx_values or None,
+                                                 idx_dir or None, int(n), int(bits), keys or None, digests or None,
+                                                 valid or None, chunk_file or None, chunk_len or None, int(m),
+                                                 file_ids or None, int(n_files), int(k), int(max_holders),
+                                                 self._peers_mode(mode), int(max_pairs), peer_count or None,
+                                                 peers or None, peer_bytes or None, shared_bytes or None,
+                                                 unique_bytes or None, common_bytes or None, counts or None,
+                                                 stream or None), "dev_chunk_peers")
 
     def dev_chunk_windows(self, blob, offs, lens, final, n, max_chunks, max_slots, params=None, file_chunks=0,
                           chunk_off=0, chunk_len=0, chunk_file=0, keys=0, digests=0, consumed=0, counts=0, stream=0):
@@ -1360,7 +1464,9 @@ class ChunkHolders(ChunkIndex):
     sorted by that triple, and so can forget files again. `match` gives a
     pair's lowest holder and the number of its holders; `add` merges the
     batch's unseen triples; `remove(file_ids)` streams the index through once
-    and leaves, byte for byte, the index built from the files that remain.
+    and leaves, byte for byte, the index built from the files that remain;
+    `peers` reads the holders between a run's two ends: per batch file, the k
+    files that hold most of its bytes.
 
     The tensors, the stream, `load` and the `_upload` / `_match_dev` /
     `_add_dev` contract are ChunkIndex's (here `_add_dev` merges the batch's
@@ -1396,6 +1502,60 @@ class ChunkHolders(ChunkIndex):
             pos, value, holders, counts = self._match_holders_dev(d_keys, d_dig, d_valid)
             return (pos.cpu().numpy(), value.cpu().numpy().view(np.uint64), holders.cpu().numpy().view(np.uint32),
                     counts)
+
+    # -- peers ----------------------------------------------------------------------
+    def _peers_dev(self, d_keys, d_digests, d_valid, d_file, d_len, d_ids, n_files, k, max_holders, mode,
+                   max_pairs=None):
+        """device tensors in (d_file int32[m]: the uint32's bits, d_len and
+        d_ids int64), the outputs on the host -> Engine.chunk_peers' dict.
+        max_pairs None: a first call without outputs and without room counts
+        the pairs (its `pairs` is exact whatever the room), the second takes
+        exactly that many, so the workspace follows the batch's pairs and not
+        m * max_holders; reading the counts is the wait, once per call"""
+        import torch
+        m, n, k = d_keys.numel(), int(n_files), int(k)
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else 0
+        with torch.cuda.stream(self.stream):
+            counts = torch.zeros(7, dtype=torch.int64, device=self.device)
+            args = (p(self.keys), p(self.digests), p(self.values), p(self.dir), self.n, self.bits, p(d_keys),
+                    p(d_digests), p(d_valid), p(d_file), p(d_len), m, p(d_ids), n, k, int(max_holders), mode)
+            if max_pairs is None:
+                self.engine.dev_chunk_peers(*args, 0, counts=counts.data_ptr(), stream=self.stream.cuda_stream)
+                max_pairs = int(counts.cpu()[3])
+                if max_pairs > N.SDCAS_PEERS_MAX_PAIRS:
+                    raise N.SdcasError(N.SDCAS_E_CAPACITY, f"ChunkHolders.peers: {max_pairs} (chunk, holder) pairs")
+            cnt = torch.empty(n, dtype=torch.int32, device=self.device)
+            peers = torch.empty(n * k, dtype=torch.int64, device=self.device)
+            pb = torch.empty(n * k, dtype=torch.int64, device=self.device)
+            shared, unique, common = (torch.empty(n, dtype=torch.int64, device=self.device) for _ in range(3))
+            self.engine.dev_chunk_peers(*args, max_pairs, p(cnt), p(peers), p(pb), p(shared), p(unique), p(common),
+                                        counts.data_ptr(), stream=self.stream.cuda_stream)
+            c = dict(zip((name for name, _ in N.PeersCounts._fields_), (int(v) for v in counts.cpu())))
+            u64 = lambda t: t.cpu().numpy().view(np.uint64)
+            out = {"peer_count": cnt.cpu().numpy().view(np.uint32), "peers": u64(peers).reshape(n, k),
+                   "peers_bytes": u64(pb).reshape(n, k), "shared_bytes": u64(shared), "unique_bytes": u64(unique),
+                   "common_bytes": u64(common), "counts": c}
+        if c["overflow"]:
+            raise N.SdcasError(N.SDCAS_E_CAPACITY,
+                               f"ChunkHolders.peers: {c['pairs']} (chunk, holder) pairs exceed max_pairs {max_pairs}")
+        return out
+
+    def peers(self, keys, digests, chunk_file, chunk_len, file_ids, k=4, max_holders=64, mode="earlier", valid=None,
+              max_pairs=None):
+        """only the batch goes up; on the index's stream -> Engine.chunk_peers'
+        dict: per batch file the k files of the index that hold most of its
+        bytes, over EVERY holder of its chunks. file_ids[i] is the id file i
+        has (or would have) in the index; mode "earlier" counts the holders
+        below it, "all" every holder but itself. The index is not changed."""
+        import torch
+        fl, ln, ids = _arr(chunk_file, np.uint32), _arr(chunk_len, np.uint64), _arr(file_ids, np.uint64)
+        with torch.cuda.stream(self.stream):
+            d_keys, d_dig, d_valid = self._batch(keys, digests, valid, "ChunkHolders.peers")
+            if fl.size != d_keys.numel() or ln.size != d_keys.numel():
+                raise ValueError(f"ChunkHolders.peers: {d_keys.numel()} keys, {fl.size} chunk files, {ln.size} lengths")
+            return self._peers_dev(d_keys, d_dig, d_valid, self._upload(fl, np.int32), self._upload(ln, np.int64),
+                                   self._upload(ids, np.int64), ids.size, k, max_holders,
+                                   Engine._peers_mode(mode), max_pairs)
 
     # -- remove ---------------------------------------------------------------------
     def remove(self, file_ids, bits_new=None):
