@@ -1132,6 +1132,85 @@ int sdcas_dev_chunk_peers(sdcas_ctx *ctx, const uint64_t *d_idx_keys, const uint
                           uint64_t *d_out_peer_bytes, uint64_t *d_out_shared_bytes, uint64_t *d_out_unique_bytes,
                           uint64_t *d_out_common_bytes, uint64_t *d_counts, void *stream);
 
+/* ---- file families: the files that are versions of one another -----------------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * sdcas_chunk_peers answers, once per file, "which k files hold most of this
+ * file's bytes". Twelve versions of a log come back as twelve rows that point
+ * at each other. This call is the group-by over those rows: the FAMILY of a
+ * file is its connected component in the graph whose edges are the peer slots
+ * that pass a shared-bytes threshold. It changes no index.
+ *   inputs   n rows, one per file: ids[n] u64, the file id of row i, STRICTLY
+ *            ASCENDING (the law of ids in scan order; it makes id -> row one
+ *            lower bound by halving, with no sort); sizes[n] u64;
+ *            peer_count[n] u32, peers[n * k] and peer_bytes[n * k] u64: exactly
+ *            sdcas_dev_chunk_peers' out_peer_count, out_peers and
+ *            out_peer_bytes; k in [1, SDCAS_PEERS_MAX_K]; a threshold num / den,
+ *            both u32, den >= 1 and num <= den.
+ *   slots    row i has min(peer_count[i], k) slots; slots past that count are
+ *            never read. Slot (i, s) names f = peers[i * k + s] with b =
+ *            peer_bytes[i * k + s] and is exactly one of
+ *              missing  f is not in ids (a removed file, a file outside the rows)
+ *              self     f == ids[i]
+ *              weak     f is row j, and b == 0 or
+ *                       b * den < num * max(sizes[i], sizes[j])
+ *              link     f is row j, b > 0 and
+ *                       b * den >= num * max(sizes[i], sizes[j])
+ *            The comparison is exact: the products reach 2^96 and are compared
+ *            in 128 bits. The size is the LARGER of the two: a small file
+ *            embedded in a large archive does not join the archive's family,
+ *            which is the "versions of one file" meaning. num = 0 links every
+ *            slot with b > 0.
+ *   family   the links, taken as undirected edges, partition the rows into
+ *            components. out_family[i] (int64) is the LOWEST ROW INDEX of i's
+ *            component; a file with no link has out_family[i] == i. The array
+ *            is a valid rep for sdcas_dev_duplicate_sets, and a family is a
+ *            set there. out_family_size[i] (u32) is the number of rows of i's
+ *            component.
+ *   unsorted the device form checks the order of ids on the device; where it
+ *            is broken it sets unsorted = 1, writes out_family[i] = i and
+ *            out_family_size[i] = 1, and every count but files and unsorted is
+ *            0: no garbage and no host wait. The host form checks on the host
+ *            before anything is uploaded and returns SDCAS_E_INVALID.
+ * SDCAS_E_INVALID for k, num or den out of range, a needed NULL array or a
+ * misalignment (8 bytes for u64 and int64, 4 for u32); SDCAS_E_CAPACITY for n >
+ * 2^30: all before anything is enqueued. n == 0 is SDCAS_OK with zero counts.
+ * Any output may be NULL; every slot of a given output is written. Results are
+ * exact and do not depend on scheduling: the lowest index of a component is a
+ * property of the graph, the sizes and counts are sums and a maximum. */
+typedef struct sdcas_families_counts {
+  uint64_t files;      /* n */
+  uint64_t slots;      /* slots read */
+  uint64_t missing;    /* slots classed missing */
+  uint64_t self_slots; /* slots classed self */
+  uint64_t weak;       /* slots classed weak */
+  uint64_t links;      /* directed slots that link; a pair that lists each other counts twice */
+  uint64_t families;   /* components with at least 2 rows */
+  uint64_t members;    /* rows in those components */
+  uint64_t largest;    /* rows in the largest family, 0 when there is none */
+  uint64_t unsorted;   /* 1: ids is not strictly ascending */
+} sdcas_families_counts;
+/* GPU-free: the range checks above (k, n) and *out_workspace_bytes = what the
+ * device call takes (8 bytes per row and a little). The output may be NULL. */
+int sdcas_file_families_plan(uint64_t n, uint32_t k, uint64_t *out_workspace_bytes);
+/* Host arrays: one upload, the device call, one download. */
+int sdcas_file_families(sdcas_ctx *ctx, const uint64_t *ids, const uint64_t *sizes, const uint32_t *peer_count,
+                        const uint64_t *peers, const uint64_t *peer_bytes, size_t n, uint32_t k, uint32_t num,
+                        uint32_t den, int64_t *out_family, uint32_t *out_family_size,
+                        sdcas_families_counts *out_counts);
+/* Device arrays under sdcas_dev_chunk_peers' stream rules. d_counts: ten u64 in
+ * sdcas_families_counts' order, overwritten. The workspace for n is allocated
+ * by the first call that needs it, which waits for the stream; after that the
+ * call never waits for the device. Every grid is sized from n and the labels
+ * are flattened by ceil_log2(n) launches, whatever the data; inside the union
+ * kernel a thread's search for a root follows the depth of the forest at that
+ * moment. */
+int sdcas_dev_file_families(sdcas_ctx *ctx, const uint64_t *d_ids, const uint64_t *d_sizes,
+                            const uint32_t *d_peer_count, const uint64_t *d_peers, const uint64_t *d_peer_bytes,
+                            size_t n, uint32_t k, uint32_t num, uint32_t den, int64_t *d_out_family,
+                            uint32_t *d_out_family_size, uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

@@ -73,6 +73,7 @@ ABI_SYMBOLS = [
     "sdcas_chunk_holders_add", "sdcas_dev_chunk_holders_add", "sdcas_chunk_holders_remove",
     "sdcas_dev_chunk_holders_remove",  # added after ABI 7
     "sdcas_chunk_peers_plan", "sdcas_chunk_peers", "sdcas_dev_chunk_peers",  # added after ABI 7
+    "sdcas_file_families_plan", "sdcas_file_families", "sdcas_dev_file_families",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -227,6 +228,17 @@ class PeersCounts(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class FamiliesCounts(ctypes.Structure):
+    """sdcas_families_counts"""
+    _fields_ = [("files", ctypes.c_uint64), ("slots", ctypes.c_uint64), ("missing", ctypes.c_uint64),
+                ("self_slots", ctypes.c_uint64), ("weak", ctypes.c_uint64), ("links", ctypes.c_uint64),
+                ("families", ctypes.c_uint64), ("members", ctypes.c_uint64), ("largest", ctypes.c_uint64),
+                ("unsorted", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _lib_path = LIB_PATH
 
@@ -330,6 +342,10 @@ def load():
                                     _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(PeersCounts)]
     L.sdcas_dev_chunk_peers.argtypes = [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz,
                                         _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.sdcas_file_families_plan.argtypes = [_u64, _u32, _vp]
+    L.sdcas_file_families.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _vp,
+                                      ctypes.POINTER(FamiliesCounts)]
+    L.sdcas_dev_file_families.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _vp, _vp, _vp]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

@@ -36,6 +36,7 @@
 #include "cdc.h"
 #include "chunk_holders.h"
 #include "chunk_peers.h"
+#include "families.h"
 #include "chunk_index.h"
 #include "dist_dedup.h"
 #include "synth.h"
@@ -234,6 +235,8 @@ struct sdcas_ctx {
   DevBuf<uint8_t> ch_ws;
   // the chunk peers (chunk_peers.hip): the runs, the expansion and the edges
   DevBuf<uint8_t> cp_ws;
+  // the file families (families.hip): the forest, the sizes, the flags and the sums
+  DevBuf<uint8_t> ff_ws;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -3267,6 +3270,91 @@ int sdcas_chunk_peers(sdcas_ctx* c, const uint64_t* idx_keys, const uint8_t* idx
   if (cts.overflow)
     return c->fail(SDCAS_E_CAPACITY, "%s: %llu (chunk, holder) pairs exceed max_pairs %llu", who,
                    (unsigned long long)cts.pairs, (unsigned long long)max_pairs);
+  return SDCAS_OK;
+}
+
+// ---- the file families (families.hip) -------------------------------------------------
+
+// the request's ranges, GPU-free: SDCAS_OK, or the code with *why set
+static int families_range(uint64_t n, uint32_t k, const char** why) {
+  static_assert(kFamiliesMaxFiles == (1ull << 30) && kFamiliesMaxPasses == 30, "families limits");
+  if (k < 1 || k > kPeersMaxK) return *why = "k is not in [1, 64]", SDCAS_E_INVALID;
+  if (n > kFamiliesMaxFiles) return *why = "more than 2^30 files", SDCAS_E_CAPACITY;
+  return SDCAS_OK;
+}
+
+int sdcas_file_families_plan(uint64_t n, uint32_t k, uint64_t* out_workspace_bytes) {
+  const char* why = nullptr;
+  if (int rc = families_range(n, k, &why)) return rc;
+  if (out_workspace_bytes) *out_workspace_bytes = families_layout(n).bytes;
+  return SDCAS_OK;
+}
+
+// a call's arguments (host or device arrays): the ranges, then the arrays it needs
+static int families_args(sdcas_ctx* c, const char* who, const void* ids, const void* sizes, const void* peer_count,
+                         const void* peers, const void* peer_bytes, size_t n, uint32_t k, uint32_t num, uint32_t den) {
+  const char* why = nullptr;
+  if (int rc = families_range(n, k, &why)) return c->fail(rc, "%s: %s", who, why);
+  if (den < 1 || num > den) return c->fail(SDCAS_E_INVALID, "%s: the threshold %u / %u is not in [0, 1]", who, num, den);
+  if (n && (!ids || !sizes || !peer_count || !peers || !peer_bytes))
+    return c->fail(SDCAS_E_INVALID, "%s: null ids, sizes, peer_count, peers or peer_bytes", who);
+  return SDCAS_OK;
+}
+
+int sdcas_dev_file_families(sdcas_ctx* c, const uint64_t* d_ids, const uint64_t* d_sizes, const uint32_t* d_peer_count,
+                            const uint64_t* d_peers, const uint64_t* d_peer_bytes, size_t n, uint32_t k, uint32_t num,
+                            uint32_t den, int64_t* d_out_family, uint32_t* d_out_family_size, uint64_t* d_counts,
+                            void* stream) {
+  const char* who = "dev_file_families";
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = families_args(c, who, d_ids, d_sizes, d_peer_count, d_peers, d_peer_bytes, n, k, num, den)) return rc;
+  if (index_misaligned({}, {d_ids, d_sizes, d_peers, d_peer_bytes, d_out_family, d_counts},
+                       {d_peer_count, d_out_family_size}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (peer_count and family_size 4 B, others 8 B)", who);
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = grow_synced(c, c->ff_ws, (size_t)families_layout(n).bytes, call.st, "file families workspace")) return rc;
+  const FamiliesIn in{d_ids, d_sizes, d_peer_count, d_peers, d_peer_bytes, (uint32_t)n, k, num, den};
+  hipError_t e = file_families(c->ff_ws.p, in, d_out_family, d_out_family_size, (unsigned long long*)d_counts, call.st);
+  return e ? hip_fail_at(c, e, who, "") : SDCAS_OK;
+}
+
+int sdcas_file_families(sdcas_ctx* c, const uint64_t* ids, const uint64_t* sizes, const uint32_t* peer_count,
+                        const uint64_t* peers, const uint64_t* peer_bytes, size_t n, uint32_t k, uint32_t num,
+                        uint32_t den, int64_t* out_family, uint32_t* out_family_size,
+                        sdcas_families_counts* out_counts) {
+  static_assert(sizeof(sdcas_families_counts) == kFamiliesCounts * sizeof(uint64_t), "ten u64 counts");
+  const char* who = "file_families";
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = families_args(c, who, ids, sizes, peer_count, peers, peer_bytes, n, k, num, den)) return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  // the order the device form checks on the device, here before anything is uploaded
+  for (size_t i = 1; i < n; ++i)
+    if (!(ids[i - 1] < ids[i])) {
+      if (out_counts) out_counts->files = n, out_counts->unsorted = 1;
+      return c->fail(SDCAS_E_INVALID, "%s: ids are not strictly ascending at row %zu", who, i);
+    }
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  sdcas_families_counts cts;
+  Parts p(c, st, who);
+  const auto d_ids = p.in(ids, n);
+  const auto d_sizes = p.in(sizes, n);
+  const auto d_pc = p.in(peer_count, n);
+  const auto d_peers = p.in(peers, n * k);
+  const auto d_pb = p.in(peer_bytes, n * k);
+  const auto d_family = p.out(out_family, n);
+  const auto d_fs = p.out(out_family_size, n);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = grow_synced(c, c->ff_ws, (size_t)families_layout(n).bytes, st, "file families workspace")) return rc;
+  if (int rc = p.upload()) return rc;
+  const FamiliesIn in{d_ids, d_sizes, d_pc, d_peers, d_pb, (uint32_t)n, k, num, den};
+  if (hipError_t e = file_families(c->ff_ws.p, in, d_family, d_fs, d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  if (int rc = p.download()) return rc;
+  if (out_counts) *out_counts = cts;
   return SDCAS_OK;
 }
 

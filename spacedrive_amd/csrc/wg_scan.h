@@ -37,4 +37,29 @@ __device__ __forceinline__ void wg_scan_exclusive_1024(uint32_t* __restrict__ cn
   if (tid == 0) *total = carry;
 }
 
+// Called by every thread of ONE workgroup of at most 1024: the sums of a and b
+// and the maximum of c over the workgroup, valid in thread 0 alone (families.hip's
+// k_ff_write: one atomic per workgroup and count behind it).
+__device__ __forceinline__ void wg_reduce_sum2_max(unsigned long long& a, unsigned long long& b,
+                                                   unsigned long long& c) {
+  __shared__ unsigned long long rs[3][16];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (uint32_t d = 32; d; d >>= 1) {
+    a += __shfl_down(a, d);
+    b += __shfl_down(b, d);
+    const unsigned long long t = __shfl_down(c, d);
+    c = t > c ? t : c;
+  }
+  if (lane == 0) rs[0][wave] = a, rs[1][wave] = b, rs[2][wave] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t waves = (blockDim.x + 63) >> 6;
+    for (uint32_t w = 1; w < waves; ++w) {
+      a += rs[0][w], b += rs[1][w];
+      c = rs[2][w] > c ? rs[2][w] : c;
+    }
+  }
+}
+
 }  // namespace sdcas

@@ -1036,6 +1036,75 @@ class Engine:
                         "peers_counts": near["counts"]})
         return out
 
+    # -- file families: the connected components of the peer rows ---------------------
+    @staticmethod
+    def file_families_plan(n, k):
+        """sdcas_file_families_plan (no GPU) -> workspace_bytes: what the device
+        call takes for n rows; SdcasError beyond the ranges"""
+        ws = ctypes.c_uint64(0)
+        rc = N.load().sdcas_file_families_plan(int(n), int(k), ctypes.byref(ws))
+        if rc != N.SDCAS_OK:
+            raise N.SdcasError(rc, f"file_families_plan({n}, k={k})")
+        return int(ws.value)
+
+    def file_families(self, ids, sizes, peer_count, peers, peer_bytes, num=1, den=2, sets=False):
+        """sdcas_file_families over host arrays: ids uint64[n] strictly
+        ascending, sizes uint64[n], and chunk_peers' "peer_count" uint32[n],
+        "peers" and "peers_bytes" uint64[n, k] as they are. A slot links row i
+        and the row j of its peer when it shares b > 0 bytes with b * den >=
+        num * max(sizes[i], sizes[j]); the default 1/2, "half of the larger
+        file", is a documented choice, not a measurement. -> dict: "family"
+        int64[n] (the lowest row of the row's component), "family_size"
+        uint32[n], "counts": sdcas_families_counts' ten fields. sets=True adds
+        duplicate_sets(family, None, SDCAS_SETS_BY_REP): "set_rep",
+        "set_offsets" and "members", one set per family of two rows or more.
+        SdcasError (SDCAS_E_INVALID) when ids is not strictly ascending."""
+        ids, sz, pc = _arr(ids, np.uint64), _arr(sizes, np.uint64), _arr(peer_count, np.uint32)
+        pe, pb = np.ascontiguousarray(peers, np.uint64), np.ascontiguousarray(peer_bytes, np.uint64)
+        n = ids.size
+        if sz.size != n or pc.size != n:
+            raise ValueError(f"file_families: {n} ids, {sz.size} sizes, {pc.size} peer counts")
+        if pe.shape != pb.shape or pe.ndim != 2 or pe.shape[0] != n:
+            raise ValueError(f"file_families: peers {pe.shape} and peer bytes {pb.shape} are not both [{n}, k]")
+        k = int(pe.shape[1])
+        if not 1 <= k <= N.SDCAS_PEERS_MAX_K:
+            raise N.SdcasError(N.SDCAS_E_INVALID, f"file_families: k = {k}")
+        family, fsize = np.zeros(n, np.int64), np.zeros(n, np.uint32)
+        counts = N.FamiliesCounts()
+        self._check(self.L.sdcas_file_families(self.ctx, _ptr(ids), _ptr(sz), _ptr(pc), _ptr(pe.reshape(-1)),
+                                               _ptr(pb.reshape(-1)), n, k, int(num), int(den), family.ctypes.data,
+                                               fsize.ctypes.data, ctypes.byref(counts)), "sdcas_file_families")
+        out = {"family": family, "family_size": fsize, "counts": counts.as_dict()}
+        if sets:
+            set_rep, set_offsets, _, members, _ = self.duplicate_sets(family, None, N.SDCAS_SETS_BY_REP)
+            out.update({"set_rep": set_rep, "set_offsets": set_offsets, "members": members})
+        return out
+
+    def families_of(self, results, file_ids, num=1, den=2):
+        """the families over consecutive similar_files_indexed(..., peers=k)
+        calls: `results` their dicts and `file_ids` their id arrays, in call
+        order (ids ascending throughout, one k throughout; a removed file's
+        row dropped from both). Concatenates "sizes", "peer_count", "peers" and
+        "peers_bytes" and calls file_families(..., sets=True); rows are numbered
+        in that order. A peer id that is no longer listed is a missing slot."""
+        results, file_ids = list(results), [_arr(x, np.uint64) for x in file_ids]
+        if len(results) != len(file_ids):
+            raise ValueError(f"families_of: {len(results)} results, {len(file_ids)} id arrays")
+        for r in results:
+            if "peers" not in r:
+                raise ValueError("families_of: a result has no peers (similar_files_indexed(..., peers=k))")
+        ks = {int(np.asarray(r["peers"]).shape[1]) for r in results}
+        if len(ks) > 1:
+            raise ValueError(f"families_of: the results have different k: {sorted(ks)}")
+        k = ks.pop() if ks else 1
+
+        def cat(key, dtype, *tail):
+            return np.concatenate([np.zeros((0,) + tail, dtype)] +
+                                  [np.asarray(r[key], dtype).reshape((-1,) + tail) for r in results])
+        ids = np.concatenate([np.zeros(0, np.uint64)] + file_ids)
+        return self.file_families(ids, cat("sizes", np.uint64), cat("peer_count", np.uint32), cat("peers", np.uint64, k),
+                                  cat("peers_bytes", np.uint64, k), num, den, sets=True)
+
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
     def dev_chunk_index_match(self, idx_keys, idx_digests, idx_values, idx_dir, n, bits, keys, digests, valid, m,
                               pos=0, value=0, counts=0, stream=0):
@@ -1118,6 +1187,19 @@ class Engine:
                                                  peers or None, peer_bytes or None, shared_bytes or None,
                                                  unique_bytes or None, common_bytes or None, counts or None,
                                                  stream or None), "dev_chunk_peers")
+
+    def dev_file_families(self, ids, sizes, peer_count, peers, peer_bytes, n, k, num=1, den=2, family=0, family_size=0,
+                          counts=0, stream=0):
+        """file_families over device arrays (sdcas_dev_file_families), e.g.
+        dev_chunk_peers' peer_count / peers / peer_bytes as they are; family
+        int64[n] (a rep for dev_duplicate_sets), family_size uint32[n], counts
+        ten uint64; any output may be 0. ids that are not strictly ascending
+        give the trivial rows and the counts' unsorted = 1. Nothing waits for
+        the device once the workspace for n exists"""
+        self._check(self.L.sdcas_dev_file_families(self.ctx, ids or None, sizes or None, peer_count or None,
+                                                   peers or None, peer_bytes or None, int(n), int(k), int(num),
+                                                   int(den), family or None, family_size or None, counts or None,
+                                                   stream or None), "dev_file_families")
 
     def dev_chunk_windows(self, blob, offs, lens, final, n, max_chunks, max_slots, params=None, file_chunks=0,
                           chunk_off=0, chunk_len=0, chunk_file=0, keys=0, digests=0, consumed=0, counts=0, stream=0):
