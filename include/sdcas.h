@@ -1211,6 +1211,111 @@ int sdcas_dev_file_families(sdcas_ctx *ctx, const uint64_t *d_ids, const uint64_
                             size_t n, uint32_t k, uint32_t num, uint32_t den, int64_t *d_out_family,
                             uint32_t *d_out_family_size, uint64_t *d_counts, void *stream);
 
+/* ---- family bytes: what a family's versions store and give back -----------------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * sdcas_file_families says that twelve versions of a log are one family. This
+ * call says what the twelve cost, what keeping each chunk once gives back, and
+ * which family to look at first: sdcas_chunk_sharing's accounting INSIDE every
+ * family, and the families that have two rows or more ranked by the bytes they
+ * give back, in the shape of sdcas_duplicate_sets. A chunk that two unrelated
+ * files happen to share is reclaimed for neither family.
+ *   inputs   sdcas_chunk_sharing's and a label per file: chunk_file[m] u32, the
+ *            file of chunk c; chunk_len[m] u64; rep[m] int64,
+ *            sdcas_confirm_duplicates' out_rep over the chunks; family[n_files]
+ *            int64, a label per file. The group-by is over the label's VALUE, as
+ *            in sdcas_duplicate_sets: sdcas_file_families' out_family is a valid
+ *            input as it is, and so is any other per-file label (confirm's rep
+ *            over files, top_rep).
+ *   row      row i takes part when 0 <= family[i] < n_files; its label is that
+ *            value. It is never used as an index into the chunk arrays.
+ *   chunk    chunk c takes part when chunk_file[c] < n_files and that row
+ *            takes part. Its class number is r(c) = rep[c] when 0 <= rep[c] <= c,
+ *            else c: a number only, never an index. Its CLASS is the pair
+ *            (label of its row, r(c)); the FIRST OCCURRENCE of a class is its
+ *            lowest participating chunk position.
+ *   per row  the sums of chunk_len over the row's participating chunks, modulo
+ *            2^64; rows that take no part get 0:
+ *              out_file_bytes[i]       all of them
+ *              out_delta_bytes[i]      those that are their class's first
+ *                                      occurrence: what row i adds to its family
+ *              out_self_bytes[i]       those whose class's first occurrence is
+ *                                      an earlier chunk of row i itself
+ *              out_inherited_bytes[i]  those whose class's first occurrence lies
+ *                                      in another row of the family
+ *            file = delta + self + inherited holds for every row.
+ *   per label  total: the sum of file_bytes over its rows; stored: the sum of
+ *            delta_bytes over its rows; reclaimable = total - stored, modulo 2^64.
+ *   sets     a SET is a label carried by at least two participating rows. The
+ *            sets are written in order of (reclaimable descending, lowest member
+ *            row ascending): out_set_rep[s] int64, the set's lowest member row
+ *            (as in sdcas_duplicate_sets); out_set_files[s] u32, its rows;
+ *            out_set_total[s] and out_set_stored[s] u64. The caller provides
+ *            n_files / 2 entries for each set array; entries past `sets` are
+ *            left as they were.
+ * Example: n_files = 4, family = [0, 0, 2, 0], seven chunks
+ *     chunk  file  len  rep
+ *     c0     0     10   0    first of class (0, 0): delta
+ *     c1     0     10   0    first occurrence in its own row: self
+ *     c2     1     10   0    first occurrence in row 0: inherited
+ *     c3     1      5   3    first of class (0, 3): delta
+ *     c4     2     10   0    label 2, first of class (2, 0): delta
+ *     c5     3      5   3    first occurrence in row 1: inherited
+ *     c6     3      7   6    first of class (0, 6): delta
+ *   rows (file, delta, self, inherited): (20, 10, 10, 0), (15, 5, 0, 10),
+ *   (10, 10, 0, 0), (12, 7, 0, 5). Row 2 is alone in label 2: the chunk it
+ *   shares with label 0 is reclaimed by nobody. One set: rep 0, files 3, total
+ *   47, stored 22. Counts: files 4, chunks 7, classes 4, total_bytes 57,
+ *   stored_bytes 32, sets 1, members 3, set_reclaimable_bytes 25,
+ *   largest_reclaimable 25.
+ * Laws: (1) with rep[rep[c]] == rep[c] <= c, all rows under one label and every
+ * chunk taking part, delta / self / inherited equal sdcas_chunk_sharing's new /
+ * self / other and stored_bytes its stored_bytes; (2) with family[i] = i,
+ * inherited is 0 everywhere and there are no sets; (3) the sum of delta over a
+ * label's rows is its stored.
+ * SDCAS_E_INVALID for a needed NULL array (chunk_file, chunk_len, rep with m !=
+ * 0; family with n_files != 0) or a misalignment (8 bytes for u64 and int64, 4
+ * for u32); SDCAS_E_CAPACITY for m > 2^30 or n_files > 2^30: all before anything
+ * is enqueued. m == 0 and n_files == 0 are SDCAS_OK; with m == 0 the rows still
+ * form sets, with zero bytes, ordered by rep. Any output may be NULL. Results
+ * are exact and do not depend on scheduling: the first occurrence of a class is
+ * a property of the input, everything else is sums modulo 2^64, a minimum and
+ * a maximum; two calls on one input give the same bytes. */
+typedef struct sdcas_family_bytes_counts {
+  uint64_t files;                 /* participating rows */
+  uint64_t chunks;                /* participating chunks */
+  uint64_t classes;               /* distinct (label, class number) pairs */
+  uint64_t total_bytes;           /* over all participating rows */
+  uint64_t stored_bytes;          /* over all participating rows */
+  uint64_t sets;                  /* labels carried by at least two rows */
+  uint64_t members;               /* rows in those sets */
+  uint64_t set_reclaimable_bytes; /* the sum over the sets only */
+  uint64_t largest_reclaimable;   /* the largest set's reclaimable bytes, 0 when there is none */
+} sdcas_family_bytes_counts;
+/* GPU-free: the range checks above (m, n_files) and *out_workspace_bytes = what
+ * the device call takes (a table of at least 2 m u32 slots, 4 bytes per chunk,
+ * 65 bytes per row and a little). The output may be NULL. */
+int sdcas_family_bytes_plan(uint64_t m, uint64_t n_files, uint64_t *out_workspace_bytes);
+/* Host arrays: one upload, the device call, the counts down, then exactly
+ * `sets` entries of each set array. */
+int sdcas_family_bytes(sdcas_ctx *ctx, const uint32_t *chunk_file, const uint64_t *chunk_len, const int64_t *rep,
+                       size_t m, const int64_t *family, size_t n_files, uint64_t *out_file_bytes,
+                       uint64_t *out_delta_bytes, uint64_t *out_self_bytes, uint64_t *out_inherited_bytes,
+                       int64_t *out_set_rep, uint32_t *out_set_files, uint64_t *out_set_total,
+                       uint64_t *out_set_stored, sdcas_family_bytes_counts *out_counts);
+/* Device arrays under sdcas_dev_chunk_peers' stream rules. d_counts: nine u64 in
+ * sdcas_family_bytes_counts' order, overwritten. The workspace for (m, n_files)
+ * is allocated by the first call that needs it, which waits for the stream;
+ * after that the call never waits for the device. Every grid is sized from m or
+ * n_files, the numbers of classes and sets stay on the device, and the sets are
+ * ordered by ceil_log2(n_files) merge launches, whatever the data. */
+int sdcas_dev_family_bytes(sdcas_ctx *ctx, const uint32_t *d_chunk_file, const uint64_t *d_chunk_len,
+                           const int64_t *d_rep, size_t m, const int64_t *d_family, size_t n_files,
+                           uint64_t *d_file_bytes, uint64_t *d_delta_bytes, uint64_t *d_self_bytes,
+                           uint64_t *d_inherited_bytes, int64_t *d_set_rep, uint32_t *d_set_files,
+                           uint64_t *d_set_total, uint64_t *d_set_stored, uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

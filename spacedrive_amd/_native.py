@@ -74,6 +74,7 @@ ABI_SYMBOLS = [
     "sdcas_dev_chunk_holders_remove",  # added after ABI 7
     "sdcas_chunk_peers_plan", "sdcas_chunk_peers", "sdcas_dev_chunk_peers",  # added after ABI 7
     "sdcas_file_families_plan", "sdcas_file_families", "sdcas_dev_file_families",  # added after ABI 7
+    "sdcas_family_bytes_plan", "sdcas_family_bytes", "sdcas_dev_family_bytes",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -239,6 +240,17 @@ class FamiliesCounts(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class FamilyBytesCounts(ctypes.Structure):
+    """sdcas_family_bytes_counts"""
+    _fields_ = [("files", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("classes", ctypes.c_uint64),
+                ("total_bytes", ctypes.c_uint64), ("stored_bytes", ctypes.c_uint64), ("sets", ctypes.c_uint64),
+                ("members", ctypes.c_uint64), ("set_reclaimable_bytes", ctypes.c_uint64),
+                ("largest_reclaimable", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _lib_path = LIB_PATH
 
@@ -346,6 +358,11 @@ def load():
     L.sdcas_file_families.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _vp,
                                       ctypes.POINTER(FamiliesCounts)]
     L.sdcas_dev_file_families.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _u32, _u32, _u32, _vp, _vp, _vp, _vp]
+    L.sdcas_family_bytes_plan.argtypes = [_u64, _u64, _vp]
+    L.sdcas_family_bytes.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     ctypes.POINTER(FamilyBytesCounts)]
+    L.sdcas_dev_family_bytes.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

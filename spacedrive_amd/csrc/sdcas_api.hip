@@ -37,6 +37,7 @@
 #include "chunk_holders.h"
 #include "chunk_peers.h"
 #include "families.h"
+#include "family_bytes.h"
 #include "chunk_index.h"
 #include "dist_dedup.h"
 #include "synth.h"
@@ -237,6 +238,8 @@ struct sdcas_ctx {
   DevBuf<uint8_t> cp_ws;
   // the file families (families.hip): the forest, the sizes, the flags and the sums
   DevBuf<uint8_t> ff_ws;
+  // the family bytes (family_bytes.hip): the class table, the row and label sums, the order
+  DevBuf<uint8_t> fb_ws;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -3353,6 +3356,109 @@ int sdcas_file_families(sdcas_ctx* c, const uint64_t* ids, const uint64_t* sizes
   const FamiliesIn in{d_ids, d_sizes, d_pc, d_peers, d_pb, (uint32_t)n, k, num, den};
   if (hipError_t e = file_families(c->ff_ws.p, in, d_family, d_fs, d_cts.as<unsigned long long>(), st))
     return hip_fail_at(c, e, who, "");
+  if (int rc = p.download()) return rc;
+  if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+// ---- the family bytes (family_bytes.hip) -----------------------------------------------
+
+// the request's ranges, GPU-free: SDCAS_OK, or the code with *why set
+static int family_bytes_range(uint64_t m, uint64_t n_files, const char** why) {
+  static_assert(kFamilyBytesMaxChunks == (1ull << 30) && kFamilyBytesMaxFiles == (1ull << 30), "family bytes limits");
+  if (m > kFamilyBytesMaxChunks) return *why = "more than 2^30 chunks", SDCAS_E_CAPACITY;
+  if (n_files > kFamilyBytesMaxFiles) return *why = "more than 2^30 files", SDCAS_E_CAPACITY;
+  return SDCAS_OK;
+}
+
+int sdcas_family_bytes_plan(uint64_t m, uint64_t n_files, uint64_t* out_workspace_bytes) {
+  const char* why = nullptr;
+  if (int rc = family_bytes_range(m, n_files, &why)) return rc;
+  if (out_workspace_bytes) *out_workspace_bytes = family_bytes_layout(m, n_files).bytes;
+  return SDCAS_OK;
+}
+
+// a call's arguments (host or device arrays): the ranges, then the arrays it needs
+static int family_bytes_args(sdcas_ctx* c, const char* who, const void* chunk_file, const void* chunk_len,
+                             const void* rep, size_t m, const void* family, size_t n_files) {
+  const char* why = nullptr;
+  if (int rc = family_bytes_range(m, n_files, &why)) return c->fail(rc, "%s: %s", who, why);
+  if (m && (!chunk_file || !chunk_len || !rep))
+    return c->fail(SDCAS_E_INVALID, "%s: null chunk_file, chunk_len or rep", who);
+  if (n_files && !family) return c->fail(SDCAS_E_INVALID, "%s: null family", who);
+  return SDCAS_OK;
+}
+
+int sdcas_dev_family_bytes(sdcas_ctx* c, const uint32_t* d_chunk_file, const uint64_t* d_chunk_len,
+                           const int64_t* d_rep, size_t m, const int64_t* d_family, size_t n_files,
+                           uint64_t* d_file_bytes, uint64_t* d_delta_bytes, uint64_t* d_self_bytes,
+                           uint64_t* d_inherited_bytes, int64_t* d_set_rep, uint32_t* d_set_files,
+                           uint64_t* d_set_total, uint64_t* d_set_stored, uint64_t* d_counts, void* stream) {
+  const char* who = "dev_family_bytes";
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = family_bytes_args(c, who, d_chunk_file, d_chunk_len, d_rep, m, d_family, n_files)) return rc;
+  if (index_misaligned({},
+                       {d_chunk_len, d_rep, d_family, d_file_bytes, d_delta_bytes, d_self_bytes, d_inherited_bytes,
+                        d_set_rep, d_set_total, d_set_stored, d_counts},
+                       {d_chunk_file, d_set_files}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (chunk_file and set_files 4 B, others 8 B)", who);
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = grow_synced(c, c->fb_ws, (size_t)family_bytes_layout(m, n_files).bytes, call.st,
+                           "family bytes workspace"))
+    return rc;
+  const FamilyBytesIn in{d_chunk_file, d_chunk_len, d_rep, d_family, (uint32_t)m, (uint32_t)n_files};
+  const FamilyBytesOut out{d_file_bytes, d_delta_bytes, d_self_bytes, d_inherited_bytes,
+                           d_set_rep,    d_set_files,   d_set_total,  d_set_stored};
+  hipError_t e = family_bytes(c->fb_ws.p, in, out, (unsigned long long*)d_counts, call.st);
+  return e ? hip_fail_at(c, e, who, "") : SDCAS_OK;
+}
+
+int sdcas_family_bytes(sdcas_ctx* c, const uint32_t* chunk_file, const uint64_t* chunk_len, const int64_t* rep,
+                       size_t m, const int64_t* family, size_t n_files, uint64_t* out_file_bytes,
+                       uint64_t* out_delta_bytes, uint64_t* out_self_bytes, uint64_t* out_inherited_bytes,
+                       int64_t* out_set_rep, uint32_t* out_set_files, uint64_t* out_set_total,
+                       uint64_t* out_set_stored, sdcas_family_bytes_counts* out_counts) {
+  static_assert(sizeof(sdcas_family_bytes_counts) == kFamilyBytesCounts * sizeof(uint64_t), "nine u64 counts");
+  const char* who = "family_bytes";
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = family_bytes_args(c, who, chunk_file, chunk_len, rep, m, family, n_files)) return rc;
+  if (index_misaligned({},
+                       {chunk_len, rep, family, out_file_bytes, out_delta_bytes, out_self_bytes, out_inherited_bytes,
+                        out_set_rep, out_set_total, out_set_stored, out_counts},
+                       {chunk_file, out_set_files}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (chunk_file and set_files 4 B, others 8 B)", who);
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  const size_t nf = n_files, h = n_files / 2;  // no more sets than that
+  sdcas_family_bytes_counts cts;
+  Parts p(c, st, who);
+  const auto d_file = p.in(chunk_file, m);
+  const auto d_len = p.in(chunk_len, m);
+  const auto d_rep = p.in(rep, m);
+  const auto d_family = p.in(family, nf);
+  const auto d_fb = p.out(out_file_bytes, nf);
+  const auto d_delta = p.out(out_delta_bytes, nf);
+  const auto d_self = p.out(out_self_bytes, nf);
+  const auto d_inh = p.out(out_inherited_bytes, nf);
+  const auto d_set_rep = p.out(out_set_rep, h);
+  const auto d_set_files = p.out(out_set_files, h);
+  const auto d_set_total = p.out(out_set_total, h);
+  const auto d_set_stored = p.out(out_set_stored, h);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = grow_synced(c, c->fb_ws, (size_t)family_bytes_layout(m, n_files).bytes, st, "family bytes workspace"))
+    return rc;
+  if (int rc = p.upload()) return rc;
+  const FamilyBytesIn in{d_file, d_len, d_rep, d_family, (uint32_t)m, (uint32_t)n_files};
+  const FamilyBytesOut out{d_fb, d_delta, d_self, d_inh, d_set_rep, d_set_files, d_set_total, d_set_stored};
+  if (hipError_t e = family_bytes(c->fb_ws.p, in, out, d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  if (int rc = p.counts(d_cts)) return rc;
+  if (cts.sets > h || cts.members > nf) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
+  d_set_rep.first(cts.sets), d_set_files.first(cts.sets), d_set_total.first(cts.sets), d_set_stored.first(cts.sets);
   if (int rc = p.download()) return rc;
   if (out_counts) *out_counts = cts;
   return SDCAS_OK;

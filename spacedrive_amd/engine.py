@@ -931,7 +931,7 @@ class Engine:
                 "common_bytes": common, "counts": counts.as_dict()}
 
     def similar_files_indexed(self, paths, file_ids, index, params=None, window_bytes=256 << 20, peers=0,
-                              max_holders=64):
+                              max_holders=64, chunks=False):
         """similar_files_streamed against what earlier calls stored: the files
         are chunked through chunk_stream, their chunks confirmed within the
         batch, matched against `index` (a ChunkIndex or a ChunkHolders) and
@@ -967,7 +967,13 @@ class Engine:
         the files — in "earlier" mode a file's result does not depend on which
         later files the index holds — and after remove(R) the rows of the later
         batches equal those of one run over the survivors and those batches.
-        With peers=0 the calls and the dict are what they were."""
+        With peers=0 the calls and the dict are what they were.
+
+        chunks=True adds the batch's chunk arrays, which the call holds anyway:
+        "chunk_file" uint32[m] (rows of this call), "chunk_len" uint64[m],
+        "chunk_keys" uint64[m] and "chunk_digests" uint8[m, 32]; the index
+        keeps no lengths, so a caller that wants family_bytes_of keeps these.
+        With the default the dict is what it was."""
         import torch
 
         if peers and not isinstance(index, ChunkHolders):
@@ -1034,6 +1040,8 @@ class Engine:
             out.update({"peers": near["peers"], "peers_bytes": near["peers_bytes"], "peer_count": near["peer_count"],
                         "shared_bytes": near["shared_bytes"], "common_bytes": near["common_bytes"],
                         "peers_counts": near["counts"]})
+        if chunks:
+            out.update({"chunk_file": fl, "chunk_len": ln, "chunk_keys": keys, "chunk_digests": dig.reshape(-1, 32)})
         return out
 
     # -- file families: the connected components of the peer rows ---------------------
@@ -1104,6 +1112,119 @@ class Engine:
         ids = np.concatenate([np.zeros(0, np.uint64)] + file_ids)
         return self.file_families(ids, cat("sizes", np.uint64), cat("peer_count", np.uint32), cat("peers", np.uint64, k),
                                   cat("peers_bytes", np.uint64, k), num, den, sets=True)
+
+    # -- family bytes: what a family's versions store and give back ---------------------
+    @staticmethod
+    def family_bytes_plan(m, n_files):
+        """sdcas_family_bytes_plan (no GPU) -> workspace_bytes: what the device
+        call takes for m chunks of n_files rows; SdcasError beyond the ranges"""
+        ws = ctypes.c_uint64(0)
+        rc = N.load().sdcas_family_bytes_plan(int(m), int(n_files), ctypes.byref(ws))
+        if rc != N.SDCAS_OK:
+            raise N.SdcasError(rc, f"family_bytes_plan({m}, {n_files})")
+        return int(ws.value)
+
+    def family_bytes(self, chunk_file, chunk_len, rep, family, sets=False):
+        """sdcas_family_bytes over host arrays: chunk_sharing's chunk_file
+        uint32[m], chunk_len uint64[m] and rep int64[m], and a label per row,
+        family int64[n] (file_families' "family" as it is; values outside
+        [0, n) take no part). A chunk's class is (label of its row, class
+        number); its bytes are the row's delta when it is the class's first
+        occurrence, self when that lies earlier in the row itself, inherited
+        when it lies in another row of the family. -> dict: "file_bytes",
+        "delta_bytes", "self_bytes", "inherited_bytes" uint64[n]; per label
+        with two rows or more, most reclaimable first (ties by lowest row):
+        "set_rep" int64[S], "set_files" uint32[S], "set_total", "set_stored"
+        and "set_reclaimable" (total - stored) uint64[S]; "counts":
+        sdcas_family_bytes_counts' nine fields. sets=True adds "set_offsets"
+        uint64[S + 1] and "members" int64[M] in the same set order: they come
+        from duplicate_sets(family, None, SDCAS_SETS_BY_REP), permuted on the
+        host through its set_rep; that host step follows the number of sets
+        and members, not the chunks."""
+        fl, ln, rp = _arr(chunk_file, np.uint32), _arr(chunk_len, np.uint64), _arr(rep, np.int64)
+        fam = _arr(family, np.int64)
+        m, n = fl.size, fam.size
+        if ln.size != m or rp.size != m:
+            raise ValueError(f"family_bytes: {m} chunk files, {ln.size} lengths, {rp.size} reps")
+        h = n // 2
+        rows = [np.zeros(n, np.uint64) for _ in range(4)]
+        set_rep, set_files = np.zeros(h, np.int64), np.zeros(h, np.uint32)
+        set_total, set_stored = np.zeros(h, np.uint64), np.zeros(h, np.uint64)
+        counts = N.FamilyBytesCounts()
+        self._check(self.L.sdcas_family_bytes(self.ctx, _ptr(fl), _ptr(ln), _ptr(rp), m, _ptr(fam), n,
+                                              *(a.ctypes.data for a in rows), set_rep.ctypes.data,
+                                              set_files.ctypes.data, set_total.ctypes.data, set_stored.ctypes.data,
+                                              ctypes.byref(counts)), "sdcas_family_bytes")
+        s = int(counts.sets)
+        out = {"file_bytes": rows[0], "delta_bytes": rows[1], "self_bytes": rows[2], "inherited_bytes": rows[3],
+               "set_rep": set_rep[:s].copy(), "set_files": set_files[:s].copy(), "set_total": set_total[:s].copy(),
+               "set_stored": set_stored[:s].copy(), "set_reclaimable": set_total[:s] - set_stored[:s],
+               "counts": counts.as_dict()}
+        if sets:
+            by_rep, offs, _, members, _ = self.duplicate_sets(fam, None, N.SDCAS_SETS_BY_REP)
+            pos = np.searchsorted(by_rep, out["set_rep"])  # by_rep ascends; both list the same sets
+            if pos.size and (pos.max(initial=0) >= by_rep.size or not np.array_equal(by_rep[pos], out["set_rep"])):
+                raise RuntimeError("family_bytes: the sets of duplicate_sets and of family_bytes differ")
+            lens = (offs[1:] - offs[:-1])[pos].astype(np.int64)
+            new_offs = np.concatenate([np.zeros(1, np.int64), np.cumsum(lens)])
+            take = np.repeat(offs[:-1][pos].astype(np.int64) - new_offs[:-1], lens) + np.arange(new_offs[-1])
+            out.update({"set_offsets": new_offs.astype(np.uint64), "members": members[take]})
+        return out
+
+    def family_bytes_of(self, results, file_ids, num=1, den=2):
+        """families_of plus the bytes: over consecutive
+        similar_files_indexed(..., peers=k, chunks=True) calls, `results` their
+        dicts and `file_ids` their id arrays in call order. The families are
+        families_of's; the chunk arrays are concatenated ("chunk_file" shifted
+        by the rows before), confirm_duplicates over the concatenated (key,
+        digest) pairs gives rep, and family_bytes(..., sets=True) runs over
+        them. -> families_of's dict merged with family_bytes': where both have
+        a key ("set_rep", "set_offsets", "members", "counts") families_of's
+        goes under "families_" + key and the reclaimable-ordered form keeps the
+        plain name. ValueError when a result lacks the chunk arrays or its rows
+        do not match its ids: dropped rows are not supported here."""
+        results, file_ids = list(results), [_arr(x, np.uint64) for x in file_ids]
+        if len(results) != len(file_ids):
+            raise ValueError(f"family_bytes_of: {len(results)} results, {len(file_ids)} id arrays")
+        for r in results:
+            for key in ("chunk_file", "chunk_len", "chunk_keys", "chunk_digests"):
+                if key not in r:
+                    raise ValueError(f"family_bytes_of: a result has no {key} (similar_files_indexed(..., chunks=True))")
+        fl, ln, keys, dig, row0 = [], [], [], [], 0
+        for r, ids in zip(results, file_ids):
+            cf = _arr(r["chunk_file"], np.uint32)
+            if np.asarray(r["sizes"]).size != ids.size or (cf.size and int(cf.max()) >= ids.size):
+                raise ValueError("family_bytes_of: a result's rows do not match its ids (dropped rows are not supported)")
+            fl.append((cf.astype(np.uint64) + row0).astype(np.uint32))
+            ln.append(_arr(r["chunk_len"], np.uint64))
+            keys.append(_arr(r["chunk_keys"], np.uint64))
+            dig.append(_arr(r["chunk_digests"], np.uint8).reshape(-1, 32))
+            row0 += ids.size
+        fl = np.concatenate([np.zeros(0, np.uint32)] + fl)
+        ln = np.concatenate([np.zeros(0, np.uint64)] + ln)
+        keys = np.concatenate([np.zeros(0, np.uint64)] + keys)
+        dig = np.concatenate([np.zeros((0, 32), np.uint8)] + dig)
+        fam = self.families_of(results, file_ids, num, den)
+        rep = self.confirm_duplicates(keys, dig)[0]
+        out = dict(fam)
+        for key in ("set_rep", "set_offsets", "members", "counts"):
+            out["families_" + key] = out.pop(key)
+        out.update(self.family_bytes(fl, ln, rep, fam["family"], sets=True))
+        return out
+
+    def similar_families(self, paths, k=4, max_holders=64, num=1, den=2, params=None, window_bytes=256 << 20):
+        """the families of these files and their bytes in one call, with no
+        index for the caller to keep: family_bytes_of over one
+        similar_files_indexed(paths, arange(n), ChunkHolders(self), ...,
+        peers=k, chunks=True). Rows are the paths in order. -> that dict plus
+        "sizes". The steps go through the host forms."""
+        paths = [os.fspath(p) for p in paths]
+        ids = np.arange(len(paths), dtype=np.uint64)
+        r = self.similar_files_indexed(paths, ids, ChunkHolders(self), params, window_bytes, peers=int(k),
+                                       max_holders=max_holders, chunks=True)
+        out = self.family_bytes_of([r], [ids], num, den)
+        out["sizes"] = r["sizes"]
+        return out
 
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
     def dev_chunk_index_match(self, idx_keys, idx_digests, idx_values, idx_dir, n, bits, keys, digests, valid, m,
@@ -1200,6 +1321,23 @@ class Engine:
                                                    peers or None, peer_bytes or None, int(n), int(k), int(num),
                                                    int(den), family or None, family_size or None, counts or None,
                                                    stream or None), "dev_file_families")
+
+    def dev_family_bytes(self, chunk_file, chunk_len, rep, m, family, n_files, file_bytes=0, delta_bytes=0,
+                         self_bytes=0, inherited_bytes=0, set_rep=0, set_files=0, set_total=0, set_stored=0,
+                         counts=0, stream=0):
+        """family_bytes over device arrays (sdcas_dev_family_bytes), e.g.
+        dev_chunk's chunk_file / chunk_len, dev_confirm_duplicates' rep and
+        dev_file_families' family as they are; the four per-row outputs
+        uint64[n_files], set_rep int64, set_files uint32, set_total and
+        set_stored uint64 of n_files // 2 entries each (the first `sets` are
+        written), counts nine uint64; any output may be 0. Nothing waits for
+        the device once the workspace for (m, n_files) exists"""
+        self._check(self.L.sdcas_dev_family_bytes(self.ctx, chunk_file or None, chunk_len or None, rep or None,
+                                                  int(m), family or None, int(n_files), file_bytes or None,
+                                                  delta_bytes or None, self_bytes or None, inherited_bytes or None,
+                                                  set_rep or None, set_files or None, set_total or None,
+                                                  set_stored or None, counts or None, stream or None),
+                    "dev_family_bytes")
 
     def dev_chunk_windows(self, blob, offs, lens, final, n, max_chunks, max_slots, params=None, file_chunks=0,
                           chunk_off=0, chunk_len=0, chunk_file=0, keys=0, digests=0, consumed=0, counts=0, stream=0):
