@@ -1316,6 +1316,118 @@ int sdcas_dev_family_bytes(sdcas_ctx *ctx, const uint32_t *d_chunk_file, const u
                            uint64_t *d_inherited_bytes, int64_t *d_set_rep, uint32_t *d_set_files,
                            uint64_t *d_set_total, uint64_t *d_set_stored, uint64_t *d_counts, void *stream);
 
+/* ---- family recipes: rebuild every file from its family's stored bytes ----------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * sdcas_family_bytes says that a family stores 22 of its 47 bytes. This call
+ * says which: per row the list of byte ranges (OPS) that rebuilds the row from
+ * what its family keeps. A literal op names bytes the row keeps itself; a copy
+ * op names a range of another row (or an earlier range of the same row) that is
+ * kept there. Neighbouring chunks that come from neighbouring bytes of one
+ * source are one op. The library returns the plan; it reads and writes no file
+ * bytes.
+ *   inputs   sdcas_family_bytes' and one array: chunk_file[m] u32;
+ *            chunk_off[m] u64, the chunk's offset IN ITS FILE (as the chunkers
+ *            here report it); chunk_len[m] u64; rep[m] int64; family[n_files]
+ *            int64. Which rows and chunks take part, the class (label, r(c)) and
+ *            its first occurrence f(c) are sdcas_family_bytes', word for word.
+ *            All arithmetic is modulo 2^64.
+ *   source   for a participating chunk c, src(c) = (chunk_file[f(c)],
+ *            chunk_off[f(c)]). c is a LITERAL when f(c) == c: the row keeps
+ *            these bytes. Otherwise it is a COPY.
+ *   continuation  a participating chunk c CONTINUES c - 1 when all of these hold:
+ *              c >= 1 and c - 1 takes part;
+ *              chunk_file[c - 1] == chunk_file[c];
+ *              both are literals or both are copies;
+ *              chunk_off[c] == chunk_off[c - 1] + chunk_len[c - 1];
+ *              chunk_file[f(c)] == chunk_file[f(c - 1)];
+ *              chunk_off[f(c)] == chunk_off[f(c - 1)] + chunk_len[c - 1].
+ *            Any other participating chunk starts an op (is its HEAD). Only c - 1
+ *            is looked at.
+ *   ops      numbered in the order of their head chunks' positions:
+ *              out_op_chunk[o]      u32  the head chunk
+ *              out_op_src_chunk[o]  u32  f(head); the op is a literal if and only
+ *                                        if this equals out_op_chunk[o]
+ *              out_op_row[o]        u32  chunk_file[head]
+ *              out_op_src_row[o]    u32  chunk_file[f(head)]
+ *              out_op_dst_off[o]    u64  chunk_off[head]
+ *              out_op_src_off[o]    u64  chunk_off[f(head)]
+ *              out_op_len[o]        u64  the sum of its chunks' lengths
+ *            The caller provides m entries for each op array; entries past `ops`
+ *            are left as they were.
+ *   per chunk  out_chunk_op[c] u32: the op of chunk c, 0xFFFFFFFF for a chunk that
+ *            takes no part.
+ *   per row  out_row_ops[i] u32: the number of the row's ops; out_row_first_op[i]
+ *            u32: its lowest op, 0xFFFFFFFF when it has none. When a row's chunks
+ *            are adjacent in the arrays, as every producer here writes them, its
+ *            ops are [row_first_op, row_first_op + row_ops). When the chunks of
+ *            two rows are interleaved the ops are still exact, but a row's ops
+ *            are not adjacent: find them through out_op_row.
+ * Example: two rows under one label, v1 = A B C and v2 = A B X C with lengths
+ * 10, 20, 30 and X = 5:
+ *     chunk_file [0,0,0,1,1,1,1]   chunk_off [0,10,30,0,10,30,35]
+ *     chunk_len  [10,20,30,10,20,5,30]   rep [0,1,2,0,1,5,2]   family [0,0]
+ *   Seven chunks give four ops:
+ *     op 0  literal  row 0  dst 0   len 60
+ *     op 1  copy     row 1  dst 0   from row 0 offset 0, len 30 (A and B merged)
+ *     op 2  literal  row 1  dst 30  len 5
+ *     op 3  copy     row 1  dst 35  from row 0 offset 30, len 30
+ *   chunk_op [0,0,0,1,1,2,3]; row_ops [1,3]; row_first_op [0,1]. Counts: files 2,
+ *   chunks 7, ops 4, literal_ops 2, copy_ops 2, literal_bytes 65, copy_bytes 60,
+ *   longest_op 60.
+ * Laws: (1) per row the sum of the literal ops' len is sdcas_family_bytes'
+ * delta_bytes and the sum of the copy ops' is self_bytes + inherited_bytes;
+ * literal_bytes is its stored_bytes. (2) For inputs whose chunk_off are the
+ * running sums of chunk_len per file, every copy op's source range is covered
+ * by literal ops of op_src_row: no copy reads from a copy, recipes have depth
+ * one. (3) With such offsets, and rep equal only where the bytes are equal,
+ * writing every op's source bytes at its dst_off rebuilds every participating
+ * file, the source bytes taken from a store that holds the literal ops' bytes
+ * and nothing else. (4) With family[i] = i every op's source lies in its own
+ * row: op_src_row == op_row everywhere.
+ * Errors and limits are sdcas_family_bytes', all before anything is enqueued:
+ * SDCAS_E_INVALID for a needed NULL array (chunk_file, chunk_off, chunk_len, rep
+ * with m != 0; family with n_files != 0) or a misalignment (8 bytes for u64 and
+ * int64, 4 for u32); SDCAS_E_CAPACITY for m > 2^30 or n_files > 2^30. m == 0
+ * and n_files == 0 are SDCAS_OK. Any output may be NULL, also all but the
+ * counts. Results are exact and do not depend on scheduling; two calls on one
+ * input give the same bytes. */
+typedef struct sdcas_family_recipes_counts {
+  uint64_t files;         /* participating rows */
+  uint64_t chunks;        /* participating chunks */
+  uint64_t ops;           /* literal_ops + copy_ops */
+  uint64_t literal_ops;
+  uint64_t copy_ops;
+  uint64_t literal_bytes; /* the sum of the literal ops' len: what the families store */
+  uint64_t copy_bytes;    /* the sum of the copy ops' len */
+  uint64_t longest_op;    /* the largest op_len, 0 when there is no op */
+} sdcas_family_recipes_counts;
+/* GPU-free: the range checks above (m, n_files) and *out_workspace_bytes = what
+ * the device call takes (a table of at least 2 m u32 slots, 17 bytes per chunk,
+ * 8 bytes per row, 8 KiB of counters and a little). The output may be NULL. */
+int sdcas_family_recipes_plan(uint64_t m, uint64_t n_files, uint64_t *out_workspace_bytes);
+/* Host arrays: one upload, the device call, the counts down, then exactly `ops`
+ * entries of each op array, with the m entries of chunk_op and the n_files of
+ * the per-row arrays. */
+int sdcas_family_recipes(sdcas_ctx *ctx, const uint32_t *chunk_file, const uint64_t *chunk_off,
+                         const uint64_t *chunk_len, const int64_t *rep, size_t m, const int64_t *family,
+                         size_t n_files, uint32_t *out_op_chunk, uint32_t *out_op_src_chunk, uint32_t *out_op_row,
+                         uint32_t *out_op_src_row, uint64_t *out_op_dst_off, uint64_t *out_op_src_off,
+                         uint64_t *out_op_len, uint32_t *out_chunk_op, uint32_t *out_row_ops,
+                         uint32_t *out_row_first_op, sdcas_family_recipes_counts *out_counts);
+/* Device arrays under sdcas_dev_chunk_peers' stream rules. d_counts: eight u64
+ * in sdcas_family_recipes_counts' order, overwritten. The workspace for (m,
+ * n_files) is allocated by the first call that needs it, which waits for the
+ * stream; after that the call never waits for the device. Every grid is sized
+ * from m or n_files and the number of ops stays on the device. */
+int sdcas_dev_family_recipes(sdcas_ctx *ctx, const uint32_t *d_chunk_file, const uint64_t *d_chunk_off,
+                             const uint64_t *d_chunk_len, const int64_t *d_rep, size_t m, const int64_t *d_family,
+                             size_t n_files, uint32_t *d_op_chunk, uint32_t *d_op_src_chunk, uint32_t *d_op_row,
+                             uint32_t *d_op_src_row, uint64_t *d_op_dst_off, uint64_t *d_op_src_off,
+                             uint64_t *d_op_len, uint32_t *d_chunk_op, uint32_t *d_row_ops,
+                             uint32_t *d_row_first_op, uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

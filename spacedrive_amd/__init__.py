@@ -8,6 +8,7 @@ include/sdcas.h.
 """
 from .engine import (ChunkHolders, ChunkIndex, Engine, Node, default_engine, digest_to_hex, file_checksum, generate_cas_id,
                      io_error, key_to_hex)
+from .recipes import rebuild_files
 
 __all__ = ["ChunkHolders", "ChunkIndex", "Engine", "Node", "default_engine", "digest_to_hex", "file_checksum", "generate_cas_id", "io_error",
-           "key_to_hex"]
+           "key_to_hex", "rebuild_files"]

@@ -75,6 +75,7 @@ ABI_SYMBOLS = [
     "sdcas_chunk_peers_plan", "sdcas_chunk_peers", "sdcas_dev_chunk_peers",  # added after ABI 7
     "sdcas_file_families_plan", "sdcas_file_families", "sdcas_dev_file_families",  # added after ABI 7
     "sdcas_family_bytes_plan", "sdcas_family_bytes", "sdcas_dev_family_bytes",  # added after ABI 7
+    "sdcas_family_recipes_plan", "sdcas_family_recipes", "sdcas_dev_family_recipes",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -251,6 +252,16 @@ class FamilyBytesCounts(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class FamilyRecipesCounts(ctypes.Structure):
+    """sdcas_family_recipes_counts"""
+    _fields_ = [("files", ctypes.c_uint64), ("chunks", ctypes.c_uint64), ("ops", ctypes.c_uint64),
+                ("literal_ops", ctypes.c_uint64), ("copy_ops", ctypes.c_uint64), ("literal_bytes", ctypes.c_uint64),
+                ("copy_bytes", ctypes.c_uint64), ("longest_op", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _lib_path = LIB_PATH
 
@@ -363,6 +374,10 @@ def load():
                                      ctypes.POINTER(FamilyBytesCounts)]
     L.sdcas_dev_family_bytes.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp]
+    L.sdcas_family_recipes_plan.argtypes = [_u64, _u64, _vp]
+    L.sdcas_family_recipes.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz] + [_vp] * 10 + [
+        ctypes.POINTER(FamilyRecipesCounts)]
+    L.sdcas_dev_family_recipes.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz] + [_vp] * 12
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

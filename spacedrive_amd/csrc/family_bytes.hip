@@ -8,7 +8,9 @@
 // occupant's class from the read-only inputs and moves on when it differs.
 // After the insert each slot holds its class's first occurrence, whatever the
 // order the chunks arrived in: the results do not depend on scheduling.
-//   k_fb_insert    one chunk per thread into the table; remembers its slot
+//   k_fb_insert    one chunk per thread into the table; remembers its slot (the
+//                  class and the insert are family_bytes_device.h's, which
+//                  family_recipes.hip shares)
 //   k_fb_classify  the chunk's length into its row's delta, self or inherited
 //                  sum, by where its class's first occurrence lies
 //   k_fb_rows      the row's four outputs; its sums into its label's total,
@@ -36,108 +38,20 @@
 
 #include "chunk_index.h"
 #include "family_bytes.h"
+#include "family_bytes_device.h"
 
 namespace sdcas {
 
 namespace {
 
 constexpr uint32_t kTB = kFamilyBytesTB;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kNone = kFbNone;
 enum { kScFiles, kScChunks, kScClasses, kScTotal, kScStored, kScSets, kScMembers, kScSetReclaimable, kScLargest, kScWords };
 static_assert(kScWords == kFamilyBytesCounts, "sdcas_family_bytes_counts' order");
 
-typedef unsigned long long u64a;  // what the 64-bit atomics take
-
-__device__ __forceinline__ uint32_t fb_load(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint64_t fb_load(const u64a* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint64_t fb_mix(uint64_t x) {
-  x ^= x >> 32;
-  x *= 0xD6E8FEB86659FD93ull;
-  x ^= x >> 32;
-  x *= 0xD6E8FEB86659FD93ull;
-  x ^= x >> 32;
-  return x;
-}
-
-__device__ __forceinline__ uint64_t fb_wave_sum(uint64_t v) {
-#pragma unroll
-  for (uint32_t d = 32; d; d >>= 1) v += __shfl_xor((u64a)v, d);
-  return v;
-}
-__device__ __forceinline__ uint64_t fb_wave_max(uint64_t v) {
-#pragma unroll
-  for (uint32_t d = 32; d; d >>= 1) {
-    const uint64_t t = __shfl_xor((u64a)v, d);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t fb_first(unsigned long long lanes) { return (uint32_t)__ffsll((long long)lanes) - 1; }
-
-// the label of row i when it takes part (in [0, n)), else false
-__device__ __forceinline__ bool fb_label(const int64_t* __restrict__ family, uint32_t n, uint32_t i, uint32_t& label) {
-  if (i >= n) return false;
-  const int64_t v = family[i];
-  if (v < 0 || (uint64_t)v >= (uint64_t)n) return false;
-  label = (uint32_t)v;
-  return true;
-}
-
-// the row and the class of chunk c when it takes part, else false. The class
-// number is a number only: rep[c] inside [0, c], else c.
-__device__ __forceinline__ bool fb_class(const FamilyBytesIn& in, uint32_t c, uint32_t& row, uint64_t& cls) {
-  if (c >= in.m) return false;
-  row = in.chunk_file[c];
-  uint32_t label;
-  if (!fb_label(in.family, in.n, row, label)) return false;
-  const int64_t r = in.rep[c];
-  cls = (uint64_t)label << 32 | (r >= 0 && r <= (int64_t)c ? (uint32_t)r : c);
-  return true;
-}
-
 __global__ void __launch_bounds__(kTB) k_fb_insert(FamilyBytesIn in, uint32_t* table, uint32_t mask,
                                                    uint32_t* __restrict__ slot) {
-  const uint32_t c = blockIdx.x * kTB + threadIdx.x, lane = threadIdx.x & 63;
-  uint32_t row = 0;
-  uint64_t cls = 0;
-  const bool on = fb_class(in, c, row, cls);
-  const unsigned long long live = __ballot(on);
-  const uint32_t lead = live ? fb_first(live) : 0u;
-  // the lanes that carry the first active lane's class follow it: that lane's
-  // position is their lowest, so it alone is sent
-  const uint64_t lcls = __shfl((u64a)cls, lead);
-  const bool follow = on && lane != lead && cls == lcls;
-  uint32_t at = kNone;
-  if (on && !follow) {
-    uint32_t h = (uint32_t)fb_mix(cls) & mask;
-    for (uint32_t step = 0; step <= mask; ++step) {  // ends at an empty slot: the table is never more than half full
-      uint32_t cur = fb_load(&table[h]);
-      if (cur == kNone) {
-        const uint32_t prev = atomicCAS(&table[h], kNone, c);
-        if (prev == kNone) {
-          at = h;
-          break;
-        }
-        cur = prev;
-      }
-      uint32_t orow;
-      uint64_t ocls;
-      if (fb_class(in, cur, orow, ocls) && ocls == cls) {
-        if (cur > c) atomicMin(&table[h], c);
-        at = h;
-        break;
-      }
-      h = (h + 1) & mask;
-    }
-  }
-  const uint32_t lat = __shfl(at, lead);
-  if (follow) at = lat;
-  if (c < in.m) slot[c] = at;
+  fb_insert(in, table, mask, slot);  // family_bytes_device.h, shared with family_recipes.hip
 }
 
 __global__ void __launch_bounds__(kTB) k_fb_classify(FamilyBytesIn in, const uint32_t* table, uint32_t mask,

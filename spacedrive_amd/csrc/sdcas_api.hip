@@ -38,6 +38,7 @@
 #include "chunk_peers.h"
 #include "families.h"
 #include "family_bytes.h"
+#include "family_recipes.h"
 #include "chunk_index.h"
 #include "dist_dedup.h"
 #include "synth.h"
@@ -240,6 +241,8 @@ struct sdcas_ctx {
   DevBuf<uint8_t> ff_ws;
   // the family bytes (family_bytes.hip): the class table, the row and label sums, the order
   DevBuf<uint8_t> fb_ws;
+  // the family recipes (family_recipes.hip): the class table, the chunks' sources and ops
+  DevBuf<uint8_t> fr_ws;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -3459,6 +3462,105 @@ int sdcas_family_bytes(sdcas_ctx* c, const uint32_t* chunk_file, const uint64_t*
   if (int rc = p.counts(d_cts)) return rc;
   if (cts.sets > h || cts.members > nf) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
   d_set_rep.first(cts.sets), d_set_files.first(cts.sets), d_set_total.first(cts.sets), d_set_stored.first(cts.sets);
+  if (int rc = p.download()) return rc;
+  if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+// ---- the family recipes (family_recipes.hip) -------------------------------------------
+
+int sdcas_family_recipes_plan(uint64_t m, uint64_t n_files, uint64_t* out_workspace_bytes) {
+  const char* why = nullptr;
+  if (int rc = family_bytes_range(m, n_files, &why)) return rc;
+  if (out_workspace_bytes) *out_workspace_bytes = family_recipes_layout(m, n_files).bytes;
+  return SDCAS_OK;
+}
+
+// a call's arguments (host or device arrays): family_bytes' and the offsets
+static int family_recipes_args(sdcas_ctx* c, const char* who, const void* chunk_file, const void* chunk_off,
+                               const void* chunk_len, const void* rep, size_t m, const void* family, size_t n_files) {
+  if (int rc = family_bytes_args(c, who, chunk_file, chunk_len, rep, m, family, n_files)) return rc;
+  if (m && !chunk_off) return c->fail(SDCAS_E_INVALID, "%s: null chunk_off", who);
+  return SDCAS_OK;
+}
+
+int sdcas_dev_family_recipes(sdcas_ctx* c, const uint32_t* d_chunk_file, const uint64_t* d_chunk_off,
+                             const uint64_t* d_chunk_len, const int64_t* d_rep, size_t m, const int64_t* d_family,
+                             size_t n_files, uint32_t* d_op_chunk, uint32_t* d_op_src_chunk, uint32_t* d_op_row,
+                             uint32_t* d_op_src_row, uint64_t* d_op_dst_off, uint64_t* d_op_src_off,
+                             uint64_t* d_op_len, uint32_t* d_chunk_op, uint32_t* d_row_ops, uint32_t* d_row_first_op,
+                             uint64_t* d_counts, void* stream) {
+  const char* who = "dev_family_recipes";
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = family_recipes_args(c, who, d_chunk_file, d_chunk_off, d_chunk_len, d_rep, m, d_family, n_files))
+    return rc;
+  if (index_misaligned({}, {d_chunk_off, d_chunk_len, d_rep, d_family, d_op_dst_off, d_op_src_off, d_op_len, d_counts},
+                       {d_chunk_file, d_op_chunk, d_op_src_chunk, d_op_row, d_op_src_row, d_chunk_op, d_row_ops,
+                        d_row_first_op}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (u32 arrays 4 B, others 8 B)", who);
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = grow_synced(c, c->fr_ws, (size_t)family_recipes_layout(m, n_files).bytes, call.st,
+                           "family recipes workspace"))
+    return rc;
+  const FamilyRecipesIn in{{d_chunk_file, d_chunk_len, d_rep, d_family, (uint32_t)m, (uint32_t)n_files}, d_chunk_off};
+  const FamilyRecipesOut out{d_op_chunk,   d_op_src_chunk, d_op_row,   d_op_src_row, d_op_dst_off,
+                             d_op_src_off, d_op_len,       d_chunk_op, d_row_ops,    d_row_first_op};
+  hipError_t e = family_recipes(c->fr_ws.p, in, out, (unsigned long long*)d_counts, call.st);
+  return e ? hip_fail_at(c, e, who, "") : SDCAS_OK;
+}
+
+int sdcas_family_recipes(sdcas_ctx* c, const uint32_t* chunk_file, const uint64_t* chunk_off,
+                         const uint64_t* chunk_len, const int64_t* rep, size_t m, const int64_t* family,
+                         size_t n_files, uint32_t* out_op_chunk, uint32_t* out_op_src_chunk, uint32_t* out_op_row,
+                         uint32_t* out_op_src_row, uint64_t* out_op_dst_off, uint64_t* out_op_src_off,
+                         uint64_t* out_op_len, uint32_t* out_chunk_op, uint32_t* out_row_ops,
+                         uint32_t* out_row_first_op, sdcas_family_recipes_counts* out_counts) {
+  static_assert(sizeof(sdcas_family_recipes_counts) == kFamilyRecipesCounts * sizeof(uint64_t), "eight u64 counts");
+  const char* who = "family_recipes";
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = family_recipes_args(c, who, chunk_file, chunk_off, chunk_len, rep, m, family, n_files)) return rc;
+  if (index_misaligned({}, {chunk_off, chunk_len, rep, family, out_op_dst_off, out_op_src_off, out_op_len, out_counts},
+                       {chunk_file, out_op_chunk, out_op_src_chunk, out_op_row, out_op_src_row, out_chunk_op,
+                        out_row_ops, out_row_first_op}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (u32 arrays 4 B, others 8 B)", who);
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  const size_t nf = n_files;
+  sdcas_family_recipes_counts cts;
+  Parts p(c, st, who);
+  const auto d_file = p.in(chunk_file, m);
+  const auto d_off = p.in(chunk_off, m);
+  const auto d_len = p.in(chunk_len, m);
+  const auto d_rep = p.in(rep, m);
+  const auto d_family = p.in(family, nf);
+  const auto d_op_chunk = p.out(out_op_chunk, m);  // no more ops than chunks
+  const auto d_op_src_chunk = p.out(out_op_src_chunk, m);
+  const auto d_op_row = p.out(out_op_row, m);
+  const auto d_op_src_row = p.out(out_op_src_row, m);
+  const auto d_op_dst_off = p.out(out_op_dst_off, m);
+  const auto d_op_src_off = p.out(out_op_src_off, m);
+  const auto d_op_len = p.out(out_op_len, m);
+  const auto d_chunk_op = p.out(out_chunk_op, m);
+  const auto d_row_ops = p.out(out_row_ops, nf);
+  const auto d_row_first = p.out(out_row_first_op, nf);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = grow_synced(c, c->fr_ws, (size_t)family_recipes_layout(m, n_files).bytes, st,
+                           "family recipes workspace"))
+    return rc;
+  if (int rc = p.upload()) return rc;
+  const FamilyRecipesIn in{{d_file, d_len, d_rep, d_family, (uint32_t)m, (uint32_t)n_files}, d_off};
+  const FamilyRecipesOut out{d_op_chunk,   d_op_src_chunk, d_op_row,   d_op_src_row, d_op_dst_off,
+                             d_op_src_off, d_op_len,       d_chunk_op, d_row_ops,    d_row_first};
+  if (hipError_t e = family_recipes(c->fr_ws.p, in, out, d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  if (int rc = p.counts(d_cts)) return rc;
+  if (cts.ops > m || cts.chunks > m || cts.files > nf) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
+  d_op_chunk.first(cts.ops), d_op_src_chunk.first(cts.ops), d_op_row.first(cts.ops), d_op_src_row.first(cts.ops);
+  d_op_dst_off.first(cts.ops), d_op_src_off.first(cts.ops), d_op_len.first(cts.ops);
   if (int rc = p.download()) return rc;
   if (out_counts) *out_counts = cts;
   return SDCAS_OK;

@@ -1183,18 +1183,24 @@ class Engine:
         goes under "families_" + key and the reclaimable-ordered form keeps the
         plain name. ValueError when a result lacks the chunk arrays or its rows
         do not match its ids: dropped rows are not supported here."""
+        fam, fl, ln, rep = self._family_inputs(results, file_ids, num, den, "family_bytes_of")
+        return self._family_bytes_merged(fam, fl, ln, rep)
+
+    def _family_inputs(self, results, file_ids, num, den, who):
+        """family_bytes_of's and family_recipes_of's common start -> (families_of's
+        dict, chunk_file, chunk_len, rep) over the concatenated rows"""
         results, file_ids = list(results), [_arr(x, np.uint64) for x in file_ids]
         if len(results) != len(file_ids):
-            raise ValueError(f"family_bytes_of: {len(results)} results, {len(file_ids)} id arrays")
+            raise ValueError(f"{who}: {len(results)} results, {len(file_ids)} id arrays")
         for r in results:
             for key in ("chunk_file", "chunk_len", "chunk_keys", "chunk_digests"):
                 if key not in r:
-                    raise ValueError(f"family_bytes_of: a result has no {key} (similar_files_indexed(..., chunks=True))")
+                    raise ValueError(f"{who}: a result has no {key} (similar_files_indexed(..., chunks=True))")
         fl, ln, keys, dig, row0 = [], [], [], [], 0
         for r, ids in zip(results, file_ids):
             cf = _arr(r["chunk_file"], np.uint32)
             if np.asarray(r["sizes"]).size != ids.size or (cf.size and int(cf.max()) >= ids.size):
-                raise ValueError("family_bytes_of: a result's rows do not match its ids (dropped rows are not supported)")
+                raise ValueError(f"{who}: a result's rows do not match its ids (dropped rows are not supported)")
             fl.append((cf.astype(np.uint64) + row0).astype(np.uint32))
             ln.append(_arr(r["chunk_len"], np.uint64))
             keys.append(_arr(r["chunk_keys"], np.uint64))
@@ -1206,6 +1212,9 @@ class Engine:
         dig = np.concatenate([np.zeros((0, 32), np.uint8)] + dig)
         fam = self.families_of(results, file_ids, num, den)
         rep = self.confirm_duplicates(keys, dig)[0]
+        return fam, fl, ln, rep
+
+    def _family_bytes_merged(self, fam, fl, ln, rep):
         out = dict(fam)
         for key in ("set_rep", "set_offsets", "members", "counts"):
             out["families_" + key] = out.pop(key)
@@ -1223,6 +1232,94 @@ class Engine:
         r = self.similar_files_indexed(paths, ids, ChunkHolders(self), params, window_bytes, peers=int(k),
                                        max_holders=max_holders, chunks=True)
         out = self.family_bytes_of([r], [ids], num, den)
+        out["sizes"] = r["sizes"]
+        return out
+
+    # -- family recipes: the byte ranges that rebuild every file from its family's stored bytes
+    @staticmethod
+    def family_recipes_plan(m, n_files):
+        """sdcas_family_recipes_plan (no GPU) -> workspace_bytes: what the device
+        call takes for m chunks of n_files rows; SdcasError beyond the ranges"""
+        ws = ctypes.c_uint64(0)
+        rc = N.load().sdcas_family_recipes_plan(int(m), int(n_files), ctypes.byref(ws))
+        if rc != N.SDCAS_OK:
+            raise N.SdcasError(rc, f"family_recipes_plan({m}, {n_files})")
+        return int(ws.value)
+
+    @staticmethod
+    def running_offsets(chunk_file, chunk_len):
+        """the per-file running sums of chunk_len in position order, uint64[m]
+        (modulo 2^64): a chunk's offset in its file when the chunks of a file
+        cover it in order, as every chunker here writes them"""
+        fl, ln = _arr(chunk_file, np.uint32), _arr(chunk_len, np.uint64)
+        if fl.size != ln.size:
+            raise ValueError(f"running_offsets: {fl.size} chunk files, {ln.size} lengths")
+        order = np.argsort(fl, kind="stable")
+        sf, sl = fl[order], ln[order]
+        before = np.cumsum(sl, dtype=np.uint64) - sl
+        start = np.flatnonzero(np.concatenate([np.ones(min(sf.size, 1), bool), sf[1:] != sf[:-1]]))
+        runs = np.diff(np.concatenate([start, [sf.size]]))
+        off = np.zeros(fl.size, np.uint64)
+        off[order] = before - np.repeat(before[start], runs)
+        return off
+
+    def family_recipes(self, chunk_file, chunk_len, rep, family, chunk_off=None):
+        """sdcas_family_recipes over host arrays: family_bytes' inputs and
+        chunk_off uint64[m], a chunk's offset in its file (None: the per-file
+        running sums of chunk_len in position order, computed on the host). ->
+        dict: per op, in order of the head chunks, "op_chunk", "op_src_chunk",
+        "op_row", "op_src_row" uint32[ops], "op_dst_off", "op_src_off", "op_len"
+        uint64[ops] and "op_literal" bool[ops] (the row keeps these bytes; else
+        the op copies op_len bytes from op_src_off of op_src_row); "chunk_op"
+        uint32[m] (0xFFFFFFFF: the chunk takes no part); "row_ops" and
+        "row_first_op" uint32[n] (a row of adjacent chunks has the ops
+        [row_first_op, row_first_op + row_ops)); "chunk_off" as used; "counts":
+        sdcas_family_recipes_counts' eight fields. rebuild_files applies them."""
+        fl, ln, rp = _arr(chunk_file, np.uint32), _arr(chunk_len, np.uint64), _arr(rep, np.int64)
+        fam = _arr(family, np.int64)
+        m, n = fl.size, fam.size
+        if ln.size != m or rp.size != m:
+            raise ValueError(f"family_recipes: {m} chunk files, {ln.size} lengths, {rp.size} reps")
+        off = self.running_offsets(fl, ln) if chunk_off is None else _arr(chunk_off, np.uint64)
+        if off.size != m:
+            raise ValueError(f"family_recipes: {m} chunk files, {off.size} offsets")
+        op32 = [np.zeros(m, np.uint32) for _ in range(4)]
+        op64 = [np.zeros(m, np.uint64) for _ in range(3)]
+        chunk_op, row_ops, row_first = np.zeros(m, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        counts = N.FamilyRecipesCounts()
+        self._check(self.L.sdcas_family_recipes(self.ctx, _ptr(fl), _ptr(off), _ptr(ln), _ptr(rp), m, _ptr(fam), n,
+                                                *(a.ctypes.data for a in op32 + op64), chunk_op.ctypes.data,
+                                                row_ops.ctypes.data, row_first.ctypes.data, ctypes.byref(counts)),
+                    "sdcas_family_recipes")
+        k = int(counts.ops)
+        names = ("op_chunk", "op_src_chunk", "op_row", "op_src_row", "op_dst_off", "op_src_off", "op_len")
+        out = {name: a[:k].copy() for name, a in zip(names, op32 + op64)}
+        out.update({"op_literal": out["op_chunk"] == out["op_src_chunk"], "chunk_op": chunk_op, "row_ops": row_ops,
+                    "row_first_op": row_first, "chunk_off": off, "counts": counts.as_dict()})
+        return out
+
+    def family_recipes_of(self, results, file_ids, num=1, den=2):
+        """family_bytes_of plus the recipes: its inputs, its dict, and under
+        "recipes" family_recipes' dict over the same concatenated chunk arrays,
+        rep and families, with chunk_off the per-file running sums (the chunks
+        of a file cover it in order). Rows are numbered as in families_of.
+        ValueError as family_bytes_of: dropped rows are not supported here."""
+        fam, fl, ln, rep = self._family_inputs(results, file_ids, num, den, "family_recipes_of")
+        out = self._family_bytes_merged(fam, fl, ln, rep)
+        out["recipes"] = self.family_recipes(fl, ln, rep, fam["family"])
+        return out
+
+    def similar_recipes(self, paths, k=4, max_holders=64, num=1, den=2, params=None, window_bytes=256 << 20):
+        """similar_families plus the recipes: family_recipes_of over one
+        similar_files_indexed(paths, arange(n), ChunkHolders(self), ...,
+        peers=k, chunks=True). Rows are the paths in order. -> similar_families'
+        dict plus "recipes"; rebuild_files(out["recipes"], read) gives every
+        file back from the literal ranges alone."""
+        paths = [os.fspath(p) for p in paths]
+        ids = np.arange(len(paths), dtype=np.uint64)
+        r = self.similar_files_indexed(paths, ids, ChunkHolders(self), params, window_bytes, peers=int(k),
+                                       max_holders=max_holders, chunks=True)
+        out = self.family_recipes_of([r], [ids], num, den)
         out["sizes"] = r["sizes"]
         return out
 
@@ -1338,6 +1435,24 @@ class Engine:
                                                   set_rep or None, set_files or None, set_total or None,
                                                   set_stored or None, counts or None, stream or None),
                     "dev_family_bytes")
+
+    def dev_family_recipes(self, chunk_file, chunk_off, chunk_len, rep, m, family, n_files, op_chunk=0, op_src_chunk=0,
+                           op_row=0, op_src_row=0, op_dst_off=0, op_src_off=0, op_len=0, chunk_op=0, row_ops=0,
+                           row_first_op=0, counts=0, stream=0):
+        """family_recipes over device arrays (sdcas_dev_family_recipes), e.g.
+        dev_chunk's chunk_file / chunk_off / chunk_len, dev_confirm_duplicates'
+        rep and dev_file_families' family as they are; the four uint32 and
+        three uint64 op arrays of m entries each (the first `ops` are written),
+        chunk_op uint32[m], row_ops and row_first_op uint32[n_files], counts
+        eight uint64; any output may be 0. Nothing waits for the device once
+        the workspace for (m, n_files) exists"""
+        self._check(self.L.sdcas_dev_family_recipes(self.ctx, chunk_file or None, chunk_off or None, chunk_len or None,
+                                                    rep or None, int(m), family or None, int(n_files),
+                                                    op_chunk or None, op_src_chunk or None, op_row or None,
+                                                    op_src_row or None, op_dst_off or None, op_src_off or None,
+                                                    op_len or None, chunk_op or None, row_ops or None,
+                                                    row_first_op or None, counts or None, stream or None),
+                    "dev_family_recipes")
 
     def dev_chunk_windows(self, blob, offs, lens, final, n, max_chunks, max_slots, params=None, file_chunks=0,
                           chunk_off=0, chunk_len=0, chunk_file=0, keys=0, digests=0, consumed=0, counts=0, stream=0):
