@@ -1428,6 +1428,139 @@ int sdcas_dev_family_recipes(sdcas_ctx *ctx, const uint32_t *d_chunk_file, const
                              uint64_t *d_op_len, uint32_t *d_chunk_op, uint32_t *d_row_ops,
                              uint32_t *d_row_first_op, uint64_t *d_counts, void *stream);
 
+/* ---- family store: pack the literal bytes and restore files from them ------------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * The family recipes say which byte ranges rebuild every row. These calls move
+ * the bytes: the literal ranges gathered into one dense STORE, every op pointed
+ * at its place there, and any window of any row given back from the store alone.
+ *
+ * LAYOUT. Over the op arrays of sdcas_family_recipes, as they are, with its
+ * chunk_op[m] and the number of ops (d_ops on the device: the recipes' d_counts
+ * + 2; the calls use min(ops, max_ops)). All arithmetic is modulo 2^64.
+ *   literal op o (op_chunk[o] == op_src_chunk[o]):
+ *     store_off[o] = the sum of op_len over the literal ops below o. The store
+ *     is dense; store_bytes is the sum over all literal ops (the recipes'
+ *     literal_bytes).
+ *   copy op o, with s = op_src_chunk[o] and L = chunk_op[s], is COVERED when
+ *     s < m and L < ops; L is a literal op; op_row[L] == op_src_row[o];
+ *     op_src_off[o] >= op_dst_off[L]; and with d = op_src_off[o] -
+ *     op_dst_off[L]: d <= op_len[L] and op_len[o] <= op_len[L] - d.
+ *     Then store_off[o] = store_off[L] + d. Otherwise store_off[o] is
+ *     SDCAS_STORE_NONE and the op is counted in uncovered_ops and
+ *     uncovered_bytes (so is a covered op whose offset comes out as 2^64 - 1).
+ *   Entries of out_op_store_off at or past `ops` are left as they were.
+ * Example, the recipes' v1 = A B C and v2 = A B X C: store_off [0, 0, 60, 30],
+ * store_bytes 65, no op uncovered. For recipes whose chunk_off are the running
+ * sums of chunk_len per file no op is uncovered: a copy's source chunk f is a
+ * literal chunk, the op L = chunk_op[f] is the maximal run of literal chunks
+ * around f, and the copy's chunks continue only while their sources continue
+ * each other as literals of one row, which is the rule that keeps them in L.
+ *
+ * THE MOVER. Rows are described by three arrays over n_files:
+ *   row_at[i]   u64  where the row's window starts in the blob
+ *   row_base[i] u64  the file offset of the window's first byte (NULL: zeros)
+ *   row_len[i]  u64  the bytes of the row present in the blob; 0: the row is absent
+ * An op's range [dst_off, dst_off + len) is clipped to its row's window [base,
+ * base + row_len), giving [lo, hi); only hi - lo bytes move. A corpus larger
+ * than memory goes window by window against one layout, a file larger than a
+ * window piece by piece; no state is carried between calls.
+ *   pack     every literal op with a store offset: blob[row_at + (lo - base) ..]
+ *            to store[store_off + (lo - dst_off) ..]
+ *   restore  every op with a store offset: the other way. Window bytes that no
+ *            op covers are left as they were.
+ * An op that the call acts on is BAD, skipped whole and counted, when its row is
+ * >= n_files; dst_off + len wraps; its store range [store_off, store_off + len)
+ * is not inside the store (off <= cap && len <= cap - off, cap the call's
+ * store_capacity or store_bytes); or its row is present and its window is not
+ * inside the blob (row_at <= blob_bytes && row_len <= blob_bytes - row_at) or
+ * base + row_len wraps. Arbitrary op arrays are therefore safe.
+ * Memory contract:
+ *   writes   exactly the destination bytes of the clipped ops, and no other byte
+ *            of the store, the blob or the gaps between windows;
+ *   reads    of blob and store only 16-byte aligned granules that hold at least
+ *            one source byte;
+ *   d_blob and d_store are 16-byte aligned and readable up to the next multiple
+ *            of 16 past their byte counts;
+ *   the windows of two rows that overlap in the blob, or two ops with a common
+ *            destination byte, are the caller's: the result is unspecified in
+ *            those bytes and never outside them.
+ * Counts: ops_moved (ops with at least one byte in a window), bytes_moved,
+ * bad_ops, tiles (the clipped ops cut into sdcas_family_store_tile_bytes()
+ * destination bytes at 16-byte aligned destination addresses: a clipped op of n
+ * bytes to address a has ceil((a % 16 + n) / tile) tiles).
+ * Errors, all before anything is enqueued: SDCAS_E_INVALID for a needed NULL
+ * pointer (the op arrays, the store offsets and d_ops with max_ops != 0;
+ * chunk_op with m != 0; row_at and row_len with n_files != 0; the blob or the
+ * store with a non-zero byte count) or a misalignment (16 bytes for blob and
+ * store, 8 for u64, 4 for u32); SDCAS_E_CAPACITY for max_ops, m or n_files above
+ * 2^30. Any count output may be NULL. Results are exact and do not depend on
+ * scheduling. */
+#define SDCAS_STORE_NONE UINT64_MAX
+typedef struct sdcas_family_store_counts {
+  uint64_t ops;             /* min(ops, max_ops) */
+  uint64_t literal_ops;
+  uint64_t copy_ops;
+  uint64_t uncovered_ops;   /* copy ops without a store offset */
+  uint64_t store_bytes;     /* the sum of the literal ops' len */
+  uint64_t uncovered_bytes; /* the sum of the uncovered ops' len */
+} sdcas_family_store_counts;
+typedef struct sdcas_family_move_counts {
+  uint64_t ops_moved;
+  uint64_t bytes_moved;
+  uint64_t bad_ops;
+  uint64_t tiles;
+} sdcas_family_move_counts;
+/* GPU-free: the mover's tile in destination bytes, a positive multiple of 16. */
+uint64_t sdcas_family_store_tile_bytes(void);
+/* GPU-free: the range checks (max_ops, n_files) and *out_workspace_bytes = what
+ * the three device calls share (32 bytes per op, 8 KiB of counters and a
+ * little). The output may be NULL. */
+int sdcas_family_store_plan(uint64_t max_ops, uint64_t n_files, uint64_t *out_workspace_bytes);
+/* Device arrays under sdcas_dev_chunk_peers' stream rules. d_counts: six u64 in
+ * sdcas_family_store_counts' order, overwritten; d_op_store_off may be NULL.
+ * The workspace for max_ops is allocated by the first of the three calls that
+ * needs it, which waits for the stream; after that no call waits for the
+ * device. Every grid is sized from max_ops or a constant. */
+int sdcas_dev_family_store_layout(sdcas_ctx *ctx, const uint32_t *d_op_chunk, const uint32_t *d_op_src_chunk,
+                                  const uint32_t *d_op_row, const uint32_t *d_op_src_row,
+                                  const uint64_t *d_op_dst_off, const uint64_t *d_op_src_off,
+                                  const uint64_t *d_op_len, const uint32_t *d_chunk_op, size_t m,
+                                  const uint64_t *d_ops, size_t max_ops, uint64_t *d_op_store_off,
+                                  uint64_t *d_counts, void *stream);
+/* d_counts: four u64 in sdcas_family_move_counts' order, overwritten. */
+int sdcas_dev_family_pack(sdcas_ctx *ctx, const uint32_t *d_op_chunk, const uint32_t *d_op_src_chunk,
+                          const uint32_t *d_op_row, const uint64_t *d_op_dst_off, const uint64_t *d_op_len,
+                          const uint64_t *d_op_store_off, const uint64_t *d_ops, size_t max_ops,
+                          const uint64_t *d_row_at, const uint64_t *d_row_base, const uint64_t *d_row_len,
+                          size_t n_files, const uint8_t *d_blob, uint64_t blob_bytes, uint8_t *d_store,
+                          uint64_t store_capacity, uint64_t *d_counts, void *stream);
+int sdcas_dev_family_restore(sdcas_ctx *ctx, const uint32_t *d_op_row, const uint64_t *d_op_dst_off,
+                             const uint64_t *d_op_len, const uint64_t *d_op_store_off, const uint64_t *d_ops,
+                             size_t max_ops, const uint64_t *d_row_at, const uint64_t *d_row_base,
+                             const uint64_t *d_row_len, size_t n_files, const uint8_t *d_store,
+                             uint64_t store_bytes, uint8_t *d_blob, uint64_t blob_bytes, uint64_t *d_counts,
+                             void *stream);
+/* Host arrays: one upload, the device call, one download. `ops` entries of
+ * every op array. pack's store and restore's blob go up and come down again, so
+ * the bytes the call does not write stay as the caller had them. */
+int sdcas_family_store_layout(sdcas_ctx *ctx, const uint32_t *op_chunk, const uint32_t *op_src_chunk,
+                              const uint32_t *op_row, const uint32_t *op_src_row, const uint64_t *op_dst_off,
+                              const uint64_t *op_src_off, const uint64_t *op_len, size_t ops,
+                              const uint32_t *chunk_op, size_t m, uint64_t *out_op_store_off,
+                              sdcas_family_store_counts *out_counts);
+int sdcas_family_pack(sdcas_ctx *ctx, const uint32_t *op_chunk, const uint32_t *op_src_chunk,
+                      const uint32_t *op_row, const uint64_t *op_dst_off, const uint64_t *op_len,
+                      const uint64_t *op_store_off, size_t ops, const uint64_t *row_at, const uint64_t *row_base,
+                      const uint64_t *row_len, size_t n_files, const uint8_t *blob, uint64_t blob_bytes,
+                      uint8_t *store, uint64_t store_capacity, sdcas_family_move_counts *out_counts);
+int sdcas_family_restore(sdcas_ctx *ctx, const uint32_t *op_row, const uint64_t *op_dst_off,
+                         const uint64_t *op_len, const uint64_t *op_store_off, size_t ops, const uint64_t *row_at,
+                         const uint64_t *row_base, const uint64_t *row_len, size_t n_files, const uint8_t *store,
+                         uint64_t store_bytes, uint8_t *blob, uint64_t blob_bytes,
+                         sdcas_family_move_counts *out_counts);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

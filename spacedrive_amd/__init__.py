@@ -8,7 +8,8 @@ include/sdcas.h.
 """
 from .engine import (ChunkHolders, ChunkIndex, Engine, Node, default_engine, digest_to_hex, file_checksum, generate_cas_id,
                      io_error, key_to_hex)
-from .recipes import rebuild_files
+from .recipes import pack_store, rebuild_files, restore_from_store, store_layout
+from .store import FamilyStore
 
-__all__ = ["ChunkHolders", "ChunkIndex", "Engine", "Node", "default_engine", "digest_to_hex", "file_checksum", "generate_cas_id", "io_error",
-           "key_to_hex", "rebuild_files"]
+__all__ = ["ChunkHolders", "ChunkIndex", "Engine", "FamilyStore", "Node", "default_engine", "digest_to_hex", "file_checksum", "generate_cas_id", "io_error",
+           "key_to_hex", "pack_store", "rebuild_files", "restore_from_store", "store_layout"]

@@ -76,6 +76,9 @@ ABI_SYMBOLS = [
     "sdcas_file_families_plan", "sdcas_file_families", "sdcas_dev_file_families",  # added after ABI 7
     "sdcas_family_bytes_plan", "sdcas_family_bytes", "sdcas_dev_family_bytes",  # added after ABI 7
     "sdcas_family_recipes_plan", "sdcas_family_recipes", "sdcas_dev_family_recipes",  # added after ABI 7
+    "sdcas_family_store_tile_bytes", "sdcas_family_store_plan", "sdcas_family_store_layout", "sdcas_family_pack",
+    "sdcas_family_restore", "sdcas_dev_family_store_layout", "sdcas_dev_family_pack",
+    "sdcas_dev_family_restore",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -262,6 +265,25 @@ class FamilyRecipesCounts(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class FamilyStoreCounts(ctypes.Structure):
+    """sdcas_family_store_counts"""
+    _fields_ = [("ops", ctypes.c_uint64), ("literal_ops", ctypes.c_uint64), ("copy_ops", ctypes.c_uint64),
+                ("uncovered_ops", ctypes.c_uint64), ("store_bytes", ctypes.c_uint64),
+                ("uncovered_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class FamilyMoveCounts(ctypes.Structure):
+    """sdcas_family_move_counts"""
+    _fields_ = [("ops_moved", ctypes.c_uint64), ("bytes_moved", ctypes.c_uint64), ("bad_ops", ctypes.c_uint64),
+                ("tiles", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _lib_path = LIB_PATH
 
@@ -378,6 +400,17 @@ def load():
     L.sdcas_family_recipes.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz] + [_vp] * 10 + [
         ctypes.POINTER(FamilyRecipesCounts)]
     L.sdcas_dev_family_recipes.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz] + [_vp] * 12
+    L.sdcas_family_store_tile_bytes.argtypes = []
+    L.sdcas_family_store_tile_bytes.restype = _u64
+    L.sdcas_family_store_plan.argtypes = [_u64, _u64, _vp]
+    L.sdcas_dev_family_store_layout.argtypes = [_vp] * 9 + [_sz, _vp, _sz, _vp, _vp, _vp]
+    L.sdcas_dev_family_pack.argtypes = [_vp] * 8 + [_sz, _vp, _vp, _vp, _sz, _vp, _u64, _vp, _u64, _vp, _vp]
+    L.sdcas_dev_family_restore.argtypes = [_vp] * 6 + [_sz, _vp, _vp, _vp, _sz, _vp, _u64, _vp, _u64, _vp, _vp]
+    L.sdcas_family_store_layout.argtypes = [_vp] * 8 + [_sz, _vp, _sz, _vp, ctypes.POINTER(FamilyStoreCounts)]
+    L.sdcas_family_pack.argtypes = [_vp] * 7 + [_sz, _vp, _vp, _vp, _sz, _vp, _u64, _vp, _u64,
+                                                ctypes.POINTER(FamilyMoveCounts)]
+    L.sdcas_family_restore.argtypes = [_vp] * 5 + [_sz, _vp, _vp, _vp, _sz, _vp, _u64, _vp, _u64,
+                                                   ctypes.POINTER(FamilyMoveCounts)]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

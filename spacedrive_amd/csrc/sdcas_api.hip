@@ -39,6 +39,7 @@
 #include "families.h"
 #include "family_bytes.h"
 #include "family_recipes.h"
+#include "family_store.h"
 #include "chunk_index.h"
 #include "dist_dedup.h"
 #include "synth.h"
@@ -243,6 +244,8 @@ struct sdcas_ctx {
   DevBuf<uint8_t> fb_ws;
   // the family recipes (family_recipes.hip): the class table, the chunks' sources and ops
   DevBuf<uint8_t> fr_ws;
+  // the family store (family_store.hip): the op sums, tile starts and clipped ranges
+  DevBuf<uint8_t> fs_ws;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -3564,6 +3567,236 @@ int sdcas_family_recipes(sdcas_ctx* c, const uint32_t* chunk_file, const uint64_
   if (int rc = p.download()) return rc;
   if (out_counts) *out_counts = cts;
   return SDCAS_OK;
+}
+
+// ---- the family store (family_store.hip) -----------------------------------------------
+
+uint64_t sdcas_family_store_tile_bytes(void) { return kFamilyStoreTile; }
+
+static int family_store_range(uint64_t max_ops, uint64_t m, uint64_t n_files, const char** why) {
+  if (max_ops > kFamilyStoreMaxOps) return *why = "more than 2^30 ops", SDCAS_E_CAPACITY;
+  if (m > kFamilyStoreMaxOps) return *why = "more than 2^30 chunks", SDCAS_E_CAPACITY;
+  if (n_files > kFamilyStoreMaxFiles) return *why = "more than 2^30 files", SDCAS_E_CAPACITY;
+  return SDCAS_OK;
+}
+
+int sdcas_family_store_plan(uint64_t max_ops, uint64_t n_files, uint64_t* out_workspace_bytes) {
+  const char* why = nullptr;
+  if (int rc = family_store_range(max_ops, 0, n_files, &why)) return rc;
+  if (out_workspace_bytes) *out_workspace_bytes = family_store_layout(max_ops).bytes;
+  return SDCAS_OK;
+}
+
+// the layout call's arguments (host or device arrays)
+static int family_store_layout_args(sdcas_ctx* c, const char* who, const FamilyStoreOps& o, const void* chunk_op,
+                                    size_t m, size_t max_ops, const void* store_off, const void* counts) {
+  const char* why = nullptr;
+  if (int rc = family_store_range(max_ops, m, 0, &why)) return c->fail(rc, "%s: %s", who, why);
+  if (max_ops && (!o.op_chunk || !o.op_src_chunk || !o.op_row || !o.op_src_row || !o.op_dst_off || !o.op_src_off ||
+                  !o.op_len || !o.d_ops))
+    return c->fail(SDCAS_E_INVALID, "%s: a null op array or null ops", who);
+  if (m && !chunk_op) return c->fail(SDCAS_E_INVALID, "%s: null chunk_op", who);
+  if (index_misaligned({}, {o.op_dst_off, o.op_src_off, o.op_len, o.d_ops, store_off, counts},
+                       {o.op_chunk, o.op_src_chunk, o.op_row, o.op_src_row, chunk_op}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (u32 arrays 4 B, others 8 B)", who);
+  return SDCAS_OK;
+}
+
+// a mover call's arguments (device arrays; the host forms check their own before they stage them)
+static int family_store_move_args(sdcas_ctx* c, const char* who, bool restore, const FamilyStoreOps& o,
+                                  const void* store_off, size_t max_ops, const FamilyStoreRows& r, size_t n_files,
+                                  const void* blob, uint64_t blob_bytes, const void* store, uint64_t store_bytes,
+                                  const void* counts, bool device) {
+  const char* why = nullptr;
+  if (int rc = family_store_range(max_ops, 0, n_files, &why)) return c->fail(rc, "%s: %s", who, why);
+  if (max_ops && (!o.op_row || !o.op_dst_off || !o.op_len || !store_off || !o.d_ops ||
+                  (!restore && (!o.op_chunk || !o.op_src_chunk))))
+    return c->fail(SDCAS_E_INVALID, "%s: a null op array, null store offsets or null ops", who);
+  if (n_files && (!r.row_at || !r.row_len)) return c->fail(SDCAS_E_INVALID, "%s: null row_at or row_len", who);
+  if ((blob_bytes && !blob) || (store_bytes && !store)) return c->fail(SDCAS_E_INVALID, "%s: null blob or store", who);
+  if (index_misaligned({device ? blob : nullptr, device ? store : nullptr},
+                       {o.op_dst_off, o.op_len, o.d_ops, store_off, r.row_at, r.row_base, r.row_len, counts},
+                       {o.op_chunk, o.op_src_chunk, o.op_row}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (blob and store 16 B, u32 arrays 4 B, others 8 B)",
+                   who);
+  return SDCAS_OK;
+}
+
+int sdcas_dev_family_store_layout(sdcas_ctx* c, const uint32_t* d_op_chunk, const uint32_t* d_op_src_chunk,
+                                  const uint32_t* d_op_row, const uint32_t* d_op_src_row,
+                                  const uint64_t* d_op_dst_off, const uint64_t* d_op_src_off,
+                                  const uint64_t* d_op_len, const uint32_t* d_chunk_op, size_t m,
+                                  const uint64_t* d_ops, size_t max_ops, uint64_t* d_op_store_off,
+                                  uint64_t* d_counts, void* stream) {
+  const char* who = "dev_family_store_layout";
+  if (!c) return SDCAS_E_INVALID;
+  const FamilyStoreOps ops{d_op_chunk,   d_op_src_chunk, d_op_row, d_op_src_row,     d_op_dst_off,
+                           d_op_src_off, d_op_len,       d_ops,    (uint32_t)max_ops};
+  if (int rc = family_store_layout_args(c, who, ops, d_chunk_op, m, max_ops, d_op_store_off, d_counts)) return rc;
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = grow_synced(c, c->fs_ws, (size_t)family_store_layout(max_ops).bytes, call.st, "family store workspace"))
+    return rc;
+  hipError_t e = family_store_offsets(c->fs_ws.p, ops, d_chunk_op, (uint32_t)m, d_op_store_off,
+                                      (unsigned long long*)d_counts, call.st);
+  return e ? hip_fail_at(c, e, who, "") : SDCAS_OK;
+}
+
+static int family_store_dev_move(sdcas_ctx* c, const char* who, bool restore, const FamilyStoreOps& ops,
+                                 const uint64_t* d_op_store_off, size_t max_ops, const FamilyStoreRows& rows,
+                                 size_t n_files, uint8_t* d_blob, uint64_t blob_bytes, uint8_t* d_store,
+                                 uint64_t store_bytes, uint64_t* d_counts, void* stream) {
+  if (!c) return SDCAS_E_INVALID;
+  if (int rc = family_store_move_args(c, who, restore, ops, d_op_store_off, max_ops, rows, n_files, d_blob, blob_bytes,
+                                      d_store, store_bytes, d_counts, true))
+    return rc;
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = grow_synced(c, c->fs_ws, (size_t)family_store_layout(max_ops).bytes, call.st, "family store workspace"))
+    return rc;
+  hipError_t e = family_store_move(c->fs_ws.p, ops, d_op_store_off, rows, d_blob, blob_bytes, d_store, store_bytes,
+                                   restore, (unsigned long long*)d_counts, call.st);
+  return e ? hip_fail_at(c, e, who, "") : SDCAS_OK;
+}
+
+int sdcas_dev_family_pack(sdcas_ctx* c, const uint32_t* d_op_chunk, const uint32_t* d_op_src_chunk,
+                          const uint32_t* d_op_row, const uint64_t* d_op_dst_off, const uint64_t* d_op_len,
+                          const uint64_t* d_op_store_off, const uint64_t* d_ops, size_t max_ops,
+                          const uint64_t* d_row_at, const uint64_t* d_row_base, const uint64_t* d_row_len,
+                          size_t n_files, const uint8_t* d_blob, uint64_t blob_bytes, uint8_t* d_store,
+                          uint64_t store_capacity, uint64_t* d_counts, void* stream) {
+  const FamilyStoreOps ops{d_op_chunk, d_op_src_chunk, d_op_row, nullptr,          d_op_dst_off,
+                           nullptr,    d_op_len,       d_ops,    (uint32_t)max_ops};
+  const FamilyStoreRows rows{d_row_at, d_row_base, d_row_len, (uint32_t)n_files};
+  return family_store_dev_move(c, "dev_family_pack", false, ops, d_op_store_off, max_ops, rows, n_files,
+                               const_cast<uint8_t*>(d_blob), blob_bytes, d_store, store_capacity, d_counts, stream);
+}
+
+int sdcas_dev_family_restore(sdcas_ctx* c, const uint32_t* d_op_row, const uint64_t* d_op_dst_off,
+                             const uint64_t* d_op_len, const uint64_t* d_op_store_off, const uint64_t* d_ops,
+                             size_t max_ops, const uint64_t* d_row_at, const uint64_t* d_row_base,
+                             const uint64_t* d_row_len, size_t n_files, const uint8_t* d_store,
+                             uint64_t store_bytes, uint8_t* d_blob, uint64_t blob_bytes, uint64_t* d_counts,
+                             void* stream) {
+  const FamilyStoreOps ops{nullptr, nullptr, d_op_row, nullptr, d_op_dst_off, nullptr, d_op_len, d_ops,
+                           (uint32_t)max_ops};
+  const FamilyStoreRows rows{d_row_at, d_row_base, d_row_len, (uint32_t)n_files};
+  return family_store_dev_move(c, "dev_family_restore", true, ops, d_op_store_off, max_ops, rows, n_files, d_blob,
+                               blob_bytes, const_cast<uint8_t*>(d_store), store_bytes, d_counts, stream);
+}
+
+int sdcas_family_store_layout(sdcas_ctx* c, const uint32_t* op_chunk, const uint32_t* op_src_chunk,
+                              const uint32_t* op_row, const uint32_t* op_src_row, const uint64_t* op_dst_off,
+                              const uint64_t* op_src_off, const uint64_t* op_len, size_t n_ops,
+                              const uint32_t* chunk_op, size_t m, uint64_t* out_op_store_off,
+                              sdcas_family_store_counts* out_counts) {
+  static_assert(sizeof(sdcas_family_store_counts) == kFamilyStoreLayoutCounts * sizeof(uint64_t), "six u64 counts");
+  const char* who = "family_store_layout";
+  if (!c) return SDCAS_E_INVALID;
+  const uint64_t h_ops = n_ops;
+  const FamilyStoreOps h{op_chunk, op_src_chunk, op_row, op_src_row, op_dst_off, op_src_off, op_len, &h_ops, 0};
+  if (int rc = family_store_layout_args(c, who, h, chunk_op, m, n_ops, out_op_store_off, out_counts)) return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  sdcas_family_store_counts cts;
+  Parts p(c, st, who);
+  const auto d_op_chunk = p.in(op_chunk, n_ops);
+  const auto d_op_src_chunk = p.in(op_src_chunk, n_ops);
+  const auto d_op_row = p.in(op_row, n_ops);
+  const auto d_op_src_row = p.in(op_src_row, n_ops);
+  const auto d_op_dst_off = p.in(op_dst_off, n_ops);
+  const auto d_op_src_off = p.in(op_src_off, n_ops);
+  const auto d_op_len = p.in(op_len, n_ops);
+  const auto d_chunk_op = p.in(chunk_op, m);
+  const auto d_ops = p.in(&h_ops, 1);
+  const auto d_off = p.out(out_op_store_off, n_ops);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = grow_synced(c, c->fs_ws, (size_t)family_store_layout(n_ops).bytes, st, "family store workspace"))
+    return rc;
+  if (int rc = p.upload()) return rc;
+  const FamilyStoreOps ops{d_op_chunk,   d_op_src_chunk, d_op_row, d_op_src_row,   d_op_dst_off,
+                           d_op_src_off, d_op_len,       d_ops,    (uint32_t)n_ops};
+  if (hipError_t e = family_store_offsets(c->fs_ws.p, ops, d_chunk_op, (uint32_t)m, d_off,
+                                          d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  if (int rc = p.download()) return rc;
+  if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+static int family_store_host_move(sdcas_ctx* c, const char* who, bool restore, const uint32_t* op_chunk,
+                                  const uint32_t* op_src_chunk, const uint32_t* op_row, const uint64_t* op_dst_off,
+                                  const uint64_t* op_len, const uint64_t* op_store_off, size_t n_ops,
+                                  const uint64_t* row_at, const uint64_t* row_base, const uint64_t* row_len,
+                                  size_t n_files, uint8_t* blob, uint64_t blob_bytes, uint8_t* store,
+                                  uint64_t store_bytes, sdcas_family_move_counts* out_counts) {
+  static_assert(sizeof(sdcas_family_move_counts) == kFamilyStoreMoveCounts * sizeof(uint64_t), "four u64 counts");
+  if (!c) return SDCAS_E_INVALID;
+  const uint64_t h_ops = n_ops;
+  const FamilyStoreOps h{op_chunk, op_src_chunk, op_row, nullptr, op_dst_off, nullptr, op_len, &h_ops, 0};
+  const FamilyStoreRows hr{row_at, row_base, row_len, 0};
+  if (int rc = family_store_move_args(c, who, restore, h, op_store_off, n_ops, hr, n_files, blob, blob_bytes, store,
+                                      store_bytes, out_counts, false))
+    return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  sdcas_family_move_counts cts;
+  Parts p(c, st, who);
+  const auto d_op_chunk = p.in(op_chunk, n_ops);
+  const auto d_op_src_chunk = p.in(op_src_chunk, n_ops);
+  const auto d_op_row = p.in(op_row, n_ops);
+  const auto d_op_dst_off = p.in(op_dst_off, n_ops);
+  const auto d_op_len = p.in(op_len, n_ops);
+  const auto d_off = p.in(op_store_off, n_ops);
+  const auto d_ops = p.in(&h_ops, 1);
+  const auto d_row_at = p.in(row_at, n_files);
+  const auto d_row_base = p.in(row_base, n_files);
+  const auto d_row_len = p.in(row_len, n_files);
+  // the source goes up, the destination goes up and comes down: what the call does not write stays
+  const auto d_blob_in = p.in(restore ? nullptr : (const uint8_t*)blob, (size_t)blob_bytes);
+  const auto d_store_in = p.in(restore ? (const uint8_t*)store : nullptr, (size_t)store_bytes);
+  const auto d_blob_io = p.inout(restore ? blob : nullptr, (size_t)blob_bytes);
+  const auto d_store_io = p.inout(restore ? nullptr : store, (size_t)store_bytes);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = grow_synced(c, c->fs_ws, (size_t)family_store_layout(n_ops).bytes, st, "family store workspace"))
+    return rc;
+  if (int rc = p.upload()) return rc;
+  const FamilyStoreOps ops{d_op_chunk, d_op_src_chunk, d_op_row, nullptr,        d_op_dst_off,
+                           nullptr,    d_op_len,       d_ops,    (uint32_t)n_ops};
+  const FamilyStoreRows rows{d_row_at, d_row_base, d_row_len, (uint32_t)n_files};
+  uint8_t* d_blob = restore ? (uint8_t*)d_blob_io : const_cast<uint8_t*>((const uint8_t*)d_blob_in);
+  uint8_t* d_store = restore ? const_cast<uint8_t*>((const uint8_t*)d_store_in) : (uint8_t*)d_store_io;
+  if (hipError_t e = family_store_move(c->fs_ws.p, ops, d_off, rows, d_blob, blob_bytes, d_store, store_bytes, restore,
+                                       d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  if (int rc = p.download()) return rc;
+  if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+int sdcas_family_pack(sdcas_ctx* c, const uint32_t* op_chunk, const uint32_t* op_src_chunk, const uint32_t* op_row,
+                      const uint64_t* op_dst_off, const uint64_t* op_len, const uint64_t* op_store_off, size_t ops,
+                      const uint64_t* row_at, const uint64_t* row_base, const uint64_t* row_len, size_t n_files,
+                      const uint8_t* blob, uint64_t blob_bytes, uint8_t* store, uint64_t store_capacity,
+                      sdcas_family_move_counts* out_counts) {
+  return family_store_host_move(c, "family_pack", false, op_chunk, op_src_chunk, op_row, op_dst_off, op_len,
+                                op_store_off, ops, row_at, row_base, row_len, n_files, const_cast<uint8_t*>(blob),
+                                blob_bytes, store, store_capacity, out_counts);
+}
+
+int sdcas_family_restore(sdcas_ctx* c, const uint32_t* op_row, const uint64_t* op_dst_off, const uint64_t* op_len,
+                         const uint64_t* op_store_off, size_t ops, const uint64_t* row_at, const uint64_t* row_base,
+                         const uint64_t* row_len, size_t n_files, const uint8_t* store, uint64_t store_bytes,
+                         uint8_t* blob, uint64_t blob_bytes, sdcas_family_move_counts* out_counts) {
+  return family_store_host_move(c, "family_restore", true, nullptr, nullptr, op_row, op_dst_off, op_len, op_store_off,
+                                ops, row_at, row_base, row_len, n_files, blob, blob_bytes,
+                                const_cast<uint8_t*>(store), store_bytes, out_counts);
 }
 
 int sdcas_dev_set_sort(sdcas_ctx* c, int enable) {

@@ -1323,6 +1323,115 @@ class Engine:
         out["sizes"] = r["sizes"]
         return out
 
+    # -- family store: the literal bytes packed into one store, files restored from it
+    @staticmethod
+    def family_store_tile_bytes():
+        """sdcas_family_store_tile_bytes (no GPU): the mover's tile in destination bytes"""
+        return int(N.load().sdcas_family_store_tile_bytes())
+
+    @staticmethod
+    def family_store_plan(max_ops, n_files):
+        """sdcas_family_store_plan (no GPU) -> workspace_bytes: what the layout,
+        pack and restore device calls share for max_ops ops; SdcasError beyond
+        the ranges"""
+        ws = ctypes.c_uint64(0)
+        rc = N.load().sdcas_family_store_plan(int(max_ops), int(n_files), ctypes.byref(ws))
+        if rc != N.SDCAS_OK:
+            raise N.SdcasError(rc, f"family_store_plan({max_ops}, {n_files})")
+        return int(ws.value)
+
+    @staticmethod
+    def _store_ops(recipes, who):
+        u32 = [_arr(recipes[k], np.uint32) for k in ("op_chunk", "op_src_chunk", "op_row", "op_src_row")]
+        u64 = [_arr(recipes[k], np.uint64) for k in ("op_dst_off", "op_src_off", "op_len")]
+        k = u32[0].size
+        if not all(a.size == k for a in u32 + u64):
+            raise ValueError(f"{who}: the op arrays differ in length")
+        return u32 + u64, k
+
+    def family_store_layout(self, recipes):
+        """sdcas_family_store_layout over family_recipes' dict -> {"op_store_off":
+        uint64[ops], 2^64 - 1 for an uncovered copy op; "counts":
+        sdcas_family_store_counts' six fields}"""
+        ops, k = self._store_ops(recipes, "family_store_layout")
+        chunk_op = _arr(recipes["chunk_op"], np.uint32)
+        off = np.zeros(k, np.uint64)
+        counts = N.FamilyStoreCounts()
+        self._check(self.L.sdcas_family_store_layout(self.ctx, *(_ptr(a) for a in ops), k, _ptr(chunk_op),
+                                                     chunk_op.size, _ptr(off), ctypes.byref(counts)),
+                    "sdcas_family_store_layout")
+        return {"op_store_off": off, "counts": counts.as_dict()}
+
+    @staticmethod
+    def _store_rows(row_at, row_len, row_base, who):
+        at, ln = _arr(row_at, np.uint64), _arr(row_len, np.uint64)
+        base = None if row_base is None else _arr(row_base, np.uint64)
+        if ln.size != at.size or (base is not None and base.size != at.size):
+            raise ValueError(f"{who}: row_at, row_len and row_base differ in length")
+        return at, base, ln
+
+    def family_pack(self, recipes, layout, blob, row_at, row_len, row_base=None, store=None, counts=None):
+        """sdcas_family_pack over host arrays: the literal ops' bytes from the
+        rows' windows in `blob` (row i's bytes [row_base[i], row_base[i] +
+        row_len[i]) at blob[row_at[i]:]; row_len 0: the row is not there) into
+        the store. `store`: an earlier call's store to pack further windows
+        into (None: store_bytes zeros). -> the store, uint8. `counts`, a dict,
+        receives sdcas_family_move_counts' four fields."""
+        ops, k = self._store_ops(recipes, "family_pack")
+        off = _arr(layout["op_store_off"], np.uint64)
+        if off.size != k:
+            raise ValueError(f"family_pack: {k} ops, {off.size} store offsets")
+        at, base, ln = self._store_rows(row_at, row_len, row_base, "family_pack")
+        blob = _arr(blob, np.uint8)
+        store = np.zeros(int(layout["counts"]["store_bytes"]), np.uint8) if store is None else \
+            np.array(store, np.uint8, copy=True).reshape(-1)
+        c = N.FamilyMoveCounts()
+        self._check(self.L.sdcas_family_pack(self.ctx, _ptr(ops[0]), _ptr(ops[1]), _ptr(ops[2]), _ptr(ops[4]),
+                                             _ptr(ops[6]), _ptr(off), k, _ptr(at), _ptr(base), _ptr(ln), at.size,
+                                             _ptr(blob), blob.size, _ptr(store), store.size, ctypes.byref(c)),
+                    "sdcas_family_pack")
+        if counts is not None:
+            counts.update(c.as_dict())
+        return store
+
+    def family_restore(self, recipes, layout, store, row_at, row_len, row_base=None, blob_bytes=None, blob=None,
+                       counts=None):
+        """sdcas_family_restore over host arrays: every op with a store offset
+        written into its row's window. The blob is `blob` (copied; the bytes no
+        op covers stay) or blob_bytes zeros (None: up to the last window's
+        end). -> the blob, uint8."""
+        ops, k = self._store_ops(recipes, "family_restore")
+        off = _arr(layout["op_store_off"], np.uint64)
+        if off.size != k:
+            raise ValueError(f"family_restore: {k} ops, {off.size} store offsets")
+        at, base, ln = self._store_rows(row_at, row_len, row_base, "family_restore")
+        store = _arr(store, np.uint8).reshape(-1)
+        if blob is not None:
+            blob = np.array(blob, np.uint8, copy=True).reshape(-1)
+        else:
+            if blob_bytes is None:
+                blob_bytes = int((at[ln != 0] + ln[ln != 0]).max()) if (ln != 0).any() else 0
+            blob = np.zeros(int(blob_bytes), np.uint8)
+        c = N.FamilyMoveCounts()
+        self._check(self.L.sdcas_family_restore(self.ctx, _ptr(ops[2]), _ptr(ops[4]), _ptr(ops[6]), _ptr(off), k,
+                                                _ptr(at), _ptr(base), _ptr(ln), at.size, _ptr(store), store.size,
+                                                _ptr(blob), blob.size, ctypes.byref(c)), "sdcas_family_restore")
+        if counts is not None:
+            counts.update(c.as_dict())
+        return blob
+
+    def store_files(self, paths, k=4, max_holders=64, num=1, den=2, params=None, window_bytes=256 << 20):
+        """The family store of these files -> FamilyStore (spacedrive_amd/store.py):
+        similar_recipes, the layout, the store allocated on the device
+        (SdcasError SDCAS_E_CAPACITY when store_bytes does not fit there), the
+        files read again window by window (plan_windows) and packed, the store
+        brought down, and the files' checksums (file_checksums) to verify
+        against. The files are read three times in all; rows are the paths in
+        order."""
+        from .store import FamilyStore
+        return FamilyStore.of_files(self, paths, k=k, max_holders=max_holders, num=num, den=den, params=params,
+                                    window_bytes=window_bytes)
+
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
     def dev_chunk_index_match(self, idx_keys, idx_digests, idx_values, idx_dir, n, bits, keys, digests, valid, m,
                               pos=0, value=0, counts=0, stream=0):
@@ -1453,6 +1562,40 @@ class Engine:
                                                     op_len or None, chunk_op or None, row_ops or None,
                                                     row_first_op or None, counts or None, stream or None),
                     "dev_family_recipes")
+
+    def dev_family_store_layout(self, op_chunk, op_src_chunk, op_row, op_src_row, op_dst_off, op_src_off, op_len,
+                                chunk_op, m, ops, max_ops, op_store_off=0, counts=0, stream=0):
+        """family_store_layout over dev_family_recipes' outputs as they are
+        (sdcas_dev_family_store_layout): ops is a device uint64, the recipes'
+        counts + 2 words; op_store_off uint64[max_ops], counts six uint64.
+        Nothing waits for the device once the workspace for max_ops exists"""
+        self._check(self.L.sdcas_dev_family_store_layout(self.ctx, op_chunk or None, op_src_chunk or None,
+                                                         op_row or None, op_src_row or None, op_dst_off or None,
+                                                         op_src_off or None, op_len or None, chunk_op or None, int(m),
+                                                         ops or None, int(max_ops), op_store_off or None,
+                                                         counts or None, stream or None), "dev_family_store_layout")
+
+    def dev_family_pack(self, op_chunk, op_src_chunk, op_row, op_dst_off, op_len, op_store_off, ops, max_ops, row_at,
+                        row_base, row_len, n_files, blob, blob_bytes, store, store_capacity, counts=0, stream=0):
+        """family_pack over device arrays (sdcas_dev_family_pack): blob and store
+        16-byte aligned and readable to the next multiple of 16; row_base may
+        be 0; counts four uint64"""
+        self._check(self.L.sdcas_dev_family_pack(self.ctx, op_chunk or None, op_src_chunk or None, op_row or None,
+                                                 op_dst_off or None, op_len or None, op_store_off or None,
+                                                 ops or None, int(max_ops), row_at or None, row_base or None,
+                                                 row_len or None, int(n_files), blob or None, int(blob_bytes),
+                                                 store or None, int(store_capacity), counts or None, stream or None),
+                    "dev_family_pack")
+
+    def dev_family_restore(self, op_row, op_dst_off, op_len, op_store_off, ops, max_ops, row_at, row_base, row_len,
+                           n_files, store, store_bytes, blob, blob_bytes, counts=0, stream=0):
+        """family_restore over device arrays (sdcas_dev_family_restore), under
+        dev_family_pack's contract"""
+        self._check(self.L.sdcas_dev_family_restore(self.ctx, op_row or None, op_dst_off or None, op_len or None,
+                                                    op_store_off or None, ops or None, int(max_ops), row_at or None,
+                                                    row_base or None, row_len or None, int(n_files), store or None,
+                                                    int(store_bytes), blob or None, int(blob_bytes), counts or None,
+                                                    stream or None), "dev_family_restore")
 
     def dev_chunk_windows(self, blob, offs, lens, final, n, max_chunks, max_slots, params=None, file_chunks=0,
                           chunk_off=0, chunk_len=0, chunk_file=0, keys=0, digests=0, consumed=0, counts=0, stream=0):
