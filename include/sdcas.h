@@ -1561,6 +1561,160 @@ int sdcas_family_restore(sdcas_ctx *ctx, const uint32_t *op_row, const uint64_t 
                          uint64_t store_bytes, uint8_t *blob, uint64_t blob_bytes,
                          sdcas_family_move_counts *out_counts);
 
+/* ---- family store: forget rows ------------------------------------------------------
+ *
+ * Added after ABI 7; probe for the symbol (SDCAS_ABI_VERSION stays 7).
+ *
+ * A packed store is frozen: once a stored file is deleted, the only way to a
+ * store without it was to read every original again. These two calls take rows
+ * out of a store with no file read. Recipes are defined per chunk, so removal is
+ * done on the chunk arrays: KEEP drops the chunks of the removed rows and
+ * elects classes and labels again among the survivors; sdcas_dev_family_recipes
+ * and sdcas_dev_family_store_layout run over what it leaves, unchanged; MOVES
+ * says where every literal byte of the new store lies in the old one, and the
+ * mover above (sdcas_dev_family_restore, one row, one window over the new store,
+ * the moves as its ops) carries the bytes. The result equals the store built
+ * from the surviving files alone. All arithmetic is modulo 2^64.
+ *
+ * KEEP. Inputs: chunk_file[m] u32, chunk_off[m] u64, chunk_len[m] u64, rep[m]
+ * int64; family[n_files] int64; keep[n_files] u8, nonzero means the row stays.
+ *   rows     row i is kept when keep[i] != 0. out_row_new[i] (u32, n_files
+ *            entries) is the number of kept rows below i, or 0xFFFFFFFF for a
+ *            removed row. out_row_from[j] (u32, n' entries, ascending) is the
+ *            inverse.
+ *   labels   a kept row takes part when 0 <= family[i] < n_files, which is
+ *            sdcas_family_bytes' rule. out_family[j] (int64) is the new number
+ *            of the lowest kept row that takes part with the same label value;
+ *            -1 for a kept row that takes no part.
+ *   chunks   chunk c survives when chunk_file[c] < n_files and that row is kept.
+ *            Its new position is the number of surviving chunks below it.
+ *            out_chunk_from[c'] (u32) is the old position; out_chunk_file[c'] =
+ *            row_new[chunk_file[c]]; out_chunk_off and out_chunk_len are copied.
+ *   classes  r(c) = rep[c] when 0 <= rep[c] <= c, else c: sdcas_family_bytes'
+ *            class number. out_rep[c'] (int64) is the new position of the lowest
+ *            surviving chunk with the same r.
+ *   counts   on the device as the others are: rows_kept (n'), rows_removed,
+ *            chunks_kept (m'), chunks_removed, bytes_kept, bytes_removed (the sums
+ *            of chunk_len over the surviving and the other chunks).
+ * The caller provides n_files entries for each row array and m for each chunk
+ * array; entries of the outputs past n' or m' are left as they were. Any output
+ * may be NULL.
+ * Laws: (1) out_rep[out_rep[c']] == out_rep[c'] <= c'. (2) Two surviving chunks
+ * have equal out_rep if and only if they have equal r. (3) Two kept
+ * participating rows have equal out_family if and only if they had equal
+ * labels. (4) keep(A) followed by keep(B) over its outputs equals one keep of
+ * the rows that both keep. (5) For a rep that was sdcas_confirm_duplicates' over
+ * all chunks, out_rep is what confirm gives over the surviving chunks alone.
+ *
+ * MOVES. Old side: chunk_off[m], chunk_op[m], op_dst_off[k], op_store_off[k] and
+ * the number of ops (d_ops, max_ops as in the layout). New side: chunk_from[m'],
+ * chunk_off'[m'], chunk_len'[m'], chunk_op'[m'] and the new ops' op_chunk',
+ * op_src_chunk', op_dst_off', op_store_off' with d_ops', max_ops'. d_chunks':
+ * m' as a device u64, which is keep's d_counts + 2; the call uses min(m',
+ * max_chunks). For a new chunk c':
+ *   old_at   let c = chunk_from[c'] and o = chunk_op[c]. old_at(c') =
+ *            op_store_off[o] + (chunk_off[c] - op_dst_off[o]). This holds for a
+ *            literal and for a covered copy alike, since a copy op's store
+ *            offset is its source's place. old_at(c') is NONE when c >= m; o is
+ *            0xFFFFFFFF or o >= ops; op_store_off[o] is SDCAS_STORE_NONE; or
+ *            chunk_off[c] < op_dst_off[o] (so is a place that comes out as
+ *            2^64 - 1).
+ *   literal  let o' = chunk_op'[c']. c' is a literal chunk when o' < ops' and
+ *            op_chunk'[o'] == op_src_chunk'[o']. Then new_at(c') =
+ *            op_store_off'[o'] + (chunk_off'[c'] - op_dst_off'[o']).
+ *   heads    a literal chunk with an old_at CONTINUES c' - 1 when both are
+ *            literal chunks of one new op, c' - 1 has an old_at, and old_at(c')
+ *            == old_at(c' - 1) + chunk_len'[c' - 1]. Only c' - 1 is looked at.
+ *            Any other such chunk is a HEAD.
+ *   moves    numbered in the order of their heads: out_move_dst[j] =
+ *            new_at(head), out_move_src[j] = old_at(head), out_move_len[j] the
+ *            sum of its chunks' lengths (u64 each). The caller gives m' entries
+ *            (max_chunks on the device); those past `moves` are left as they were.
+ *   lost     a literal chunk whose old_at is NONE gets no move and is counted.
+ * Example, the recipes' v1 = A B C and v2 = A B X C with v1 removed: the old
+ * store is A B C X with offsets [0, 0, 60, 30]; the new recipes are one literal
+ * op of 65 bytes; old_at of A, B, X, C is 0, 10, 60, 30. Three moves (dst, src,
+ * len): (0, 0, 30), (30, 60, 5), (35, 30, 30). Counts: moves 3, literal_chunks
+ * 4, moved_bytes 65, lost 0, longest_move 30.
+ * Laws: for stores of recipes under the recipes' law 2 (running-sum offsets)
+ * nothing is lost: a literal chunk of the new recipes took part before, so its
+ * old op has a place, and a copy's place is its source's. The moves'
+ * destinations are disjoint and cover [0, store_bytes'). store_bytes' <=
+ * store_bytes, so a new store never needs more room than the old one.
+ * The bytes: sdcas_dev_family_restore with op_row all 0, op_dst_off =
+ * move_dst, op_len = move_len, op_store_off = move_src, d_ops = moves' d_counts,
+ * n_files = 1, row_at [0], row_len [store_bytes'], the old store as d_store and
+ * the new one as d_blob, out of place. The mover's memory contract and its
+ * bad-op rule hold for moves as they are.
+ * Errors, all before anything is enqueued: SDCAS_E_INVALID for a needed NULL
+ * (keep: chunk_file, chunk_off, chunk_len, rep with m != 0; family, keep with
+ * n_files != 0. moves: chunk_off, chunk_op with m != 0; op_dst_off,
+ * op_store_off, d_ops with max_ops != 0; the new chunk arrays and d_chunks' with
+ * max_chunks != 0; the new op arrays and d_ops' with max_ops' != 0) or a
+ * misalignment (8 bytes for u64 and int64, 4 for u32); SDCAS_E_CAPACITY for m,
+ * n_files, max_ops, max_ops' or max_chunks above 2^30. m == 0 and n_files == 0
+ * are SDCAS_OK. Results are exact and do not depend on scheduling; two calls on
+ * one input give the same bytes. */
+typedef struct sdcas_family_keep_counts {
+  uint64_t rows_kept;
+  uint64_t rows_removed;
+  uint64_t chunks_kept;
+  uint64_t chunks_removed;
+  uint64_t bytes_kept;
+  uint64_t bytes_removed;
+} sdcas_family_keep_counts;
+typedef struct sdcas_family_moves_counts {
+  uint64_t moves;
+  uint64_t literal_chunks; /* literal chunks of the new recipes, the lost among them */
+  uint64_t moved_bytes;    /* the sum of the moves' len */
+  uint64_t lost_chunks;
+  uint64_t lost_bytes;
+  uint64_t longest_move;   /* the largest move_len, 0 when there is no move */
+} sdcas_family_moves_counts;
+/* GPU-free: the range checks (m, n_files) and *out_workspace_bytes = what the two
+ * device calls share for m chunks of n_files rows (17 bytes per chunk, 8 per
+ * row, 8 KiB of counters and a little). The output may be NULL. */
+int sdcas_family_forget_plan(uint64_t m, uint64_t n_files, uint64_t *out_workspace_bytes);
+/* Host arrays: one upload, the device call, the counts down, then exactly n'
+ * entries of row_from and family, m' of the chunk arrays and n_files of row_new. */
+int sdcas_family_chunks_keep(sdcas_ctx *ctx, const uint32_t *chunk_file, const uint64_t *chunk_off,
+                             const uint64_t *chunk_len, const int64_t *rep, size_t m, const int64_t *family,
+                             const uint8_t *keep, size_t n_files, uint32_t *out_row_new, uint32_t *out_row_from,
+                             int64_t *out_family, uint32_t *out_chunk_from, uint32_t *out_chunk_file,
+                             uint64_t *out_chunk_off, uint64_t *out_chunk_len, int64_t *out_rep,
+                             sdcas_family_keep_counts *out_counts);
+/* Device arrays under sdcas_dev_chunk_peers' stream rules. d_counts: six u64 in
+ * sdcas_family_keep_counts' order, overwritten. The workspace is allocated by
+ * the first of the two calls that needs it, which waits for the stream; after
+ * that no call waits for the device. Every grid is sized from m or n_files. */
+int sdcas_dev_family_chunks_keep(sdcas_ctx *ctx, const uint32_t *d_chunk_file, const uint64_t *d_chunk_off,
+                                 const uint64_t *d_chunk_len, const int64_t *d_rep, size_t m,
+                                 const int64_t *d_family, const uint8_t *d_keep, size_t n_files,
+                                 uint32_t *d_row_new, uint32_t *d_row_from, int64_t *d_family_out,
+                                 uint32_t *d_chunk_from, uint32_t *d_chunk_file_out, uint64_t *d_chunk_off_out,
+                                 uint64_t *d_chunk_len_out, int64_t *d_rep_out, uint64_t *d_counts, void *stream);
+/* Host arrays: one upload, the device call, the counts down, then exactly
+ * `moves` entries of each move array. */
+int sdcas_family_store_moves(sdcas_ctx *ctx, const uint64_t *chunk_off, const uint32_t *chunk_op, size_t m,
+                             const uint64_t *op_dst_off, const uint64_t *op_store_off, size_t ops,
+                             const uint32_t *new_chunk_from, const uint64_t *new_chunk_off,
+                             const uint64_t *new_chunk_len, const uint32_t *new_chunk_op, size_t new_chunks,
+                             const uint32_t *new_op_chunk, const uint32_t *new_op_src_chunk,
+                             const uint64_t *new_op_dst_off, const uint64_t *new_op_store_off, size_t new_ops,
+                             uint64_t *out_move_dst, uint64_t *out_move_src, uint64_t *out_move_len,
+                             sdcas_family_moves_counts *out_counts);
+/* d_counts: six u64 in sdcas_family_moves_counts' order, overwritten. Every grid
+ * is sized from max_chunks; the number of moves stays on the device. */
+int sdcas_dev_family_store_moves(sdcas_ctx *ctx, const uint64_t *d_chunk_off, const uint32_t *d_chunk_op, size_t m,
+                                 const uint64_t *d_op_dst_off, const uint64_t *d_op_store_off,
+                                 const uint64_t *d_ops, size_t max_ops, const uint32_t *d_new_chunk_from,
+                                 const uint64_t *d_new_chunk_off, const uint64_t *d_new_chunk_len,
+                                 const uint32_t *d_new_chunk_op, const uint64_t *d_new_chunks, size_t max_chunks,
+                                 const uint32_t *d_new_op_chunk, const uint32_t *d_new_op_src_chunk,
+                                 const uint64_t *d_new_op_dst_off, const uint64_t *d_new_op_store_off,
+                                 const uint64_t *d_new_ops, size_t max_new_ops, uint64_t *d_move_dst,
+                                 uint64_t *d_move_src, uint64_t *d_move_len, uint64_t *d_counts, void *stream);
+
 /* ---- multi-GPU dedup stages (one process per GPU) -------
  *
  * sdcas_dedup's group-by split at its one exchange step, for a node whose

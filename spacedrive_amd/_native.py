@@ -79,6 +79,8 @@ ABI_SYMBOLS = [
     "sdcas_family_store_tile_bytes", "sdcas_family_store_plan", "sdcas_family_store_layout", "sdcas_family_pack",
     "sdcas_family_restore", "sdcas_dev_family_store_layout", "sdcas_dev_family_pack",
     "sdcas_dev_family_restore",  # added after ABI 7
+    "sdcas_family_forget_plan", "sdcas_family_chunks_keep", "sdcas_dev_family_chunks_keep",
+    "sdcas_family_store_moves", "sdcas_dev_family_store_moves",  # added after ABI 7
     "sdcas_key_to_hex",
     "sdcas_digest_to_hex", "sdcas_cas_message_len", "sdcas_dev_dedup_combine", "sdcas_dev_dedup_combine_async",
     "sdcas_dev_dedup_resolve",
@@ -284,6 +286,25 @@ class FamilyMoveCounts(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class FamilyKeepCounts(ctypes.Structure):
+    """sdcas_family_keep_counts"""
+    _fields_ = [("rows_kept", ctypes.c_uint64), ("rows_removed", ctypes.c_uint64), ("chunks_kept", ctypes.c_uint64),
+                ("chunks_removed", ctypes.c_uint64), ("bytes_kept", ctypes.c_uint64),
+                ("bytes_removed", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class FamilyMovesCounts(ctypes.Structure):
+    """sdcas_family_moves_counts"""
+    _fields_ = [("moves", ctypes.c_uint64), ("literal_chunks", ctypes.c_uint64), ("moved_bytes", ctypes.c_uint64),
+                ("lost_chunks", ctypes.c_uint64), ("lost_bytes", ctypes.c_uint64), ("longest_move", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _lib_path = LIB_PATH
 
@@ -411,6 +432,14 @@ def load():
                                                 ctypes.POINTER(FamilyMoveCounts)]
     L.sdcas_family_restore.argtypes = [_vp] * 5 + [_sz, _vp, _vp, _vp, _sz, _vp, _u64, _vp, _u64,
                                                    ctypes.POINTER(FamilyMoveCounts)]
+    L.sdcas_family_forget_plan.argtypes = [_u64, _u64, _vp]
+    L.sdcas_family_chunks_keep.argtypes = [_vp] * 5 + [_sz, _vp, _vp, _sz] + [_vp] * 8 + [
+        ctypes.POINTER(FamilyKeepCounts)]
+    L.sdcas_dev_family_chunks_keep.argtypes = [_vp] * 5 + [_sz, _vp, _vp, _sz] + [_vp] * 10
+    L.sdcas_family_store_moves.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp,
+                                           _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(FamilyMovesCounts)]
+    L.sdcas_dev_family_store_moves.argtypes = [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz,
+                                               _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
     L.sdcas_key_to_hex.argtypes = [_u64, ctypes.c_char_p]
     L.sdcas_digest_to_hex.argtypes = [_vp, ctypes.c_char_p]
     L.sdcas_cas_message_len.argtypes = [_u64]

@@ -39,6 +39,7 @@
 #include "families.h"
 #include "family_bytes.h"
 #include "family_recipes.h"
+#include "family_forget.h"
 #include "family_store.h"
 #include "chunk_index.h"
 #include "dist_dedup.h"
@@ -246,6 +247,8 @@ struct sdcas_ctx {
   DevBuf<uint8_t> fr_ws;
   // the family store (family_store.hip): the op sums, tile starts and clipped ranges
   DevBuf<uint8_t> fs_ws;
+  // a family store that forgets rows (family_forget.hip): the tables, new numbers and move heads
+  DevBuf<uint8_t> fg_ws;
 
   // multi-GPU dedup stages
   DistWs dist;
@@ -3797,6 +3800,220 @@ int sdcas_family_restore(sdcas_ctx* c, const uint32_t* op_row, const uint64_t* o
   return family_store_host_move(c, "family_restore", true, nullptr, nullptr, op_row, op_dst_off, op_len, op_store_off,
                                 ops, row_at, row_base, row_len, n_files, blob, blob_bytes,
                                 const_cast<uint8_t*>(store), store_bytes, out_counts);
+}
+
+// ---- a family store that forgets rows (family_forget.hip) -------------------------------
+
+static int family_forget_range(uint64_t m, uint64_t n_files, uint64_t max_ops, uint64_t max_new_ops,
+                               const char** why) {
+  if (m > kFamilyForgetMax) return *why = "more than 2^30 chunks", SDCAS_E_CAPACITY;
+  if (n_files > kFamilyForgetMax) return *why = "more than 2^30 files", SDCAS_E_CAPACITY;
+  if (max_ops > kFamilyForgetMax || max_new_ops > kFamilyForgetMax) return *why = "more than 2^30 ops", SDCAS_E_CAPACITY;
+  return SDCAS_OK;
+}
+
+int sdcas_family_forget_plan(uint64_t m, uint64_t n_files, uint64_t* out_workspace_bytes) {
+  const char* why = nullptr;
+  if (int rc = family_forget_range(m, n_files, 0, 0, &why)) return rc;
+  if (out_workspace_bytes) *out_workspace_bytes = family_forget_bytes(m, n_files);
+  return SDCAS_OK;
+}
+
+// keep's arguments (host or device arrays)
+static int family_keep_args(sdcas_ctx* c, const char* who, const FamilyKeepIn& in, size_t m, size_t n_files,
+                            const FamilyKeepOut& out, const void* counts) {
+  const char* why = nullptr;
+  if (int rc = family_forget_range(m, n_files, 0, 0, &why)) return c->fail(rc, "%s: %s", who, why);
+  if (m && (!in.chunk_file || !in.chunk_off || !in.chunk_len || !in.rep))
+    return c->fail(SDCAS_E_INVALID, "%s: null chunk_file, chunk_off, chunk_len or rep", who);
+  if (n_files && (!in.family || !in.keep)) return c->fail(SDCAS_E_INVALID, "%s: null family or keep", who);
+  if (index_misaligned({}, {in.chunk_off, in.chunk_len, in.rep, in.family, out.family, out.chunk_off, out.chunk_len,
+                            out.rep, counts},
+                       {in.chunk_file, out.row_new, out.row_from, out.chunk_from, out.chunk_file}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (u32 arrays 4 B, u64 and int64 8 B)", who);
+  return SDCAS_OK;
+}
+
+int sdcas_dev_family_chunks_keep(sdcas_ctx* c, const uint32_t* d_chunk_file, const uint64_t* d_chunk_off,
+                                 const uint64_t* d_chunk_len, const int64_t* d_rep, size_t m, const int64_t* d_family,
+                                 const uint8_t* d_keep, size_t n_files, uint32_t* d_row_new, uint32_t* d_row_from,
+                                 int64_t* d_family_out, uint32_t* d_chunk_from, uint32_t* d_chunk_file_out,
+                                 uint64_t* d_chunk_off_out, uint64_t* d_chunk_len_out, int64_t* d_rep_out,
+                                 uint64_t* d_counts, void* stream) {
+  const char* who = "dev_family_chunks_keep";
+  if (!c) return SDCAS_E_INVALID;
+  const FamilyKeepIn in{d_chunk_file, d_chunk_off, d_chunk_len, d_rep, d_family, d_keep, (uint32_t)m, (uint32_t)n_files};
+  const FamilyKeepOut out{d_row_new,        d_row_from,      d_family_out,    d_chunk_from,
+                          d_chunk_file_out, d_chunk_off_out, d_chunk_len_out, d_rep_out};
+  if (int rc = family_keep_args(c, who, in, m, n_files, out, d_counts)) return rc;
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = grow_synced(c, c->fg_ws, (size_t)family_keep_layout(m, n_files).bytes, call.st, "family forget workspace"))
+    return rc;
+  hipError_t e = family_chunks_keep(c->fg_ws.p, in, out, (unsigned long long*)d_counts, call.st);
+  return e ? hip_fail_at(c, e, who, "") : SDCAS_OK;
+}
+
+int sdcas_family_chunks_keep(sdcas_ctx* c, const uint32_t* chunk_file, const uint64_t* chunk_off,
+                             const uint64_t* chunk_len, const int64_t* rep, size_t m, const int64_t* family,
+                             const uint8_t* keep, size_t n_files, uint32_t* out_row_new, uint32_t* out_row_from,
+                             int64_t* out_family, uint32_t* out_chunk_from, uint32_t* out_chunk_file,
+                             uint64_t* out_chunk_off, uint64_t* out_chunk_len, int64_t* out_rep,
+                             sdcas_family_keep_counts* out_counts) {
+  static_assert(sizeof(sdcas_family_keep_counts) == kFamilyKeepCounts * sizeof(uint64_t), "six u64 counts");
+  const char* who = "family_chunks_keep";
+  if (!c) return SDCAS_E_INVALID;
+  const FamilyKeepIn h{chunk_file, chunk_off, chunk_len, rep, family, keep, 0, 0};
+  const FamilyKeepOut ho{out_row_new,    out_row_from,  out_family,    out_chunk_from,
+                         out_chunk_file, out_chunk_off, out_chunk_len, out_rep};
+  if (int rc = family_keep_args(c, who, h, m, n_files, ho, out_counts)) return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  const size_t nf = n_files;
+  sdcas_family_keep_counts cts;
+  Parts p(c, st, who);
+  const auto d_file = p.in(chunk_file, m);
+  const auto d_off = p.in(chunk_off, m);
+  const auto d_len = p.in(chunk_len, m);
+  const auto d_rep = p.in(rep, m);
+  const auto d_family = p.in(family, nf);
+  const auto d_keep = p.in(keep, nf);
+  const auto d_row_new = p.out(out_row_new, nf);
+  const auto d_row_from = p.out(out_row_from, nf);
+  const auto d_fam_out = p.out(out_family, nf);
+  const auto d_chunk_from = p.out(out_chunk_from, m);
+  const auto d_file_out = p.out(out_chunk_file, m);
+  const auto d_off_out = p.out(out_chunk_off, m);
+  const auto d_len_out = p.out(out_chunk_len, m);
+  const auto d_rep_out = p.out(out_rep, m);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = grow_synced(c, c->fg_ws, (size_t)family_keep_layout(m, n_files).bytes, st, "family forget workspace"))
+    return rc;
+  if (int rc = p.upload()) return rc;
+  const FamilyKeepIn in{d_file, d_off, d_len, d_rep, d_family, d_keep, (uint32_t)m, (uint32_t)n_files};
+  const FamilyKeepOut out{d_row_new, d_row_from, d_fam_out, d_chunk_from, d_file_out, d_off_out, d_len_out, d_rep_out};
+  if (hipError_t e = family_chunks_keep(c->fg_ws.p, in, out, d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  if (int rc = p.counts(d_cts)) return rc;
+  if (cts.rows_kept > nf || cts.chunks_kept > m) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
+  d_row_from.first(cts.rows_kept), d_fam_out.first(cts.rows_kept);
+  d_chunk_from.first(cts.chunks_kept), d_file_out.first(cts.chunks_kept), d_off_out.first(cts.chunks_kept);
+  d_len_out.first(cts.chunks_kept), d_rep_out.first(cts.chunks_kept);
+  if (int rc = p.download()) return rc;
+  if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
+}
+
+// moves' arguments (host or device arrays)
+static int family_moves_args(sdcas_ctx* c, const char* who, const FamilyMovesIn& in, size_t m, size_t max_ops,
+                             size_t max_chunks, size_t max_new_ops, const void* move_dst, const void* move_src,
+                             const void* move_len, const void* counts) {
+  const char* why = nullptr;
+  if (int rc = family_forget_range(m > max_chunks ? m : max_chunks, 0, max_ops, max_new_ops, &why))
+    return c->fail(rc, "%s: %s", who, why);
+  if (m && (!in.chunk_off || !in.chunk_op)) return c->fail(SDCAS_E_INVALID, "%s: null chunk_off or chunk_op", who);
+  if (max_ops && (!in.op_dst_off || !in.op_store_off || !in.d_ops))
+    return c->fail(SDCAS_E_INVALID, "%s: null op_dst_off, op_store_off or ops", who);
+  if (max_chunks && (!in.nchunk_from || !in.nchunk_off || !in.nchunk_len || !in.nchunk_op || !in.d_chunks))
+    return c->fail(SDCAS_E_INVALID, "%s: a null new chunk array or null new chunks", who);
+  if (max_new_ops && (!in.nop_chunk || !in.nop_src_chunk || !in.nop_dst_off || !in.nop_store_off || !in.d_nops))
+    return c->fail(SDCAS_E_INVALID, "%s: a null new op array or null new ops", who);
+  if (index_misaligned({}, {in.chunk_off, in.op_dst_off, in.op_store_off, in.d_ops, in.nchunk_off, in.nchunk_len,
+                            in.d_chunks, in.nop_dst_off, in.nop_store_off, in.d_nops, move_dst, move_src, move_len,
+                            counts},
+                       {in.chunk_op, in.nchunk_from, in.nchunk_op, in.nop_chunk, in.nop_src_chunk}))
+    return c->fail(SDCAS_E_INVALID, "%s: an array is misaligned (u32 arrays 4 B, u64 8 B)", who);
+  return SDCAS_OK;
+}
+
+int sdcas_dev_family_store_moves(sdcas_ctx* c, const uint64_t* d_chunk_off, const uint32_t* d_chunk_op, size_t m,
+                                 const uint64_t* d_op_dst_off, const uint64_t* d_op_store_off, const uint64_t* d_ops,
+                                 size_t max_ops, const uint32_t* d_new_chunk_from, const uint64_t* d_new_chunk_off,
+                                 const uint64_t* d_new_chunk_len, const uint32_t* d_new_chunk_op,
+                                 const uint64_t* d_new_chunks, size_t max_chunks, const uint32_t* d_new_op_chunk,
+                                 const uint32_t* d_new_op_src_chunk, const uint64_t* d_new_op_dst_off,
+                                 const uint64_t* d_new_op_store_off, const uint64_t* d_new_ops, size_t max_new_ops,
+                                 uint64_t* d_move_dst, uint64_t* d_move_src, uint64_t* d_move_len, uint64_t* d_counts,
+                                 void* stream) {
+  const char* who = "dev_family_store_moves";
+  if (!c) return SDCAS_E_INVALID;
+  const FamilyMovesIn in{d_chunk_off,        d_chunk_op,       (uint32_t)m,          d_op_dst_off,     d_op_store_off,
+                         d_ops,              (uint32_t)max_ops, d_new_chunk_from,    d_new_chunk_off,  d_new_chunk_len,
+                         d_new_chunk_op,     d_new_chunks,     (uint32_t)max_chunks, d_new_op_chunk,   d_new_op_src_chunk,
+                         d_new_op_dst_off,   d_new_op_store_off, d_new_ops,          (uint32_t)max_new_ops};
+  if (int rc = family_moves_args(c, who, in, m, max_ops, max_chunks, max_new_ops, d_move_dst, d_move_src, d_move_len,
+                                 d_counts))
+    return rc;
+  DevCall call(c, stream);
+  if (call.rc) return call.rc;
+  if (int rc = grow_synced(c, c->fg_ws, (size_t)family_moves_layout(max_chunks).bytes, call.st,
+                           "family forget workspace"))
+    return rc;
+  hipError_t e = family_store_moves(c->fg_ws.p, in, d_move_dst, d_move_src, d_move_len, (unsigned long long*)d_counts,
+                                    call.st);
+  return e ? hip_fail_at(c, e, who, "") : SDCAS_OK;
+}
+
+int sdcas_family_store_moves(sdcas_ctx* c, const uint64_t* chunk_off, const uint32_t* chunk_op, size_t m,
+                             const uint64_t* op_dst_off, const uint64_t* op_store_off, size_t n_ops,
+                             const uint32_t* new_chunk_from, const uint64_t* new_chunk_off,
+                             const uint64_t* new_chunk_len, const uint32_t* new_chunk_op, size_t new_chunks,
+                             const uint32_t* new_op_chunk, const uint32_t* new_op_src_chunk,
+                             const uint64_t* new_op_dst_off, const uint64_t* new_op_store_off, size_t new_ops,
+                             uint64_t* out_move_dst, uint64_t* out_move_src, uint64_t* out_move_len,
+                             sdcas_family_moves_counts* out_counts) {
+  static_assert(sizeof(sdcas_family_moves_counts) == kFamilyMovesCounts * sizeof(uint64_t), "six u64 counts");
+  const char* who = "family_store_moves";
+  if (!c) return SDCAS_E_INVALID;
+  const uint64_t h_n[3] = {n_ops, new_chunks, new_ops};
+  const FamilyMovesIn h{chunk_off,      chunk_op,     0, op_dst_off,   op_store_off,     &h_n[0],        0,
+                        new_chunk_from, new_chunk_off, new_chunk_len, new_chunk_op,    &h_n[1],        0,
+                        new_op_chunk,   new_op_src_chunk, new_op_dst_off, new_op_store_off, &h_n[2],   0};
+  if (int rc = family_moves_args(c, who, h, m, n_ops, new_chunks, new_ops, out_move_dst, out_move_src, out_move_len,
+                                 out_counts))
+    return rc;
+  if (out_counts) memset(out_counts, 0, sizeof *out_counts);
+  DevCall call(c, nullptr);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  sdcas_family_moves_counts cts;
+  Parts p(c, st, who);
+  const auto d_chunk_off = p.in(chunk_off, m);
+  const auto d_chunk_op = p.in(chunk_op, m);
+  const auto d_op_dst = p.in(op_dst_off, n_ops);
+  const auto d_op_off = p.in(op_store_off, n_ops);
+  const auto d_from = p.in(new_chunk_from, new_chunks);
+  const auto d_noff = p.in(new_chunk_off, new_chunks);
+  const auto d_nlen = p.in(new_chunk_len, new_chunks);
+  const auto d_nop = p.in(new_chunk_op, new_chunks);
+  const auto d_nop_chunk = p.in(new_op_chunk, new_ops);
+  const auto d_nop_src = p.in(new_op_src_chunk, new_ops);
+  const auto d_nop_dst = p.in(new_op_dst_off, new_ops);
+  const auto d_nop_off = p.in(new_op_store_off, new_ops);
+  const auto d_n = p.in(h_n, 3);
+  const auto d_dst = p.out(out_move_dst, new_chunks);
+  const auto d_src = p.out(out_move_src, new_chunks);
+  const auto d_len = p.out(out_move_len, new_chunks);
+  const auto d_cts = p.out(&cts, 1);
+  if (int rc = p.reserve()) return rc;
+  if (int rc = grow_synced(c, c->fg_ws, (size_t)family_moves_layout(new_chunks).bytes, st, "family forget workspace"))
+    return rc;
+  if (int rc = p.upload()) return rc;
+  const uint64_t* dn = d_n;
+  const FamilyMovesIn in{d_chunk_off, d_chunk_op, (uint32_t)m, d_op_dst, d_op_off, dn, (uint32_t)n_ops,
+                         d_from,      d_noff,     d_nlen,      d_nop,    dn + 1,   (uint32_t)new_chunks,
+                         d_nop_chunk, d_nop_src,  d_nop_dst,   d_nop_off, dn + 2,  (uint32_t)new_ops};
+  if (hipError_t e = family_store_moves(c->fg_ws.p, in, d_dst, d_src, d_len, d_cts.as<unsigned long long>(), st))
+    return hip_fail_at(c, e, who, "");
+  if (int rc = p.counts(d_cts)) return rc;
+  if (cts.moves > new_chunks) return c->fail(SDCAS_E_HIP, "%s: counts out of range", who);
+  d_dst.first(cts.moves), d_src.first(cts.moves), d_len.first(cts.moves);
+  if (int rc = p.download()) return rc;
+  if (out_counts) *out_counts = cts;
+  return SDCAS_OK;
 }
 
 int sdcas_dev_set_sort(sdcas_ctx* c, int enable) {

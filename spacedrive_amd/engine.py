@@ -1432,7 +1432,107 @@ class Engine:
         return FamilyStore.of_files(self, paths, k=k, max_holders=max_holders, num=num, den=den, params=params,
                                     window_bytes=window_bytes)
 
+    # -- family store: forget rows (keep on the chunk arrays, moves from the old store to the new)
+    @staticmethod
+    def family_forget_plan(m, n_files):
+        """sdcas_family_forget_plan (no GPU) -> workspace_bytes: what keep and
+        moves share for m chunks of n_files rows; SdcasError beyond the ranges"""
+        ws = ctypes.c_uint64(0)
+        rc = N.load().sdcas_family_forget_plan(int(m), int(n_files), ctypes.byref(ws))
+        if rc != N.SDCAS_OK:
+            raise N.SdcasError(rc, f"family_forget_plan({m}, {n_files})")
+        return int(ws.value)
+
+    def family_chunks_keep(self, chunk_file, chunk_off, chunk_len, rep, family, keep):
+        """sdcas_family_chunks_keep over host arrays -> recipes.keep_chunks'
+        dict: "row_new" uint32[n], "row_from" uint32[n'], "family" int64[n'],
+        "chunk_from", "chunk_file" uint32[m'], "chunk_off", "chunk_len"
+        uint64[m'], "rep" int64[m'], "counts": sdcas_family_keep_counts' six
+        fields"""
+        fl, off = _arr(chunk_file, np.uint32), _arr(chunk_off, np.uint64)
+        ln, rp = _arr(chunk_len, np.uint64), _arr(rep, np.int64)
+        fam = _arr(family, np.int64)
+        kp = np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, np.uint8)
+        m, n = fl.size, fam.size
+        if off.size != m or ln.size != m or rp.size != m:
+            raise ValueError(f"family_chunks_keep: {m} chunk files, {off.size} offsets, {ln.size} lengths, "
+                             f"{rp.size} reps")
+        if kp.size != n:
+            raise ValueError(f"family_chunks_keep: {n} labels, {kp.size} keep flags")
+        row_new, row_from, out_family = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.int64)
+        c_from, c_file = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        c_off, c_len, c_rep = np.zeros(m, np.uint64), np.zeros(m, np.uint64), np.zeros(m, np.int64)
+        counts = N.FamilyKeepCounts()
+        self._check(self.L.sdcas_family_chunks_keep(self.ctx, _ptr(fl), _ptr(off), _ptr(ln), _ptr(rp), m, _ptr(fam),
+                                                    _ptr(kp), n, _ptr(row_new), _ptr(row_from), _ptr(out_family),
+                                                    _ptr(c_from), _ptr(c_file), _ptr(c_off), _ptr(c_len), _ptr(c_rep),
+                                                    ctypes.byref(counts)), "sdcas_family_chunks_keep")
+        n2, m2 = int(counts.rows_kept), int(counts.chunks_kept)
+        return {"row_new": row_new, "row_from": row_from[:n2].copy(), "family": out_family[:n2].copy(),
+                "chunk_from": c_from[:m2].copy(), "chunk_file": c_file[:m2].copy(), "chunk_off": c_off[:m2].copy(),
+                "chunk_len": c_len[:m2].copy(), "rep": c_rep[:m2].copy(), "counts": counts.as_dict()}
+
+    def family_store_moves(self, old_recipes, old_layout, new_recipes, new_layout, chunk_from, chunk_len):
+        """sdcas_family_store_moves over host arrays, with recipes.store_moves'
+        arguments -> its dict: "move_dst", "move_src", "move_len" uint64[moves],
+        "counts": sdcas_family_moves_counts' six fields"""
+        coff, cop = _arr(old_recipes["chunk_off"], np.uint64), _arr(old_recipes["chunk_op"], np.uint32)
+        odst, ooff = _arr(old_recipes["op_dst_off"], np.uint64), _arr(old_layout["op_store_off"], np.uint64)
+        nfrom, nlen = _arr(chunk_from, np.uint32), _arr(chunk_len, np.uint64)
+        noff, nop = _arr(new_recipes["chunk_off"], np.uint64), _arr(new_recipes["chunk_op"], np.uint32)
+        noc, nosc = _arr(new_recipes["op_chunk"], np.uint32), _arr(new_recipes["op_src_chunk"], np.uint32)
+        ndst, nso = _arr(new_recipes["op_dst_off"], np.uint64), _arr(new_layout["op_store_off"], np.uint64)
+        m, k, m2, k2 = coff.size, odst.size, nfrom.size, noc.size
+        if cop.size != m or ooff.size != k:
+            raise ValueError("family_store_moves: the old layout is of other recipes")
+        if nlen.size != m2 or noff.size != m2 or nop.size != m2 or nosc.size != k2 or ndst.size != k2 or \
+                nso.size != k2:
+            raise ValueError("family_store_moves: the new arrays differ in length")
+        dst, src, ln = np.zeros(m2, np.uint64), np.zeros(m2, np.uint64), np.zeros(m2, np.uint64)
+        counts = N.FamilyMovesCounts()
+        self._check(self.L.sdcas_family_store_moves(self.ctx, _ptr(coff), _ptr(cop), m, _ptr(odst), _ptr(ooff), k,
+                                                    _ptr(nfrom), _ptr(noff), _ptr(nlen), _ptr(nop), m2, _ptr(noc),
+                                                    _ptr(nosc), _ptr(ndst), _ptr(nso), k2, _ptr(dst), _ptr(src),
+                                                    _ptr(ln), ctypes.byref(counts)), "sdcas_family_store_moves")
+        j = int(counts.moves)
+        return {"move_dst": dst[:j].copy(), "move_src": src[:j].copy(), "move_len": ln[:j].copy(),
+                "counts": counts.as_dict()}
+
     # -- device-resident (pointers are ints: device addresses, e.g. tensor.data_ptr())
+    def dev_family_chunks_keep(self, chunk_file, chunk_off, chunk_len, rep, m, family, keep, n_files, row_new=0,
+                               row_from=0, family_out=0, chunk_from=0, chunk_file_out=0, chunk_off_out=0,
+                               chunk_len_out=0, rep_out=0, counts=0, stream=0):
+        """family_chunks_keep over device arrays (sdcas_dev_family_chunks_keep):
+        keep uint8[n_files]; the row outputs hold n_files entries and the chunk
+        outputs m, counts six uint64; any output may be 0. The outputs are
+        dev_family_recipes' inputs as they are, with counts + 2 words the new
+        number of chunks"""
+        self._check(self.L.sdcas_dev_family_chunks_keep(self.ctx, chunk_file or None, chunk_off or None,
+                                                        chunk_len or None, rep or None, int(m), family or None,
+                                                        keep or None, int(n_files), row_new or None, row_from or None,
+                                                        family_out or None, chunk_from or None, chunk_file_out or None,
+                                                        chunk_off_out or None, chunk_len_out or None, rep_out or None,
+                                                        counts or None, stream or None), "dev_family_chunks_keep")
+
+    def dev_family_store_moves(self, chunk_off, chunk_op, m, op_dst_off, op_store_off, ops, max_ops, new_chunk_from,
+                               new_chunk_off, new_chunk_len, new_chunk_op, new_chunks, max_chunks, new_op_chunk,
+                               new_op_src_chunk, new_op_dst_off, new_op_store_off, new_ops, max_new_ops, move_dst=0,
+                               move_src=0, move_len=0, counts=0, stream=0):
+        """family_store_moves over device arrays (sdcas_dev_family_store_moves):
+        ops, new_chunks and new_ops are device uint64 (the old recipes' counts +
+        2 words, keep's counts + 2, the new recipes' counts + 2); the move arrays
+        hold max_chunks entries, counts six uint64, whose first word is the
+        number of moves: dev_family_restore's `ops` when the moves are carried"""
+        self._check(self.L.sdcas_dev_family_store_moves(self.ctx, chunk_off or None, chunk_op or None, int(m),
+                                                        op_dst_off or None, op_store_off or None, ops or None,
+                                                        int(max_ops), new_chunk_from or None, new_chunk_off or None,
+                                                        new_chunk_len or None, new_chunk_op or None,
+                                                        new_chunks or None, int(max_chunks), new_op_chunk or None,
+                                                        new_op_src_chunk or None, new_op_dst_off or None,
+                                                        new_op_store_off or None, new_ops or None, int(max_new_ops),
+                                                        move_dst or None, move_src or None, move_len or None,
+                                                        counts or None, stream or None), "dev_family_store_moves")
+
     def dev_chunk_index_match(self, idx_keys, idx_digests, idx_values, idx_dir, n, bits, keys, digests, valid, m,
                               pos=0, value=0, counts=0, stream=0):
         """chunk_index_match over device arrays (sdcas_dev_chunk_index_match);

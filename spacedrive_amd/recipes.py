@@ -169,3 +169,125 @@ def restore_from_store(recipes, layout, store, rows=None):
         for r in range(np.asarray(recipes["row_ops"]).size):
             done.setdefault(r, b"")
     return done
+
+
+_NO32 = 0xFFFFFFFF
+
+
+def keep_chunks(chunk_file, chunk_off, chunk_len, rep, family, keep):
+    """sdcas_family_chunks_keep on the host (include/sdcas.h, "family store:
+    forget rows"): the chunk arrays of the rows with keep != 0, rows and chunks
+    renumbered densely, classes and labels elected again among the survivors. ->
+    {"row_new": uint32[n] (0xFFFFFFFF: removed), "row_from": uint32[n'],
+    "family": int64[n'], "chunk_from": uint32[m'], "chunk_file": uint32[m'],
+    "chunk_off", "chunk_len": uint64[m'], "rep": int64[m'], "counts":
+    sdcas_family_keep_counts' six fields}. The outputs are valid inputs of the
+    recipes and of another keep."""
+    fl, off = np.asarray(chunk_file, np.uint32).reshape(-1), np.asarray(chunk_off, np.uint64).reshape(-1)
+    ln, rp = np.asarray(chunk_len, np.uint64).reshape(-1), np.asarray(rep, np.int64).reshape(-1)
+    fam, kp = np.asarray(family, np.int64).reshape(-1), np.asarray(keep).reshape(-1) != 0
+    m, n = fl.size, fam.size
+    if off.size != m or ln.size != m or rp.size != m:
+        raise ValueError(f"keep_chunks: {m} chunk files, {off.size} offsets, {ln.size} lengths, {rp.size} reps")
+    if kp.size != n:
+        raise ValueError(f"keep_chunks: {n} labels, {kp.size} keep flags")
+    row_from = np.flatnonzero(kp)
+    row_new = np.full(n, _NO32, np.uint32)
+    row_new[row_from] = np.arange(row_from.size, dtype=np.uint32)
+    # a label's lowest kept row that takes part
+    part = kp & (fam >= 0) & (fam < n)
+    low = np.full(n, n, np.int64)
+    rows = np.flatnonzero(part)
+    np.minimum.at(low, fam[rows], rows)
+    out_family = np.full(row_from.size, -1, np.int64)
+    sel = part[row_from]
+    out_family[sel] = row_new[low[fam[row_from[sel]]]]
+    # the chunks of the kept rows
+    sv = fl < n
+    sv[sv] = kp[fl[sv]]
+    chunk_from = np.flatnonzero(sv)
+    chunk_new = np.full(m, -1, np.int64)
+    chunk_new[chunk_from] = np.arange(chunk_from.size)
+    pos = np.arange(m, dtype=np.int64)
+    r = np.where((rp >= 0) & (rp <= pos), rp, pos)
+    lowc = np.full(m, m, np.int64)
+    np.minimum.at(lowc, r[chunk_from], chunk_from)
+    counts = {"rows_kept": int(row_from.size), "rows_removed": int(n - row_from.size),
+              "chunks_kept": int(chunk_from.size), "chunks_removed": int(m - chunk_from.size),
+              "bytes_kept": int(ln[sv].sum(dtype=np.uint64)) if m else 0,
+              "bytes_removed": int(ln[~sv].sum(dtype=np.uint64)) if m else 0}
+    return {"row_new": row_new, "row_from": row_from.astype(np.uint32), "family": out_family,
+            "chunk_from": chunk_from.astype(np.uint32), "chunk_file": row_new[fl[chunk_from]],
+            "chunk_off": off[chunk_from], "chunk_len": ln[chunk_from],
+            "rep": chunk_new[lowc[r[chunk_from]]].astype(np.int64), "counts": counts}
+
+
+def store_moves(old_recipes, old_layout, new_recipes, new_layout, chunk_from, chunk_len):
+    """sdcas_family_store_moves on the host: where the literal chunks of the new
+    recipes lie in the old store, neighbours merged into ranges. The recipes
+    carry "chunk_off" and "chunk_op" (Engine.family_recipes' dicts); chunk_from
+    and chunk_len are keep_chunks' over the new chunks. -> {"move_dst",
+    "move_src", "move_len": uint64[moves], "counts": sdcas_family_moves_counts'
+    six fields}. A literal chunk without a place in the old store gets no move
+    and is counted as lost."""
+    coff, cop = np.asarray(old_recipes["chunk_off"], np.uint64), np.asarray(old_recipes["chunk_op"], np.uint32)
+    odst, ooff = np.asarray(old_recipes["op_dst_off"], np.uint64), np.asarray(old_layout["op_store_off"], np.uint64)
+    nfrom, nlen = np.asarray(chunk_from, np.uint32).reshape(-1), np.asarray(chunk_len, np.uint64).reshape(-1)
+    noff, nop = np.asarray(new_recipes["chunk_off"], np.uint64), np.asarray(new_recipes["chunk_op"], np.uint32)
+    noc, nosc = np.asarray(new_recipes["op_chunk"], np.uint32), np.asarray(new_recipes["op_src_chunk"], np.uint32)
+    ndst, nso = np.asarray(new_recipes["op_dst_off"], np.uint64), np.asarray(new_layout["op_store_off"], np.uint64)
+    m, k, m2, k2 = coff.size, odst.size, nfrom.size, noc.size
+    if cop.size != m or ooff.size != k:
+        raise ValueError("store_moves: the old layout is of other recipes")
+    if nlen.size != m2 or noff.size != m2 or nop.size != m2 or nosc.size != k2 or ndst.size != k2 or nso.size != k2:
+        raise ValueError("store_moves: the new arrays differ in length")
+    none = np.uint64(STORE_NONE)
+    z64, z32 = np.zeros(1, np.uint64), np.zeros(1, np.uint32)
+    # old_at
+    ok = nfrom < m
+    c = np.where(ok, nfrom, 0).astype(np.int64)
+    o = (cop if m else z32)[c]
+    ok &= o < k
+    o = np.where(ok, o, 0).astype(np.int64)
+    so, d, at_file = (ooff if k else z64)[o], (odst if k else z64)[o], (coff if m else z64)[c]
+    ok &= (so != none) & (at_file >= d)
+    at = so + (at_file - d)
+    ok &= at != none
+    # the literal chunks and their places in the new store
+    lit = nop < k2
+    o2 = np.where(lit, nop, 0).astype(np.int64)
+    lit &= (noc if k2 else z32)[o2] == (nosc if k2 else z32)[o2]
+    new_at = (nso if k2 else z64)[o2] + (noff - (ndst if k2 else z64)[o2])
+    has = lit & ok
+    cont = np.zeros(m2, bool)
+    if m2 > 1:
+        cont[1:] = has[1:] & has[:-1] & (nop[1:] == nop[:-1]) & (at[1:] == at[:-1] + nlen[:-1])
+    head = has & ~cont
+    move = np.cumsum(head) - 1
+    moves = int(head.sum())
+    move_len = np.zeros(moves, np.uint64)
+    np.add.at(move_len, move[has], nlen[has])
+    lost = lit & ~ok
+    counts = {"moves": moves, "literal_chunks": int(lit.sum()),
+              "moved_bytes": int(move_len.sum(dtype=np.uint64)) if moves else 0, "lost_chunks": int(lost.sum()),
+              "lost_bytes": int(nlen[lost].sum(dtype=np.uint64)) if m2 else 0,
+              "longest_move": int(move_len.max()) if moves else 0}
+    return {"move_dst": new_at[head], "move_src": at[head], "move_len": move_len, "counts": counts}
+
+
+def apply_moves(moves, old_store, store_bytes=None):
+    """The new store: every move's bytes from the old one, out of place ->
+    uint8[store_bytes] (None: up to the last move's end; the moves of a
+    removal cover the new store). ValueError for a move outside either."""
+    dst, src = np.asarray(moves["move_dst"], np.uint64), np.asarray(moves["move_src"], np.uint64)
+    ln = np.asarray(moves["move_len"], np.uint64)
+    old = np.asarray(old_store, np.uint8).reshape(-1)
+    if store_bytes is None:
+        store_bytes = max((int(d) + int(n) for d, n in zip(dst, ln)), default=0)
+    new = np.zeros(int(store_bytes), np.uint8)
+    for d, s, n in zip(dst, src, ln):
+        d, s, n = int(d), int(s), int(n)
+        if d + n > new.size or s + n > old.size:
+            raise ValueError(f"apply_moves: a move of {n} bytes from {s} to {d} leaves a store ({old.size} -> {new.size})")
+        new[d:d + n] = old[s:s + n]
+    return new

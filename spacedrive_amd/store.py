@@ -11,6 +11,7 @@ from .recipes import STORE_NONE, store_layout
 
 _OP32 = ("op_chunk", "op_src_chunk", "op_row", "op_src_row")
 _OP64 = ("op_dst_off", "op_src_off", "op_len")
+_CHUNKS = ("chunk_file", "chunk_len", "rep", "family")  # what `remove` needs besides the recipes' chunk_off
 _SLACK = 64   # readable bytes sdcas_dev_hash_messages wants after every message
 _ALIGN = 128  # rows start on line boundaries in a window
 
@@ -24,24 +25,34 @@ class FamilyStore:
     """recipes: Engine.family_recipes' dict; layout: Engine.family_store_layout's;
     store: uint8[store_bytes], the literal ops' bytes; sizes uint64[n] and
     digests uint8[n, 32]: every row's length and BLAKE3. Rows are numbered as
-    the recipes number them. `restore` and `verify` run on the engine's GPU
-    (engine None: default_engine()); everything else needs none."""
+    the recipes number them. chunks (optional): {"chunk_file" uint32[m],
+    "chunk_len" uint64[m], "rep" int64[m], "family" int64[n]}, the recipes'
+    inputs, which `remove` needs; a store without them does everything else.
+    `restore`, `verify` and `remove` run on the engine's GPU (engine None:
+    default_engine()); everything else needs none."""
 
-    def __init__(self, recipes, layout, store, sizes, digests, engine=None):
+    def __init__(self, recipes, layout, store, sizes, digests, engine=None, chunks=None):
         self.recipes, self.layout = recipes, layout
+        self.chunks = None if chunks is None else {
+            "chunk_file": np.ascontiguousarray(chunks["chunk_file"], np.uint32).reshape(-1),
+            "chunk_len": np.ascontiguousarray(chunks["chunk_len"], np.uint64).reshape(-1),
+            "rep": np.ascontiguousarray(chunks["rep"], np.int64).reshape(-1),
+            "family": np.ascontiguousarray(chunks["family"], np.int64).reshape(-1)}
         self.store = np.ascontiguousarray(store, np.uint8).reshape(-1)
         self.sizes = np.ascontiguousarray(sizes, np.uint64).reshape(-1)
         self.digests = np.ascontiguousarray(digests, np.uint8).reshape(-1, 32)
         self.engine = engine
         self._dev = None
-        self.check(self.recipes, self.layout, self.store, self.sizes, self.digests)
+        self.check(self.recipes, self.layout, self.store, self.sizes, self.digests, chunks=self.chunks)
 
     # -- the check a store passes before it is used (no GPU) ---------------------------
     @staticmethod
-    def check(recipes, layout, store, sizes, digests, what="FamilyStore"):
+    def check(recipes, layout, store, sizes, digests, what="FamilyStore", chunks=None):
         """ValueError unless the parts make a store: array lengths, `ops`
         consistent, rows and chunk_op in range, every op inside its row, the
-        layout that of the recipes, every offset within the store"""
+        layout that of the recipes, every offset within the store; with chunk
+        arrays, their lengths against chunk_op, chunk_file in range and the
+        chunks of every row that takes part adding up to its size"""
         ops = [np.asarray(recipes[k]) for k in _OP32 + _OP64]
         k, n = ops[0].size, np.asarray(sizes).size
         if not all(a.size == k for a in ops):
@@ -75,6 +86,22 @@ class FamilyStore:
         o, l = off.astype(np.uint64)[has], ln[has]
         if ((o > size) | (l > np.uint64(size) - np.minimum(o, np.uint64(size)))).any():
             raise ValueError(f"{what}: an op's bytes lie outside the store")
+        if chunks is not None:
+            fl, cl = np.asarray(chunks["chunk_file"], np.uint32), np.asarray(chunks["chunk_len"], np.uint64)
+            fam, m = np.asarray(chunks["family"], np.int64), chunk_op.size
+            if fl.size != m or cl.size != m or np.asarray(chunks["rep"]).size != m or \
+                    np.asarray(recipes.get("chunk_off", ())).size != m:
+                raise ValueError(f"{what}: {m} entries of chunk_op, other numbers of chunk_file, chunk_len, rep or "
+                                 f"chunk_off")
+            if fam.size != n:
+                raise ValueError(f"{what}: {n} sizes, {fam.size} family labels")
+            if (fl >= n).any():
+                raise ValueError(f"{what}: chunk_file names a row past {n}")
+            sums = np.zeros(n, np.uint64)
+            np.add.at(sums, fl.astype(np.int64), cl)
+            part = (fam >= 0) & (fam < n)
+            if (sums[part] != np.asarray(sizes, np.uint64)[part]).any():
+                raise ValueError(f"{what}: a row's chunks do not add up to its size")
 
     # -- across runs ---------------------------------------------------------------------
     def save(self, path):
@@ -85,6 +112,9 @@ class FamilyStore:
         parts["recipes_counts"] = np.array([r["counts"][name] for name, _ in N.FamilyRecipesCounts._fields_], np.uint64)
         parts["layout_counts"] = np.array([l["counts"][name] for name, _ in N.FamilyStoreCounts._fields_], np.uint64)
         parts["op_store_off"] = np.asarray(l["op_store_off"], np.uint64)
+        if self.chunks is not None:  # extra arrays: a reader that does not know them ignores them
+            parts.update({"chunks_" + k: self.chunks[k] for k in _CHUNKS})
+            parts["chunks_chunk_off"] = np.asarray(r["chunk_off"], np.uint64)
         with open(path, "wb") as f:
             np.savez(f, store=self.store, sizes=self.sizes, digests=self.digests, **parts)
 
@@ -100,6 +130,12 @@ class FamilyStore:
                 off = z["op_store_off"].astype(np.uint64)
                 store, sizes, digests = z["store"].astype(np.uint8), z["sizes"].astype(np.uint64), \
                     z["digests"].astype(np.uint8)
+                chunks = None  # a store saved before the chunk arrays were kept has none, and does all but `remove`
+                if all("chunks_" + k in z.files for k in _CHUNKS + ("chunk_off",)):
+                    chunks = {"chunk_file": z["chunks_chunk_file"].astype(np.uint32),
+                              "chunk_len": z["chunks_chunk_len"].astype(np.uint64),
+                              "rep": z["chunks_rep"].astype(np.int64), "family": z["chunks_family"].astype(np.int64)}
+                    recipes["chunk_off"] = z["chunks_chunk_off"].astype(np.uint64)
         except (zipfile.BadZipFile, KeyError, EOFError, OSError, ValueError) as e:
             raise ValueError(f"{path}: not a saved family store ({e})") from e
         if rc.size != len(N.FamilyRecipesCounts._fields_) or lc.size != len(N.FamilyStoreCounts._fields_):
@@ -107,8 +143,8 @@ class FamilyStore:
         recipes["counts"] = {name: int(v) for (name, _), v in zip(N.FamilyRecipesCounts._fields_, rc)}
         recipes["op_literal"] = recipes["op_chunk"] == recipes["op_src_chunk"]
         layout = {"op_store_off": off, "counts": {name: int(v) for (name, _), v in zip(N.FamilyStoreCounts._fields_, lc)}}
-        cls.check(recipes, layout, store, sizes, digests, os.fspath(path))
-        return cls(recipes, layout, store, sizes, digests, engine)
+        cls.check(recipes, layout, store, sizes, digests, os.fspath(path), chunks=chunks)
+        return cls(recipes, layout, store, sizes, digests, engine, chunks)
 
     # -- on the device -------------------------------------------------------------------
     def _engine(self):
@@ -253,15 +289,121 @@ class FamilyStore:
             bad += [r for j, r in enumerate(group) if not np.array_equal(got[j], self.digests[r])]
         return sorted(bad)
 
+    # -- forgetting rows -------------------------------------------------------------------
+    def remove(self, rows):
+        """-> (FamilyStore, row_from): the store without `rows`, equal to the
+        one built from the remaining files alone, and per new row its old
+        number. No file is read: the chunk arrays lose the rows' chunks
+        (dev_family_chunks_keep), the recipes and the layout run over the rest,
+        and every literal byte of the new store is carried from where it lies
+        in the old one (dev_family_store_moves, then the mover), all on the
+        device. This object stays as it is. ValueError for a store without
+        chunk arrays or a row out of range; SdcasError SDCAS_E_CAPACITY when
+        the two stores do not fit in device memory."""
+        import torch
+        if self.chunks is None:
+            raise ValueError("FamilyStore.remove: the store carries no chunk arrays (it was saved before they were kept)")
+        n = self.sizes.size
+        gone = sorted({int(r) for r in rows})
+        if any(not 0 <= r < n for r in gone):
+            raise ValueError(f"FamilyStore.remove: a row outside [0, {n})")
+        keep = np.ones(n, np.uint8)
+        keep[np.array(gone, np.int64)] = 0
+        d, eng, ch, r = self._device(), self._engine(), self.chunks, self.recipes
+        dev, m, k = d["device"], ch["chunk_file"].size, d["k"]
+        n2 = int(keep.sum())
+        m2 = int(keep[ch["chunk_file"].astype(np.int64)].sum())  # check: chunk_file < n
+
+        def room(count, dtype):
+            return torch.zeros(max(int(count), 2), dtype=dtype, device=dev)
+
+        def down(t, count, dtype):
+            return t[:int(count)].cpu().numpy().view(dtype).copy()
+
+        i32, i64, st = torch.int32, torch.int64, d["stream"].cuda_stream
+        with torch.cuda.stream(d["stream"]):
+            o_file, o_off, o_len, o_rep, o_fam, o_keep, o_chunk_op, o_dst = (self._up(a, dev) for a in (
+                ch["chunk_file"], np.asarray(r["chunk_off"], np.uint64), ch["chunk_len"], ch["rep"], ch["family"], keep,
+                np.asarray(r["chunk_op"], np.uint32), np.asarray(r["op_dst_off"], np.uint64)))
+            row_from, fam2 = room(n, i32), room(n, i64)
+            c_from, c_file, c_off, c_len, c_rep = room(m, i32), room(m, i32), room(m, i64), room(m, i64), room(m, i64)
+            kc, rc, lc, mc = room(6, i64), room(8, i64), room(6, i64), room(6, i64)
+            eng.dev_family_chunks_keep(o_file.data_ptr(), o_off.data_ptr(), o_len.data_ptr(), o_rep.data_ptr(), m,
+                                       o_fam.data_ptr(), o_keep.data_ptr(), n, 0, row_from.data_ptr(),
+                                       fam2.data_ptr(), c_from.data_ptr(), c_file.data_ptr(), c_off.data_ptr(),
+                                       c_len.data_ptr(), c_rep.data_ptr(), kc.data_ptr(), st)
+            op32 = [room(m2, i32) for _ in range(4)]
+            op64 = [room(m2, i64) for _ in range(3)]
+            chunk_op, row_ops, row_first, off2 = room(m2, i32), room(n2, i32), room(n2, i32), room(m2, i64)
+            eng.dev_family_recipes(c_file.data_ptr(), c_off.data_ptr(), c_len.data_ptr(), c_rep.data_ptr(), m2,
+                                   fam2.data_ptr(), n2, *(t.data_ptr() for t in op32 + op64), chunk_op.data_ptr(),
+                                   row_ops.data_ptr(), row_first.data_ptr(), rc.data_ptr(), st)
+            eng.dev_family_store_layout(*(t.data_ptr() for t in op32 + op64), chunk_op.data_ptr(), m2,
+                                        rc.data_ptr() + 16, m2, off2.data_ptr(), lc.data_ptr(), st)
+            mv_dst, mv_src, mv_len = room(m2, i64), room(m2, i64), room(m2, i64)
+            eng.dev_family_store_moves(o_off.data_ptr(), o_chunk_op.data_ptr(), m, o_dst.data_ptr(),
+                                       d["off"].data_ptr(), d["ops"].data_ptr(), k, c_from.data_ptr(),
+                                       c_off.data_ptr(), c_len.data_ptr(), chunk_op.data_ptr(), kc.data_ptr() + 16, m2,
+                                       op32[0].data_ptr(), op32[1].data_ptr(), op64[0].data_ptr(), off2.data_ptr(),
+                                       rc.data_ptr() + 16, m2, mv_dst.data_ptr(), mv_src.data_ptr(), mv_len.data_ptr(),
+                                       mc.data_ptr(), st)
+            kcs, rcs, lcs, mcs = (down(t, c, np.uint64) for t, c in ((kc, 6), (rc, 8), (lc, 6), (mc, 6)))
+            if int(kcs[0]) != n2 or int(kcs[2]) != m2:
+                raise RuntimeError("FamilyStore.remove: the device kept other rows or chunks than the host counted")
+            if int(mcs[3]):
+                raise ValueError(f"FamilyStore.remove: {int(mcs[3])} literal chunks of the new store have no place in "
+                                 f"the old one")
+            ops2, size2 = int(rcs[2]), int(lcs[4])
+            if size2 > self.store.size:
+                raise RuntimeError("FamilyStore.remove: the new store is larger than the old one")
+            free, _ = torch.cuda.mem_get_info(dev)
+            if size2 + 32 > free:
+                raise N.SdcasError(N.SDCAS_E_CAPACITY, f"FamilyStore.remove: a second store of {size2} bytes does not "
+                                                       f"fit in the {free} bytes free on the device")
+            try:
+                store2 = torch.zeros(size2 + 32, dtype=torch.uint8, device=dev)
+            except torch.cuda.OutOfMemoryError as e:
+                raise N.SdcasError(N.SDCAS_E_CAPACITY, f"FamilyStore.remove: a second store of {size2} bytes: {e}") from e
+            # the moves as the mover's ops: one row, one window over the new store
+            zero_rows = room(m2, i32)
+            w_at, w_len = self._up(np.zeros(1, np.uint64), dev), self._up(np.array([size2], np.uint64), dev)
+            moved = room(4, i64)
+            eng.dev_family_restore(zero_rows.data_ptr(), mv_dst.data_ptr(), mv_len.data_ptr(), mv_src.data_ptr(),
+                                   mc.data_ptr(), m2, w_at.data_ptr(), 0, w_len.data_ptr(), 1, d["store"].data_ptr(),
+                                   self.store.size, store2.data_ptr(), size2, moved.data_ptr(), st)
+            mvd = down(moved, 4, np.uint64)
+            if int(mvd[1]) != size2 or int(mvd[2]):
+                raise RuntimeError(f"FamilyStore.remove: {int(mvd[1])} of {size2} bytes moved, {int(mvd[2])} bad moves")
+            names = ("op_chunk", "op_src_chunk", "op_row", "op_src_row", "op_dst_off", "op_src_off", "op_len")
+            recipes = {name: down(t, ops2, np.uint32 if t.dtype == i32 else np.uint64)
+                       for name, t in zip(names, op32 + op64)}
+            recipes.update({"op_literal": recipes["op_chunk"] == recipes["op_src_chunk"],
+                            "chunk_op": down(chunk_op, m2, np.uint32), "row_ops": down(row_ops, n2, np.uint32),
+                            "row_first_op": down(row_first, n2, np.uint32), "chunk_off": down(c_off, m2, np.uint64),
+                            "counts": {name: int(v) for (name, _), v in zip(N.FamilyRecipesCounts._fields_, rcs)}})
+            layout = {"op_store_off": down(off2, ops2, np.uint64),
+                      "counts": {name: int(v) for (name, _), v in zip(N.FamilyStoreCounts._fields_, lcs)}}
+            chunks = {"chunk_file": down(c_file, m2, np.uint32), "chunk_len": down(c_len, m2, np.uint64),
+                      "rep": down(c_rep, m2, np.int64), "family": down(fam2, n2, np.int64)}
+            frm = down(row_from, n2, np.uint32)
+            store = store2[:size2].cpu().numpy()
+        sel = frm.astype(np.int64)
+        return FamilyStore(recipes, layout, store, self.sizes[sel], self.digests[sel], self.engine, chunks), frm
+
     # -- from files ------------------------------------------------------------------------
     @classmethod
     def of_files(cls, engine, paths, k=4, max_holders=64, num=1, den=2, params=None, window_bytes=256 << 20):
         """Engine.store_files"""
         import torch
         paths = [os.fspath(p) for p in paths]
-        found = engine.similar_recipes(paths, k=k, max_holders=max_holders, num=num, den=den, params=params,
-                                       window_bytes=window_bytes)
-        recipes, sizes = found["recipes"], np.asarray(found["sizes"], np.uint64)
+        # similar_recipes' steps, keeping the recipes' inputs: `remove` needs them
+        from .engine import ChunkHolders
+        ids = np.arange(len(paths), dtype=np.uint64)
+        found = engine.similar_files_indexed(paths, ids, ChunkHolders(engine), params, window_bytes, peers=int(k),
+                                             max_holders=max_holders, chunks=True)
+        fam, fl, ln, rep = engine._family_inputs([found], [ids], num, den, "store_files")
+        chunks = {"chunk_file": fl, "chunk_len": ln, "rep": rep, "family": fam["family"]}
+        recipes, sizes = engine.family_recipes(fl, ln, rep, fam["family"]), np.asarray(found["sizes"], np.uint64)
         layout = engine.family_store_layout(recipes)
         store_bytes, n = int(layout["counts"]["store_bytes"]), len(paths)
         device = torch.device(f"cuda:{engine.device_ordinal}")
@@ -314,4 +456,4 @@ class FamilyStore:
             from .engine import io_error
             i = int(np.flatnonzero(st)[0])
             raise io_error(int(st[i]), paths[i])
-        return cls(recipes, layout, store, sizes, digests, engine)
+        return cls(recipes, layout, store, sizes, digests, engine, chunks)
