@@ -24,6 +24,11 @@ arrays against the remove's, the match's pos / value / holders / counts.
 --count-only prints the byte and request model without a device. No threshold
 is set: the numbers go to profiles/chunk_holders.json and DESIGN.md §3.8.
 
+This tool is no longer the only place where the block scan's third level (2^24
+entries and more, so its sizes from 2^24 + 1 on, 2^26 among them) is checked:
+tests/test_gpu_index_scale.py compares the remove, the add and the match with a
+torch reference at 2^24 + 1 to 2^25 + 257 entries, every output element.
+
 The model. Remove: every entry is read once (48 bytes) and the kept ones are
 written once (48 bytes each); per entry one search of `removed` by halving,
 ceil_log2(r + 1) dependent 8-byte reads of an array of 8 r bytes; 32 bytes of

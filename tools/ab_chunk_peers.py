@@ -25,6 +25,11 @@ compared with the tool's own numpy reference.
 --count-only prints the request and byte model without a device. No ratio is
 set in advance: the numbers go to profiles/chunk_peers.json and DESIGN.md §3.9.
 
+The batches here have about 2.7 M pairs; only the plan's bound at H = 64 (2^26
+places, nearly all of them empty) is sized past the scans' third level. Pairs
+and chunks past 2^24, where that level carries sums, are covered by the suite:
+tests/test_gpu_index_scale.py, both modes, against a dense torch reference.
+
 The model. Per chunk three halvings (the pair's two bounds inside its bucket,
 the triple's lower bound) and 16 bytes of run description written; the scan of
 the counts; per pair place one halving in the offsets (ceil_log2(m) steps) and
